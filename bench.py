@@ -11,9 +11,10 @@ channel simulator (synthetic, distinct per run and per frame) and are resident i
 What one invocation does (rank 0 prints ONE JSON line, contract in the task statement):
   1. parity gate (before anything is timed): the first runs are trained from the Dirac start on the GPU and by the CPU oracle on the same
      samples; per-step ELBO, taps and the epilogue's SER must agree (tolerances below) or the process exits non-zero -> ``parity``;
-  2. W warm-up steps, then timed regions of EXACTLY K steps each (barrier + synchronize on both sides, max over ranks), repeated until
-     --min-seconds of timed GPU work has accumulated; ``value`` is the MEDIAN region (``timed_regions`` / ``region_ms`` say how many and
-     how they spread); per-launch HIP-event times -> ``roofline`` (HBM and flop fractions, measured stream-copy bandwidth);
+  2. W warm-up steps, then ONE timed region of EXACTLY K steps (barrier + synchronize on both sides, max over ranks); --min-seconds S > 0
+     repeats the region until S seconds of timed GPU work have accumulated, and ``value`` is then the MEDIAN region (``timed_regions`` /
+     ``region_ms`` say how many and how they spread); per-launch HIP-event times -> ``roofline`` (HBM and flop fractions, measured
+     stream-copy bandwidth); --dump-outputs DIR writes what the last timed step returned (see dump_outputs);
   3. N = 1 only, all untimed for the headline: ``extra.pipeline`` (generate -> train -> epilogue per frame, compact mode),
      ``extra.configs`` (config 4 VAEflex and config 2 AWGN kernel rates), ``cpu_baseline`` (the C oracle on the host cores).
 
@@ -230,6 +231,30 @@ def cpu_baseline(frame_rx, t, var, lr, target_s, threads, note=""):
             "reference_dp_symbols_per_s": REFERENCE_DP_SYMBOLS_PER_S}
 
 
+DUMP_BYTES_PER_GROUP = 32 << 20       # --dump-outputs: the per-run result arrays and the per-symbol arrays get 32 MB each (64 MB in all)
+
+
+def dump_outputs(out, eng, directory):
+    """What the last timed step handed its caller, as float32 .npy files: loss [r,1,steps], var_est [r,1,2,steps] and the trained taps W [r,2,4,M],
+    h [r,2,2,2,M] for every run (a fixed seeded sample of runs beyond 32 MB), q [r',1,2,2n,N] and y [r',1,2,2,N] for a fixed seeded sample of runs.
+    The samples depend only on the run count, so two builds run with the same arguments write the same runs."""
+    os.makedirs(directory, exist_ok=True)
+    R = eng.R
+    per_run = {"loss": out["loss"], "var_est": out["var_est"], "W": eng.W, "h": eng.h}
+    per_symbol = {"q": out["q"], "y": out["y"]}
+    written = {}
+    for group in (per_run, per_symbol):
+        run_bytes = sum(t[0].numel() * t.element_size() for t in group.values())
+        n = max(1, min(R, DUMP_BYTES_PER_GROUP // run_bytes))
+        runs = np.arange(R) if n == R else np.sort(np.random.default_rng(0).choice(R, n, replace=False))
+        idx = torch.from_numpy(runs).to(eng.W.device)
+        for name, t in group.items():
+            a = t.index_select(0, idx).cpu().numpy().astype(np.float32, copy=False)
+            np.save(os.path.join(directory, name + ".npy"), a)
+            written[name] = list(a.shape)
+    return written
+
+
 def _event_ms(fn, n):
     """n launches of fn() on the current stream, each bracketed by HIP events -> list of ms."""
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
@@ -431,7 +456,9 @@ def main():
     ap.add_argument("--runs", type=int, default=0, help="independent runs per GPU (one workgroup each); 0 = 4 x the number of runs "
                     "the device keeps co-resident (vaeq_dp_resident_runs), i.e. four full rounds, no ragged tail")
     ap.add_argument("--threads", type=int, default=0, help="workgroup size per run (0 = library default)")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-step timed region until this much timed GPU work has accumulated")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the K-step timed region until this much timed GPU work has accumulated "
+                    "(0 = one region: exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned (rank 0's runs) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip extra.pipeline / extra.configs / the stream-copy calibration")
@@ -441,6 +468,10 @@ def main():
                     "a fixed total sharded r mod N over the ranks, one gather of the result rows")
     ap.add_argument("--iter", type=int, default=64, help="--config5: seeds per sweep point (script default 5 -> 300 runs; 64 -> 3840 runs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.min_seconds > 0:              # repeated regions train on for a time-dependent number of steps
+        ap.error("--dump-outputs needs a fixed number of timed steps: leave --min-seconds at 0")
 
     from vae_equalizer_amd import sweep
     from vae_equalizer_amd.engine import DPEngine
@@ -541,6 +572,7 @@ def main():
     kern_ms = float(np.median(launch_ms))                     # the MEDIAN launch of the timed regions prices the roofline, like `value` takes the median
     kern_ms_mean = float(np.mean(launch_ms))                  # region (one cold launch no longer puts kernel_ms above ms_per_step); the mean -- the statistic
                                                               # rocprofv3's kernel stats report -- is given next to it
+    dumped = dump_outputs(out, eng, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         sym_per_launch = R * CFG["N_frame_max"]
@@ -597,6 +629,8 @@ def main():
                          "algorithmic_flops_per_dp_symbol": ALGO_FLOPS_PER_DP_SYMBOL,
                          "binds": "fp32 VALU issue + LDS (45 flop/B is above the 20 flop/B ridge); the HBM fraction is reported because north_star declares it"},
         }
+        if dumped:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if not args.no_cpu_baseline and world == 1 and not args.config5:      # reported baseline: rank 0 at N = 1 only
             # The CPU leg (~12 s of OpenMP work) runs in a thread WHILE the GPU keeps executing the headline launch back to back (untimed for `value`,
             # reported as extra.sustained): the GPU is busy for the whole invocation and the line also says what ten seconds of sustained load reach.

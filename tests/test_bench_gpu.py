@@ -100,3 +100,25 @@ def test_bench_config5_two_ranks_rehearsal():
     assert d["config"]["runs_total"] == 180 and d["config"]["runs_per_gpu"] == 90 and "config 5" in d["config"]["workload"]
     assert abs(d["value"] - 180 * 10000 * 2 / (d["region_ms"]["median"] * 1e-3)) < 1e-6 * d["value"]
     assert d["roofline"]["traffic"] is None and "extra" not in d and "cpu_baseline" not in d
+
+
+def test_bench_steps_and_dump_outputs(tmp_path):
+    """--steps K times exactly K steps in one region by default, and --dump-outputs writes the last timed step's outputs (float32 .npy, <= 64 MB):
+    the inputs are seeded, so two invocations with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--runs", "256", "--steps", "3", "--warmup", "1", "--no-extras",
+                            "--no-cpu-baseline", "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _last_json(r.stdout)
+        assert d["steps"] == 3 and d["timed_regions"] == 1 and d["roofline"]["launches_timed"] == 3 and d["parity"]["ok"]
+        assert abs(d["ms_per_step"] * 3 - d["region_ms"]["median"]) < 1e-6 * d["region_ms"]["median"] + 1e-9
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == ["W.npy", "h.npy", "loss.npy", "q.npy", "var_est.npy", "y.npy"] and d["dumped_outputs"]["dir"] == str(tmp_path / tag)
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in files) <= 64 << 20
+        dumps.append({f[:-4]: np.load(tmp_path / tag / f) for f in files})
+    a, b = dumps
+    assert a["loss"].shape == (256, 1, 100) and a["W"].shape == (256, 2, 4, 25) and a["q"].shape[1:] == (1, 2, 16, 10000)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k

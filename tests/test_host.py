@@ -245,3 +245,30 @@ def test_padded_rows_prefer_the_librarys_own_fft_lengths():
     assert [ch.padded_row_len(n) for n in (1, 2098, 4096, 4097, 6098, 10098, 12098, 16385, 20098, 20480)] == [4096, 4096, 4096, 5120, 8192, 10240, 16384, 20480, 20480, 20480]
     assert ch.padded_row_len(20481) == ch.fast_fft_len(20481) == 24576 and ch.padded_row_len(40098) == 40960
     assert ch.STREAM_BLOCK == 8192 and "chunk" not in ch.generate_batch_hip.__code__.co_varnames[:ch.generate_batch_hip.__code__.co_argcount]
+
+
+def test_bench_dump_outputs_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs on host tensors shaped like a DP step's outputs: float32 .npy files, at most 64 MB in all, every run of the
+    per-run arrays, a seeded sample of runs for q / y that is the same on every call and holds those runs' rows unchanged."""
+    import types
+    import bench
+    R, n, N, M = 40, 8, 10000, 25
+    g = torch.Generator().manual_seed(0)
+    r = lambda *s: torch.randn(*s, generator=g)
+    eng = types.SimpleNamespace(R=R, W=r(R, 2, 4, M), h=r(R, 2, 2, 2, M))
+    out = {"loss": r(R, 1, 100), "var_est": r(R, 1, 2, 100), "q": r(R, 1, 2, 2 * n, N), "y": r(R, 1, 2, 2, N)}
+    shapes = bench.dump_outputs(out, eng, str(tmp_path / "a"))
+    bench.dump_outputs(out, eng, str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["W.npy", "h.npy", "loss.npy", "q.npy", "var_est.npy", "y.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for k, v in a.items():
+        assert v.dtype == np.float32 and list(v.shape) == shapes[k] and np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy")))
+    for k in ("loss", "var_est"):
+        assert np.array_equal(a[k], out[k].numpy())
+    assert np.array_equal(a["W"], eng.W.numpy()) and np.array_equal(a["h"], eng.h.numpy())
+    k = a["q"].shape[0]
+    assert 1 <= k < R and a["y"].shape[0] == k
+    rows = [i for i in range(R) if (out["y"][i].numpy() == a["y"]).all(axis=tuple(range(1, 5))).any()]
+    assert len(rows) == k and np.array_equal(a["q"], out["q"][rows].numpy())
