@@ -364,6 +364,23 @@ int vaeq_cma(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t mode, int32_t
              float *h, const float *lr, float *out, float *e, void *stream);
 int vaeq_cpe(int32_t R, int64_t N, int32_t M_ma, const float *y, float *y_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * The constant-modulus baseline of the AWGN scripts (AWGN_channel/func_CMA_MQAM_shaping.py, Eval_run_shaping_cma.py): ONE complex FIR,
+ * no input power scaling, a CPE without unwrapping, its own shift search -- not vaeq_cma / vaeq_cpe with one polarisation removed.
+ * vaeq_awgn_cma: CMA(Rx, R, h, lr, sps, eval) (:142-168) on one frame per run: rx[R][2][N] (re, im), taps h[R][2][M] (re, im; updated in place
+ * when update != 0, untouched otherwise = eval False), lr[R] -> loss[R] = mean |e|, out[R][2][N/sps] and e[R][N/sps] (both nullable) at the
+ * reference's wrapped indices.  M odd <= 63, 1 <= sps <= 8, N a multiple of sps, N / sps >= M.
+ * vaeq_awgn_cma_validate: one evaluated epoch (:225-232) -- CMA(..., False) with the taps h, CPE (:170-198), find_shift_symb(., ., n_shift)
+ * (:127-140) and SER_CMA (:63-94) -- in one launch: data_f16[R][2][N/sps] (TX, fp16), amp[n_lev] -> ser[R], shift[R] (nullable),
+ * cpe_out[R][2][N/sps] (nullable: the CPE output).  n_lev in {2, 4, 8}, n_shift odd <= 23, N / sps >= 1000 + n_shift (the shift search
+ * reads the first 1000 symbols).  ws: vaeq_awgn_cma_validate_ws_bytes(R, N, sps) bytes of device workspace -- 0 (ws may be NULL) while a
+ * run's equalised track fits in LDS (N / sps <= 17408), R * 2 * (N / sps) * 8 otherwise. */
+int vaeq_awgn_cma(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t update, const float *rx, float R_mod, float *h, const float *lr,
+                  float *loss, float *out, float *e, void *stream);
+int vaeq_awgn_cma_validate(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t n_shift, const float *rx, const float *h,
+                           const float *amp, const void *data_f16, float *ws, float *ser, int32_t *shift, float *cpe_out, void *stream);
+int64_t vaeq_awgn_cma_validate_ws_bytes(int32_t R, int64_t N, int32_t sps);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

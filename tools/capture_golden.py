@@ -18,7 +18,7 @@ The reference seeds nothing; determinism comes from patching
 Fixture families: G0 init tables, G1-G3 DP step / free runs (VAE-LE, VAEflex), G4 AWGN VAE-LE, G5 DP epilogue, G6 generator,
 G7 processing()-level runs (configs 1-3), G8 AWGN VAE-NN (Net), G9 converging VAEflex run (config 4), G10 converging PCS VAE-LE
 run (config 5 shape), G11 VAE-NN with BatchNorm (Net_BN), G12 CMA / CPE, G1b heavy-shaping DP steps, G13 config-5 on-grid runs,
-G14 the CMA modules' epilogue at 16- / 64-QAM.
+G14 the CMA modules' epilogue at 16- / 64-QAM, G15 the AWGN constant-modulus baseline (AWGN_channel/func_CMA_MQAM_shaping.py).
 
 Usage:  python tools/capture_golden.py [--only G1,G2] [--full-run]
 """
@@ -782,6 +782,66 @@ def capture_G14(sfun, awgn):
     save("G14_cma_epilogue_64qam_pcs", **_g14_case(sfun, "64-QAM", 25, NU_572, 1e-3, seed=143, num_frames=12))
 
 
+# --------------------------------------------------------------------------
+# G15: the AWGN constant-modulus baseline (AWGN_channel/func_CMA_MQAM_shaping.py): one training frame (CMA eval=True), an evaluated epoch
+#      with every intermediate (CMA eval=False -> CPE -> find_shift_symb -> SER_CMA), a CPE input whose drift crosses the pi/4 boundaries
+#      (no unwrapping in this CPE), and processing() trajectories at a reduced shape
+# --------------------------------------------------------------------------
+def _g15_case(ref, mod, SNR, lr, seed, n_pre=3, N_train=1500, N_valid=4000, M_est=25):
+    sps = 2
+    amps, P, _, _, h_channel, M = _awgn_tables(mod, 0.0, SNR)            # M = 5 taps of h1 (func_CMA_MQAM_shaping.py:212)
+    amp_levels = torch.tensor(amps, dtype=torch.float32)
+    num_lev = len(amps)
+    h = torch.zeros(2, M_est)
+    h[0, M_est // 2] = 1
+    with SeededRng(seed), torch.no_grad():
+        for _ in range(n_pre):                                            # a few frames first: the captured taps equalise already
+            rx, _ = ref.generate_data(N_train, M, amps, SNR, h_channel, sps, "cpu", P)
+            _, h, _ = ref.CMA(rx, 1, h, lr, sps, True)
+        h0 = h.clone()
+        rx, data = ref.generate_data(N_train, M, amps, SNR, h_channel, sps, "cpu", P)
+        out, h, e = ref.CMA(rx, 1, h, lr, sps, True)
+        rxv, datav = ref.generate_data(N_valid, M, amps, SNR, h_channel, sps, "cpu", P)
+        hv = h.clone()
+        outv, _, ev = ref.CMA(rxv, 1, h, lr, sps, False)
+        cpe = ref.CPE(outv)
+        shift = ref.find_shift_symb(cpe, datav, 21)
+        cpe_in = cpe.clone()
+        ser = ref.SER_CMA(cpe[:, 11 + shift:-11], datav[:, 11:-11 - shift], sps, amp_levels, num_lev, "cpu")
+    return dict(rx=t2n(rx), h0=t2n(h0), lr=np.float64(lr), out=t2n(out), h=t2n(h), e=t2n(e), rx_valid=t2n(rxv), data_valid=t2n(datav),
+                h_valid=t2n(hv), out_valid=t2n(outv), e_valid=t2n(ev), cpe=t2n(cpe_in), shift=np.int64(shift), SER=np.float64(ser),
+                amp_levels=t2n(amp_levels), seed=np.int64(seed), SNR=np.float64(SNR), mod=np.array(mod), sps=np.int64(sps), M_est=np.int64(M_est))
+
+
+def capture_G15(sfun, awgn):
+    import contextlib
+    import io
+    sys.path.insert(0, os.path.join(REF, "AWGN_channel"))
+    import func_CMA_MQAM_shaping as ref                                   # reference module
+
+    save("G15_awgn_cma_16qam", **_g15_case(ref, "16-QAM", 22, 3e-4, seed=151))
+    save("G15_awgn_cma_64qam", **_g15_case(ref, "64-QAM", 27, 1e-4, seed=152, n_pre=6))
+    g = torch.Generator().manual_seed(153)                                # CPE on a drifting 16-QAM constellation: the phase crosses +-pi/4
+    n = 3000
+    lev = torch.tensor([-3.0, -1.0, 1.0, 3.0]) / np.sqrt(10.0)
+    x = lev[torch.randint(0, 4, (2, n), generator=g)]
+    phi = 0.9 + 2.2 * torch.arange(n) / n
+    y = torch.stack([x[0] * torch.cos(phi) - x[1] * torch.sin(phi), x[1] * torch.cos(phi) + x[0] * torch.sin(phi)]) + 0.02 * torch.randn(2, n, generator=g)
+    with torch.no_grad():
+        save("G15_awgn_cma_cpe", cpe_in=t2n(y), cpe_out=t2n(ref.CPE(y.clone())))
+    runs = {}
+    for tag, mod, SNR, lr, seed in (("4qam", "4-QAM", 16, 3e-5, 154), ("16qam", "16-QAM", 22, 1e-4, 155)):
+        t0 = time.time()
+        with SeededRng(seed), contextlib.redirect_stdout(io.StringIO()):
+            SER = ref.processing(mod, 2, SNR, 0.0, 25, lr, 3000, 2000, 40, 2, "h1")
+        secs = time.time() - t0
+        print(f"   G15 {tag}: {secs:.0f}s  SER {np.round(t2n(SER), 3).tolist()}", flush=True)
+        runs.update({f"{tag}_SER": t2n(SER), f"{tag}_seed": np.int64(seed), f"{tag}_lr": np.float64(lr), f"{tag}_SNR": np.float64(SNR),
+                     f"{tag}_mod": np.array(mod), f"{tag}_seconds": np.float64(secs)})
+    runs.update(N_valid=np.int64(3000), N_train=np.int64(2000), num_epochs=np.int64(40), epe=np.int64(2), M_est=np.int64(25))
+    save("G15_awgn_cma_runs", **runs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
@@ -790,7 +850,7 @@ def main():
     torch.set_num_threads(1)
     os.makedirs(OUT, exist_ok=True)
     sfun, awgn = _import_reference()
-    todo = [s for s in args.only.split(",") if s] or ["G0", "G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G1b", "G13a", "G13b", "G13c", "G13d", "G13e", "G13f", "G14"]
+    todo = [s for s in args.only.split(",") if s] or ["G0", "G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G1b", "G13a", "G13b", "G13c", "G13d", "G13e", "G13f", "G14", "G15"]
     for g in todo:
         print(f"[{g}]")
         if g == "G7":

@@ -489,3 +489,47 @@ def cpe(y, M_ma=501):
     with torch.cuda.device(y.device):
         nat.check(nat.lib().vaeq_cpe(y.shape[0], y.shape[-1], int(M_ma), nat.ptr(y), nat.ptr(out), nat.current_stream(y.device)), "vaeq_cpe")
     return out[0] if squeeze else out
+
+
+def awgn_cma(rx, h, lr, sps=2, update=True, R_mod=1.0, want_out=False, want_e=False):
+    """The AWGN scripts' constant-modulus training pass (AWGN_channel/func_CMA_MQAM_shaping.py:142-168, vaeq_awgn_cma) for R runs:
+    rx[R,2,N], h[R,2,M] (updated IN PLACE when ``update``; untouched otherwise = CMA(..., eval=False)), lr scalar or [R]
+    -> (loss[R] = mean|e|, out[R,2,N//sps] or None, e[R,N//sps] or None)."""
+    dev, R, N = rx.device, rx.shape[0], rx.shape[-1]
+    if rx.dim() != 3 or rx.shape[1] != 2 or h.dim() != 3 or tuple(h.shape[:2]) != (R, 2) or not h.is_contiguous():
+        raise ValueError(f"rx must be [R,2,N] and h a contiguous [R,2,M], got {tuple(rx.shape)}, {tuple(h.shape)}")
+    rx = rx.contiguous()
+    lr_t = _f32(lr, dev).expand(R).contiguous()
+    K = N // sps
+    loss = torch.empty(R, dtype=torch.float32, device=dev)
+    out = torch.empty(R, 2, K, dtype=torch.float32, device=dev) if want_out else None
+    e = torch.empty(R, K, dtype=torch.float32, device=dev) if want_e else None
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_awgn_cma(R, N, int(sps), h.shape[-1], int(bool(update)), nat.ptr(rx), float(R_mod), nat.ptr(h), nat.ptr(lr_t),
+                                          nat.ptr(loss), nat.ptr(out), nat.ptr(e), nat.current_stream(dev)), "vaeq_awgn_cma")
+    return loss, out, e
+
+
+def awgn_cma_validate(rx, h, data, amp_levels, sps=2, n_shift=21, want_cpe=False):
+    """One evaluated epoch of the AWGN constant-modulus script in one launch (func_CMA_MQAM_shaping.py:225-232, vaeq_awgn_cma_validate):
+    CMA(..., eval=False) with the taps h[R,2,M], CPE, find_shift_symb and SER_CMA on rx[R,2,N] against data[R,2,N//sps] (fp16)
+    -> (SER[R] f32, shift[R] i32, CPE output [R,2,N//sps] or None)."""
+    dev, R, N = rx.device, rx.shape[0], rx.shape[-1]
+    K = N // sps
+    if tuple(data.shape) != (R, 2, K) or tuple(h.shape[:2]) != (R, 2):
+        raise ValueError(f"data must be [R={R}, 2, {K}] and h [R, 2, M], got {tuple(data.shape)}, {tuple(h.shape)}")
+    rx, h = rx.contiguous(), h.contiguous()
+    data = data.to(torch.float16).contiguous()
+    amp = _f32(amp_levels, dev).reshape(-1)
+    L = nat.lib()
+    wsb = int(L.vaeq_awgn_cma_validate_ws_bytes(R, N, int(sps)))
+    nat.check(min(wsb, 0), "vaeq_awgn_cma_validate_ws_bytes")
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev) if wsb > 0 else None
+    ser = torch.empty(R, dtype=torch.float32, device=dev)
+    shift = torch.empty(R, dtype=torch.int32, device=dev)
+    cpe_out = torch.empty(R, 2, K, dtype=torch.float32, device=dev) if want_cpe else None
+    with torch.cuda.device(dev):
+        nat.check(L.vaeq_awgn_cma_validate(R, N, int(sps), h.shape[-1], amp.numel(), int(n_shift), nat.ptr(rx), nat.ptr(h), nat.ptr(amp),
+                                           nat.ptr(data, torch.float16), nat.ptr(ws), nat.ptr(ser), nat.ptr(shift, torch.int32), nat.ptr(cpe_out),
+                                           nat.current_stream(dev)), "vaeq_awgn_cma_validate")
+    return ser, shift, cpe_out
