@@ -381,6 +381,29 @@ int vaeq_awgn_cma_validate(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t
                            const float *amp, const void *data_f16, float *ws, float *ser, int32_t *shift, float *cpe_out, void *stream);
 int64_t vaeq_awgn_cma_validate_ws_bytes(int32_t R, int64_t N, int32_t sps);
 
+/* ------------------------------------------------------------------------
+ * The known-channel ("genie") baselines of AWGN_channel/DFE_MQAM_shaping.py at sps = 1 (the only setting of the script; VAEQ_ERR_SHAPE
+ * otherwise).  rx[R][2][N] (re, im), data_f16[R][2][N] (TX, fp16), amp[n_lev] (n_lev in {2, 4, 8}), complex taps [R][2][K] (re, im), one
+ * set per frame.  N >= 1000 + n_shift + 2 n_cut + 22 (the shift search reads the first 1000 symbols; n_shift / 2 <= n_cut + 11).
+ * vaeq_awgn_lmmse_eval: compl_conv(rx, lmmse_taps) (:236-241, K even <= 64 -> N + 1 outputs), nearest_neighbor(out[1::1]) (:275),
+ * find_shift_symb(out, data, n_shift) (:280) and SER_func(out[:, n_cut+11+shift : -11-n_cut], data[:, n_cut+11 : -11-shift-n_cut]) (:281,
+ * the rescale over the one-sample-longer output slice) -> ser[R], shift[R] (nullable), dec[R][N] int8 (nullable: the per-symbol decisions
+ * iI * n_lev + iQ), out[R][N+1] complex64 (nullable; the track lives in ws, vaeq_awgn_lmmse_eval_ws_bytes(R, N, K) bytes, when NULL).
+ * vaeq_awgn_dfe: compl_conv(rx, ff_taps) (K1 <= 64 taps, :285), dfe(ff, ff_taps, fb_taps, init_dec) (:200-222, K2 = len(fb) in 1..10,
+ * init_dec[R][N] = the LMMSE decisions) -> dec[R][N] int8, then find_shift_symb(., ., n_shift) and SER_func on the hard decisions (:290-293)
+ * -> ser[R] (nullable: no evaluation, and no rule on N, n_shift, n_cut), shift[R] (nullable).  The recursion runs as speculate-and-repair over C chunks of ceil((N - K2) / C)
+ * symbols (1 <= C <= 8192, each chunk at least K2 long) with W symbols of warm-up; the decisions are bit-identical for every C and W (C = 1
+ * is the plain serial recursion).  repairs[R] (nullable): symbols the repair pass re-ran; ff_out[R][N] complex64 (nullable): the
+ * feed-forward output.  ws: vaeq_awgn_dfe_ws_bytes(R, N, C) bytes. */
+int vaeq_awgn_lmmse_eval(int32_t R, int64_t N, int32_t sps, int32_t n_lev, int32_t K, int32_t n_shift, int32_t n_cut, const float *rx,
+                         const float *taps, const float *amp, const void *data_f16, float *ws, float *ser, int32_t *shift, int8_t *dec,
+                         float *out, void *stream);
+int64_t vaeq_awgn_lmmse_eval_ws_bytes(int32_t R, int64_t N, int32_t K);
+int vaeq_awgn_dfe(int32_t R, int64_t N, int32_t sps, int32_t n_lev, int32_t K1, int32_t K2, int32_t C, int32_t W, int32_t n_shift,
+                  int32_t n_cut, const float *rx, const float *ff_taps, const float *fb_taps, const float *amp, const int8_t *init_dec,
+                  const void *data_f16, void *ws, int8_t *dec, float *ser, int32_t *shift, int32_t *repairs, float *ff_out, void *stream);
+int64_t vaeq_awgn_dfe_ws_bytes(int32_t R, int64_t N, int32_t C);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

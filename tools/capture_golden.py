@@ -18,7 +18,8 @@ The reference seeds nothing; determinism comes from patching
 Fixture families: G0 init tables, G1-G3 DP step / free runs (VAE-LE, VAEflex), G4 AWGN VAE-LE, G5 DP epilogue, G6 generator,
 G7 processing()-level runs (configs 1-3), G8 AWGN VAE-NN (Net), G9 converging VAEflex run (config 4), G10 converging PCS VAE-LE
 run (config 5 shape), G11 VAE-NN with BatchNorm (Net_BN), G12 CMA / CPE, G1b heavy-shaping DP steps, G13 config-5 on-grid runs,
-G14 the CMA modules' epilogue at 16- / 64-QAM, G15 the AWGN constant-modulus baseline (AWGN_channel/func_CMA_MQAM_shaping.py).
+G14 the CMA modules' epilogue at 16- / 64-QAM, G15 the AWGN constant-modulus baseline (AWGN_channel/func_CMA_MQAM_shaping.py),
+G16 the known-channel LMMSE and DFE baselines (AWGN_channel/DFE_MQAM_shaping.py).
 
 Usage:  python tools/capture_golden.py [--only G1,G2] [--full-run]
 """
@@ -842,6 +843,80 @@ def capture_G15(sfun, awgn):
     save("G15_awgn_cma_runs", **runs)
 
 
+# --------------------------------------------------------------------------
+# G16: the known-channel LMMSE / DFE baselines (AWGN_channel/DFE_MQAM_shaping.py).  The script runs its sweep at import, so it is parsed
+#      with ast and only its top-level statements before the first top-level ``for`` are executed (definitions and constants, device cpu);
+#      other channels / modulations rebind the globals its functions read.
+# --------------------------------------------------------------------------
+def _load_dfe_reference():
+    import ast
+    path = os.path.join(REF, "AWGN_channel", "DFE_MQAM_shaping.py")
+    tree = ast.parse(open(path).read(), path)
+    body = []
+    for node in tree.body:
+        if isinstance(node, ast.For):
+            break
+        body.append(node)
+    ns = {"__name__": "dfe_reference"}
+    for node in body:
+        exec(compile(ast.Module(body=[node], type_ignores=[]), path, "exec"), ns)
+        if isinstance(node, ast.Assign) and any(getattr(t, "id", None) == "device" for t in node.targets):
+            ns["device"] = "cpu"
+    return ns
+
+
+_G16_CHANNELS = {
+    "h1": np.array([0.0545 + 1j * 0.05, 0.2823 - 1j * 0.11971, -0.7676 + 1j * 0.2788, -0.0641 - 1j * 0.0576, 0.0466 - 1j * 0.02275]),
+    "h2": np.array([0.0545 + 1j * 0.0165, -1.3449 - 1j * 0.4523, 1.0067 + 1j * 1.1524, 0.3476 + 1j * 0.3153]),
+    "proakis_a": np.array([0.04, -0.05, 0.07, -0.21, -0.5, 0.72, 0.36, 0, 0.21, 0.03, 0.07]),
+}
+
+
+def _g16_case(ns, mod, channel, SNR, seed, N=4000):
+    h_orig = _G16_CHANNELS[channel].astype(np.complex64)
+    h = h_orig / np.linalg.norm(h_orig)
+    const = ns["constellations"][mod] / np.sqrt(np.mean(np.abs(ns["constellations"][mod]) ** 2))
+    n = int(np.sqrt(len(const)))
+    ns.update(const_torch=torch.tensor(const, dtype=torch.cfloat), num_lev=n, M=len(h_orig), h_channel=h,
+              amp_levels=torch.tensor(const.real[::n], dtype=torch.float32))
+    h_t = torch.tensor(h, dtype=torch.cfloat)
+    SNR = np.int64(SNR)
+    nc = ns["N_cut"]
+    with SeededRng(seed), torch.no_grad():
+        rx, data, P = ns["generate_data_shaping"](N, ns["amp_levels"], SNR, h, ns["nu"])
+    lm = ns["compute_lmmse"](h_t, SNR, ns["lmmse_filter_order"], ns["lmmse_filter_order"] // 2 + 1)
+    ff = ns["compute_feedforward"](h_t, SNR, ns["M_dfe"])
+    fb = ns["compute_feedback_filter"](h_t, ff)
+    rxc = torch.complex(rx[0, :], rx[1, :])
+    mm = ns["compl_conv"](rxc, lm)
+    mm_out = mm.clone()
+    idx = ns["nearest_neighbor"](mm[1::1])
+    sh_m = ns["find_shift_symb"](torch.view_as_real(mm).T, data, 21)
+    ser_m = ns["SER_func"](torch.view_as_real(mm).T[:, nc + 11 + sh_m:-11 - nc], data[:, nc + 11:-11 - sh_m - nc])
+    ffo = ns["compl_conv"](rxc, ff)
+    t0 = time.time()
+    didx = ns["dfe"](ffo, ff, fb, idx)
+    secs = time.time() - t0
+    hard = torch.view_as_real(ns["const_torch"][didx.long()]).T
+    sh_d = ns["find_shift_symb"](hard, data, 24)
+    ser_d = ns["SER_func"](hard[:, nc + 11 + sh_d:-11 - nc], data[:, nc + 11:-11 - sh_d - nc])
+    print(f"   G16 {mod} {channel} {int(SNR)} dB: SER_mmse {float(ser_m):.4f}  SER_dfe {float(ser_d):.4f}  dfe {secs / N * 1e6:.0f} us/symbol")
+    c = lambda t: t2n(t).astype(np.complex64)  # noqa: E731
+    return dict(rx=t2n(rx), data=t2n(data), P=t2n(P), lmmse=c(lm), ff=c(ff), fb=c(fb), lmmse_out=c(mm_out), lmmse_dec=t2n(idx).astype(np.int8),
+                lmmse_shift=np.int64(sh_m), lmmse_SER=np.float64(ser_m), ff_out=c(ffo), dfe_dec=t2n(didx).astype(np.int8),
+                dfe_shift=np.int64(sh_d), dfe_SER=np.float64(ser_d), h_channel=h.astype(np.complex64), h_orig=h_orig,
+                amp_levels=t2n(ns["amp_levels"]), nu=np.float64(ns["nu"]), mod=np.array(mod), channel=np.array(channel),
+                SNR=np.float64(SNR), seed=np.int64(seed), N=np.int64(N), N_cut=np.int64(nc))
+
+
+def capture_G16(sfun, awgn):
+    ns = _load_dfe_reference()
+    for name, mod, channel, SNR, seed in (("G16_dfe_64qam_h1_15dB", "64-QAM", "h1", 15, 161), ("G16_dfe_64qam_h1_22dB", "64-QAM", "h1", 22, 162),
+                                          ("G16_dfe_16qam_h2_18dB", "16-QAM", "h2", 18, 163),
+                                          ("G16_dfe_4qam_proakis_a_8dB", "4-QAM", "proakis_a", 8, 164)):
+        save(name, **_g16_case(ns, mod, channel, SNR, seed))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
@@ -850,7 +925,7 @@ def main():
     torch.set_num_threads(1)
     os.makedirs(OUT, exist_ok=True)
     sfun, awgn = _import_reference()
-    todo = [s for s in args.only.split(",") if s] or ["G0", "G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G1b", "G13a", "G13b", "G13c", "G13d", "G13e", "G13f", "G14", "G15"]
+    todo = [s for s in args.only.split(",") if s] or ["G0", "G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G1b", "G13a", "G13b", "G13c", "G13d", "G13e", "G13f", "G14", "G15", "G16"]
     for g in todo:
         print(f"[{g}]")
         if g == "G7":

@@ -439,3 +439,78 @@ def generate_awgn_clean_batch_hip(R, N, amps, P, SNR, h_channel, sps, device, se
 def _mix_seed(seed, r0):
     """Key of the Philox streams of the chunk that starts at run r0 (runs inside a chunk are told apart by the run counter word)."""
     return (int(seed) * 0x9E3779B97F4A7C15 + int(r0) * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+
+
+def dfe_frame_geometry(N, h_channel, sps=1):
+    """Lengths of DFE_MQAM_shaping.py's generate_data_shaping (:77-105): the combined pulse g = rcfir(8, sps, 0.1) * h_channel (at 1 sps the
+    raised cosine is a Dirac up to float32 rounding), its 'valid' output length Ls and the offset T + M - 1 of the TX reference (M = the
+    number of symbol-spaced channel taps)."""
+    return _geo_cached("dfe", _dfe_frame_geometry, N, h_channel, sps)
+
+
+def _dfe_frame_geometry(N, h_channel, sps):
+    T = PULSE_SPAN
+    h = np.asarray(h_channel, dtype=np.complex64)
+    M_channel = (len(h) - 1) // sps + 1
+    N_conv = N + len(h) + 4 * T
+    g = np.convolve(rcfir(T, sps, ROLL_OFF).astype(np.complex64), h).astype(np.complex64)
+    Ls = sps * (N_conv - 1) + 1 - len(g) + 1
+    return dict(N_conv=N_conv, g=g, Lg=len(g), Ls=Ls, ref_offset=T + M_channel - 1)
+
+
+def pcs_probabilities(amps, nu):
+    """P over the per-axis levels as DFE_MQAM_shaping.py:82-86 computes it (float32 levels scaled by their smallest magnitude)."""
+    a = np.asarray(amps, dtype=np.float32)
+    s = a / np.min(np.abs(a))
+    P = np.exp(-nu * np.abs(s) ** 2)
+    return P / np.sum(P)
+
+
+def generate_data_rc(N, amps, SNR, h_channel, nu, sps=1, rng=None, noise=None):
+    """DFE_MQAM_shaping.py's generate_data_shaping (:77-105) in numpy with the reference's random-number consumption: raised-cosine pulse,
+    then the channel, both 'valid'; TX reference from T + M - 1.  -> (rx[2, sps N] f32, data[2, N] f16, P) as numpy arrays."""
+    rng = np.random.default_rng() if rng is None else rng
+    noise = np.random if noise is None else noise
+    T = PULSE_SPAN
+    a = np.asarray(amps, dtype=np.float32)
+    P = pcs_probabilities(a, nu)
+    M_channel = (len(h_channel) - 1) // sps + 1
+    N_conv = N + len(h_channel) + 4 * T
+    tx_up = np.zeros(sps * (N_conv - 1) + 1, dtype=np.complex64)
+    data = rng.choice(a, (2, N_conv), p=P)
+    tx_up[::sps] = data[0] + 1j * data[1]
+    sig = np.convolve(np.convolve(tx_up, rcfir(T, sps, ROLL_OFF), mode="valid"), h_channel, mode="valid")
+    sigma_n = np.sqrt(sps * np.mean(np.abs(sig) ** 2) / 2 / 10 ** (SNR / 10))
+    sig += sigma_n * (noise.randn(*sig.shape) + 1j * noise.randn(*sig.shape))
+    lo = T + M_channel - 1
+    rx = np.asarray([np.real(sig[:sps * N]), np.imag(sig[:sps * N])], dtype=np.float32)
+    ref = np.asarray([data[0, lo:lo + N], data[1, lo:lo + N]], dtype=np.float16)
+    return rx, ref, P.astype(np.float32)
+
+
+def generate_dfe_batch_hip(R, N, amps, P, SNR, h_channel, device, seed, frame, sigma_fixed=None):
+    """generate_data_rc for R frames on the device (vaeq_gen_awgn at sps = 1 with the raised-cosine geometry): deterministic in
+    (seed, frame, run).  SNR scalar or [R].  Returns (rx[R,2,N] f32, data[R,2,N] f16)."""
+    import ctypes as C
+
+    from . import _native as nat
+    dev = torch.device(device)
+    geo = dfe_frame_geometry(N, h_channel, 1)
+    n = len(amps)
+    amp_t = _dev_const(amps, torch.float32, dev)
+    cdf = _cdf_dev(P, R, n, dev)
+    g_t = _dev_const(np.stack([geo["g"].real, geo["g"].imag], -1), torch.float32, dev)
+    snr = _dev_const(np.broadcast_to(np.asarray(SNR, np.float32), (R,)), torch.float32, dev)
+    rx = torch.empty(R, 2, N, dtype=torch.float32, device=dev)
+    data = torch.empty(R, 2, N, dtype=torch.float16, device=dev)
+    sigma = torch.empty(R, dtype=torch.float32, device=dev)
+    sig = torch.empty(R, geo["Ls"], 2, dtype=torch.float32, device=dev)
+    pw = torch.empty(R, (geo["Ls"] + 2047) // 2048, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_gen_awgn(R, N, geo["N_conv"], 1, n, geo["Lg"], geo["Ls"], geo["ref_offset"], nat.ptr(amp_t), nat.ptr(cdf),
+                                          nat.ptr(g_t), nat.ptr(snr), C.c_uint64(_mix_seed(seed, 0)), C.c_uint32(frame), nat.ptr(sig),
+                                          nat.ptr(pw), nat.ptr(rx), nat.ptr(data, torch.float16), nat.ptr(sigma),
+                                          None if sigma_fixed is None else
+                                          nat.ptr(_dev_const(np.broadcast_to(np.asarray(sigma_fixed, np.float32), (R,)), torch.float32, dev)),
+                                          nat.current_stream(dev)), "vaeq_gen_awgn")
+    return rx, data

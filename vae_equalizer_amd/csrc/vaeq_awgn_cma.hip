@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "vaeq.h"
+#include "vaeq_awgn_eval.h"
 #include "vaeq_common.h"
 #include "vaeq_wave.h"
 
@@ -125,20 +126,6 @@ __device__ __forceinline__ void pow4(float2 v, float &r, float &i)   // (a + jb)
     i = 4.0f * (a2 * v.x * v.y - v.x * b2 * v.y);
 }
 
-// Block sum of one float per thread in a fixed order (DPP wave sums, then the 16 wave sums in wave order): deterministic and the same for
-// every run of a batch.
-__device__ __forceinline__ float block_sum(float v, float *red, int tid)
-{
-    v = wave_sum_dpp(v);
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < AV_NT / 64; w++) s += red[w];
-    __syncthreads();
-    return s;
-}
-
 // LDS: the equalised track [K] float2 lives in LDS and is phase-corrected in place (K <= AV_LDS_K).  !LDS: raw and corrected tracks in the
 // global workspace ws[R][2][K] float2 (any K; N_valid = 50 000 in the script's alternative setting).
 template <bool LDS>
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(AV_NT) void awgn_cma_validate_kernel(int N, int sps
     __shared__ float hs[2][64];
     __shared__ float lev[8];
     __shared__ int sh_shift;
-    const int run = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int run = blockIdx.x, tid = threadIdx.x;
     const int K = N / sps, mh = M / 2, joff = mh - mh / sps;
     const float *x0 = rx + (size_t)run * 2 * N, *x1 = x0 + N;
     float2 *tr = LDS ? av_track : ws + (size_t)run * 2 * K;    // equalised track (k order)
@@ -245,70 +232,14 @@ __global__ __launch_bounds__(AV_NT) void awgn_cma_validate_kernel(int N, int sps
             c0[K + n] = v.y;
         }
     }
-    // 3. find_shift_symb (:127-140): corr[rail][i] = sum_m tx[rail][hs + m] * yc[i + m].x, m < 1000 - hs; one wave per dot product
-    const int hsh = n_shift / 2, nm = 1000 - hsh;
+    // 3. find_shift_symb (:127-140) and 4. SER_CMA(out_cpe[:, 11+shift:-11], data[:, 11:-11-shift]) (:63-94, :231): vaeq_awgn_eval.h
     const __half *tx0 = data + (size_t)run * 2 * K, *tx1 = tx0 + K;
-    for (int q = wv; q < 2 * n_shift; q += AV_NT / 64) {
-        const int rail = q / n_shift, i = q - rail * n_shift;
-        const __half *t = rail ? tx1 : tx0;
-        float acc = 0.f;
-        for (int m = lane; m < nm; m += 64) acc = fmaf(__half2float(t[hsh + m]), yc[i + m].x, acc);
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) corr[rail][i] = acc;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float mI = -1.f, mQ = -1.f;
-        int aI = 0, aQ = 0;
-        for (int i = 0; i < n_shift; i++) {                    // argmax: the first index on ties, as torch.argmax
-            const float vI = fabsf(corr[0][i]), vQ = fabsf(corr[1][i]);
-            if (vI > mI) { mI = vI; aI = i; }
-            if (vQ > mQ) { mQ = vQ; aQ = i; }
-        }
-        const float thr = (float)(0.02 * (double)K);           // 0.02 * rx.shape[-1] compared in float32
-        sh_shift = (mI >= thr ? aI : (mQ >= mI ? aQ : aI)) - hsh;
-    }
-    __syncthreads();
-    const int shift = sh_shift;
-    // 4. SER_CMA(out_cpe[:, 11+shift:-11], data[:, 11:-11-shift]) (:63-94, :231)
+    auto track = [&](int m) { return yc[m]; };
+    const int shift = eval_find_shift<AV_NT>(track, tx0, tx1, n_shift, K, corr, &sh_shift, tid);
     const int L = K - 22 - shift;
-    const float2 *r = yc + 11 + shift;
-    const __half *d0 = tx0 + 11, *d1 = tx1 + 11;
-    float at = 0.f, ar = 0.f;
-    for (int m = tid; m < L; m += AV_NT) {
-        const float t0 = __half2float(d0[m]), t1 = __half2float(d1[m]);
-        const float2 v = r[m];
-        at += sqrtf(t0 * t0 + t1 * t1);
-        ar += sqrtf(v.x * v.x + v.y * v.y);
-    }
-    at = block_sum(at, red, tid);
-    ar = block_sum(ar, red, tid);
-    const float scale = (at / (float)L) / (ar / (float)L);
-    const float sl = 0.5f * (float)(n_lev - 1);
-    const int top = n_lev - 1;                                 // 2 * scale: the level index mirror
-    int e0 = 0, e1 = 0, e2 = 0, e3 = 0;
-    for (int m = tid; m < L; m += AV_NT) {
-        const float2 v = r[m];
-        const float sI = v.x * scale, sQ = v.y * scale;
-        int cI = 0, cQ = 0;
-        float bI = fabsf(sI - lev[0]), bQ = fabsf(sQ - lev[0]);
-        for (int l = 1; l < n_lev; l++) {                      // argmin: the first index on ties
-            const float dI = fabsf(sI - lev[l]), dQ = fabsf(sQ - lev[l]);
-            if (dI < bI) { bI = dI; cI = l; }
-            if (dQ < bQ) { bQ = dQ; cQ = l; }
-        }
-        const int tI = (int)rintf(__fadd_rn(__fmul_rn(sl, __half2float(d0[m])), sl));
-        const int tQ = (int)rintf(__fadd_rn(__fmul_rn(sl, __half2float(d1[m])), sl));
-        e0 += (tI != cI) | (tQ != cQ);
-        e1 += (tI != top - cI) | (tQ != top - cQ);
-        e2 += (tI != top - cQ) | (tQ != cI);
-        e3 += (tI != cQ) | (tQ != top - cI);
-    }
-    const float f0 = block_sum((float)e0, red, tid), f1 = block_sum((float)e1, red, tid);   // counts < 2^24: exact in float
-    const float f2 = block_sum((float)e2, red, tid), f3 = block_sum((float)e3, red, tid);
+    const float s = eval_ser<AV_NT>(track, 11 + shift, L, tx0 + 11, tx1 + 11, L, lev, n_lev, red, tid);
     if (tid == 0) {
-        const float fL = (float)L;
-        ser[run] = fminf(fminf(f0 / fL, f1 / fL), fminf(f2 / fL, f3 / fL));
+        ser[run] = s;
         if (shift_out) shift_out[run] = shift;
     }
 }

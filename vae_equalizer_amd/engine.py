@@ -533,3 +533,87 @@ def awgn_cma_validate(rx, h, data, amp_levels, sps=2, n_shift=21, want_cpe=False
                                            nat.ptr(data, torch.float16), nat.ptr(ws), nat.ptr(ser), nat.ptr(shift, torch.int32), nat.ptr(cpe_out),
                                            nat.current_stream(dev)), "vaeq_awgn_cma_validate")
     return ser, shift, cpe_out
+
+
+def _taps2(taps, R, dev):
+    """Complex taps [K] or [R,K] (complex tensor / array) or [R,2,K] float -> contiguous float32 [R,2,K] (re, im) on ``dev``."""
+    t = torch.as_tensor(taps)
+    if t.is_complex():
+        t = t.to(dev).reshape(-1, t.shape[-1]).expand(R, -1)
+        t = torch.stack([t.real, t.imag], 1)
+    elif t.dim() == 2 and t.shape[0] == 2:
+        t = t.to(dev).unsqueeze(0).expand(R, -1, -1)
+    return t.to(dev, torch.float32).contiguous()
+
+
+def awgn_lmmse_eval(rx, taps, data, amp_levels, n_shift=21, n_cut=20, want_out=False):
+    """The LMMSE evaluation of AWGN_channel/DFE_MQAM_shaping.py (:274-281, vaeq_awgn_lmmse_eval) for R frames at sps = 1 in one launch:
+    rx[R,2,N], taps (complex [K] / [R,K], or [R,2,K] re/im; K even), data[R,2,N] (fp16) -> (SER[R] f32, shift[R] i32, decisions[R,N] int8
+    (iI * n + iQ of out[1:]), LMMSE output [R,N+1] complex64 or None)."""
+    dev, R, N = rx.device, rx.shape[0], rx.shape[-1]
+    if rx.dim() != 3 or rx.shape[1] != 2 or tuple(data.shape) != (R, 2, N):
+        raise ValueError(f"rx and data must be [R,2,N], got {tuple(rx.shape)}, {tuple(data.shape)}")
+    rx = rx.contiguous()
+    h = _taps2(taps, R, dev)
+    K = h.shape[-1]
+    data = data.to(torch.float16).contiguous()
+    amp = _f32(amp_levels, dev).reshape(-1)
+    L = nat.lib()
+    wsb = int(L.vaeq_awgn_lmmse_eval_ws_bytes(R, N, K))
+    nat.check(min(wsb, 0), "vaeq_awgn_lmmse_eval_ws_bytes")
+    No = N + 2 * (K // 2) - K + 1
+    out = torch.empty(R, No, 2, dtype=torch.float32, device=dev) if want_out else None
+    ws = None if want_out else torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=dev)
+    ser = torch.empty(R, dtype=torch.float32, device=dev)
+    shift = torch.empty(R, dtype=torch.int32, device=dev)
+    dec = torch.empty(R, N, dtype=torch.int8, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(L.vaeq_awgn_lmmse_eval(R, N, 1, amp.numel(), K, int(n_shift), int(n_cut), nat.ptr(rx), nat.ptr(h), nat.ptr(amp),
+                                         nat.ptr(data, torch.float16), nat.ptr(ws), nat.ptr(ser), nat.ptr(shift, torch.int32),
+                                         nat.ptr(dec, torch.int8), nat.ptr(out), nat.current_stream(dev)), "vaeq_awgn_lmmse_eval")
+    return ser, shift, dec, (torch.view_as_complex(out) if want_out else None)
+
+
+def dfe_chunks(R, N, K2):
+    """The speculate-and-repair split the host picks: C chunks of about 128 symbols each, at most 64 Ki lanes in all (R * C), and W = 32
+    symbols of warm-up."""
+    C = max(1, min(max(1, 65536 // max(R, 1)), (N - K2) // 128, 8192))
+    return C, 32
+
+
+def awgn_dfe(rx, ff_taps, fb_taps, init_dec, amp_levels, data=None, n_shift=24, n_cut=20, C=None, W=None, want_ff=False):
+    """The DFE of AWGN_channel/DFE_MQAM_shaping.py (:283-293, vaeq_awgn_dfe) for R frames at sps = 1: feed-forward FIR, the decision
+    recursion seeded by the LMMSE decisions init_dec[R,N] (int8), and -- when ``data`` [R,2,N] is given -- find_shift_symb and SER_func on
+    the hard decisions.  C / W: chunks and warm-up of the speculate-and-repair recursion (default: dfe_chunks; the decisions do not depend
+    on them).  -> dict(dec[R,N] int8, ser[R] / shift[R] (None without data), repairs[R] i32, ff [R,N] complex64 or None, C, W)."""
+    dev, R, N = rx.device, rx.shape[0], rx.shape[-1]
+    if rx.dim() != 3 or rx.shape[1] != 2 or tuple(init_dec.shape) != (R, N):
+        raise ValueError(f"rx must be [R,2,N] and init_dec [R,N], got {tuple(rx.shape)}, {tuple(init_dec.shape)}")
+    rx = rx.contiguous()
+    ff_t, fb_t = _taps2(ff_taps, R, dev), _taps2(fb_taps, R, dev)
+    K1, K2 = ff_t.shape[-1], fb_t.shape[-1]
+    c0, w0 = dfe_chunks(R, N, K2)
+    C = c0 if C is None else int(C)
+    W = w0 if W is None else int(W)
+    init_dec = init_dec.to(dev, torch.int8).contiguous()
+    amp = _f32(amp_levels, dev).reshape(-1)
+    L = nat.lib()
+    wsb = int(L.vaeq_awgn_dfe_ws_bytes(R, N, C))
+    nat.check(min(wsb, 0), "vaeq_awgn_dfe_ws_bytes")
+    ws = torch.empty(max(wsb, 1), dtype=torch.int8, device=dev)
+    dec = torch.empty(R, N, dtype=torch.int8, device=dev)
+    repairs = torch.empty(R, dtype=torch.int32, device=dev)
+    ff = torch.empty(R, N, 2, dtype=torch.float32, device=dev) if want_ff else None
+    ser = shift = None
+    if data is not None:
+        if tuple(data.shape) != (R, 2, N):
+            raise ValueError(f"data must be [R={R}, 2, {N}], got {tuple(data.shape)}")
+        data = data.to(torch.float16).contiguous()
+        ser = torch.empty(R, dtype=torch.float32, device=dev)
+        shift = torch.empty(R, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(L.vaeq_awgn_dfe(R, N, 1, amp.numel(), K1, K2, C, W, int(n_shift), int(n_cut), nat.ptr(rx), nat.ptr(ff_t), nat.ptr(fb_t),
+                                  nat.ptr(amp), nat.ptr(init_dec, torch.int8), nat.ptr(data, torch.float16), nat.ptr(ws, torch.int8),
+                                  nat.ptr(dec, torch.int8), nat.ptr(ser), nat.ptr(shift, torch.int32), nat.ptr(repairs, torch.int32),
+                                  nat.ptr(ff), nat.current_stream(dev)), "vaeq_awgn_dfe")
+    return dict(dec=dec, ser=ser, shift=shift, repairs=repairs, ff=torch.view_as_complex(ff) if want_ff else None, C=C, W=W)
