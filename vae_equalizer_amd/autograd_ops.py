@@ -13,7 +13,7 @@ against the reference's operators keeps working.  No CPU path: CPU tensors are r
 import torch
 
 from . import _native as nat
-from .engine import _f32, dp_forward, dp_loss
+from .engine import _f32, dp_forward, dp_loss, pad_to_symbols
 
 
 class _FIRDemap(torch.autograd.Function):
@@ -39,10 +39,10 @@ def _fir_bwd(x, q, y, gq, gy, amp, var, sps, M):
     n = amp.numel()
     gW = torch.empty(2, 4, M, dtype=torch.float32, device=dev)
     var2 = _f32(var, dev).reshape(1, 2).contiguous()
+    x, q, y = x.contiguous(), q.contiguous(), y.contiguous()      # locals: every argument lives until the launch is queued
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_dp_forward_bwd(1, N, sps, M, n, nat.ptr(x.contiguous()), nat.ptr(q.contiguous()), nat.ptr(y.contiguous()),
-                                                nat.ptr(gq), nat.ptr(gy), nat.ptr(amp), nat.ptr(var2), nat.ptr(gW),
-                                                nat.current_stream(dev)), "vaeq_dp_forward_bwd")
+        nat.check(nat.lib().vaeq_dp_forward_bwd(1, N, sps, M, n, nat.ptr(x), nat.ptr(q), nat.ptr(y), nat.ptr(gq), nat.ptr(gy),
+                                                nat.ptr(amp), nat.ptr(var2), nat.ptr(gW), nat.current_stream(dev)), "vaeq_dp_forward_bwd")
     return gW
 
 
@@ -50,7 +50,7 @@ def fir_demap(x, W, amp_levels, var, nu_sc, sps):
     """Differentiable twoXtwoFIR.forward: gradients flow to W (x is data)."""
     amp = _f32(amp_levels, x.device).reshape(-1)
     var_t = _f32(var, x.device).reshape(2)
-    return _FIRDemap.apply(x.contiguous(), W, amp, var_t, float(nu_sc), int(sps))
+    return _FIRDemap.apply(pad_to_symbols(x, sps).contiguous(), W, amp, var_t, float(nu_sc), int(sps))
 
 
 class _Loss(torch.autograd.Function):
@@ -68,13 +68,14 @@ class _Loss(torch.autograd.Function):
         q, rx, h, amp, P = ctx.saved_tensors
         dev, B = q.device, q.shape[-1]
         sps, M, n = rx.shape[-1] // B, h.shape[-1], amp.numel()
-        gq = torch.empty_like(q)
-        gh = torch.empty_like(h)
+        # the kernel writes row-major: allocate contiguous (empty_like would keep a permuted q's strides) and return in q's / h's shape
+        gq = torch.empty(q.shape, dtype=torch.float32, device=dev)
+        gh = torch.empty(h.shape, dtype=torch.float32, device=dev)
         up = g_loss.reshape(1).to(torch.float32).contiguous()
+        qc, rxc, hc = q.contiguous(), rx.contiguous(), h.contiguous()   # locals: temporaries freed before the launch could alias
         with torch.cuda.device(dev):
-            nat.check(nat.lib().vaeq_dp_loss_bwd(1, B, sps, M, n, nat.ptr(q.contiguous()), nat.ptr(rx.contiguous()), nat.ptr(h.contiguous()),
-                                                 nat.ptr(amp), nat.ptr(P), nat.ptr(up), nat.ptr(gq), nat.ptr(gh),
-                                                 nat.current_stream(dev)), "vaeq_dp_loss_bwd")
+            nat.check(nat.lib().vaeq_dp_loss_bwd(1, B, sps, M, n, nat.ptr(qc), nat.ptr(rxc), nat.ptr(hc), nat.ptr(amp), nat.ptr(P),
+                                                 nat.ptr(up), nat.ptr(gq), nat.ptr(gh), nat.current_stream(dev)), "vaeq_dp_loss_bwd")
         return gq, None, gh, None, None
 
 
@@ -106,17 +107,19 @@ class _AwgnFIRDemap(torch.autograd.Function):
         x, W, amp, amp_mean, var = ctx.saved_tensors
         dev, N, M = x.device, gq.shape[-1], W.shape[-1]
         gW = torch.empty(1, 2, M, dtype=torch.float32, device=dev)
+        x, gq = x.contiguous(), gq.contiguous()
         gy = gy.contiguous() if gy is not None else None
         with torch.cuda.device(dev):
-            nat.check(nat.lib().vaeq_awgn_forward_bwd(1, N, ctx.sps, M, amp.numel(), nat.ptr(x.contiguous()), nat.ptr(W), nat.ptr(amp),
-                                                      nat.ptr(amp_mean), nat.ptr(var), nat.ptr(gq.contiguous()), nat.ptr(gy), nat.ptr(gW),
-                                                      nat.current_stream(dev)), "vaeq_awgn_forward_bwd")
+            nat.check(nat.lib().vaeq_awgn_forward_bwd(1, N, ctx.sps, M, amp.numel(), nat.ptr(x), nat.ptr(W), nat.ptr(amp), nat.ptr(amp_mean),
+                                                      nat.ptr(var), nat.ptr(gq), nat.ptr(gy), nat.ptr(gW), nat.current_stream(dev)),
+                      "vaeq_awgn_forward_bwd")
         return None, gW.reshape(ctx.wshape), None, None, None, None
 
 
 def awgn_fir_demap(x, W, amp_levels, amp_mean, var, sps):
     """Differentiable twoFIR.forward: gradients flow to W (x is data)."""
-    return _AwgnFIRDemap.apply(x.contiguous(), W, _f32(amp_levels, x.device).reshape(-1), float(amp_mean), float(var), int(sps))
+    return _AwgnFIRDemap.apply(pad_to_symbols(x, sps).contiguous(), W, _f32(amp_levels, x.device).reshape(-1), float(amp_mean), float(var),
+                               int(sps))
 
 
 class _AwgnLoss(torch.autograd.Function):
@@ -138,10 +141,11 @@ class _AwgnLoss(torch.autograd.Function):
         gh = torch.empty(1, 2, M, dtype=torch.float32, device=dev)
         Pt = P.reshape(1, n).contiguous() if ctx.has_P else None
         up = g.reshape(1).to(torch.float32).contiguous()
+        qc, rxc, hc = q.contiguous(), rx.contiguous(), h.contiguous()   # locals: temporaries freed before the launch could alias
         with torch.cuda.device(dev):
-            nat.check(nat.lib().vaeq_awgn_loss_bwd(1, B, rx.shape[-1] // B, M, n, nat.ptr(q.contiguous()), nat.ptr(rx.contiguous()),
-                                                   nat.ptr(h.contiguous()), nat.ptr(amp), nat.ptr(Pt), nat.ptr(up), nat.ptr(gq), nat.ptr(gh),
-                                                   nat.current_stream(dev)), "vaeq_awgn_loss_bwd")
+            nat.check(nat.lib().vaeq_awgn_loss_bwd(1, B, rx.shape[-1] // B, M, n, nat.ptr(qc), nat.ptr(rxc), nat.ptr(hc), nat.ptr(amp),
+                                                   nat.ptr(Pt), nat.ptr(up), nat.ptr(gq), nat.ptr(gh), nat.current_stream(dev)),
+                      "vaeq_awgn_loss_bwd")
         return gq[0], None, gh[0], None, None
 
 

@@ -120,6 +120,13 @@ class DPEngine:
         return out
 
 
+def pad_to_symbols(x, sps):
+    """Zero-pad the last axis of x to ceil(L / sps) * sps samples.  The reference's Conv1d(padding=M//2, stride=sps) yields ceil(L / sps)
+    outputs and reads zeros past the end, so the padded block gives exactly its outputs; the FIR kernels take whole symbols."""
+    r = x.shape[-1] % sps
+    return x if r == 0 else torch.nn.functional.pad(x, (0, sps - r))
+
+
 def soft_demap(y, amp_levels, var, nu_sc):
     """soft_dec on device: y[R,2,2,N] (or [2,2,N]) -> q[R,2,2n,N]."""
     squeeze = y.dim() == 3
@@ -139,10 +146,11 @@ def soft_demap(y, amp_levels, var, nu_sc):
 
 
 def dp_forward(x, W, amp_levels, var, nu_sc, sps=2, want_q=True):
-    """twoXtwoFIR.forward (eval) on device: x[R,2,2,N*sps], W[R,2,4,M] -> (q[R,2,2n,N] or None, y[R,2,2,N])."""
+    """twoXtwoFIR.forward (eval) on device: x[R,2,2,L], W[R,2,4,M] -> (q[R,2,2n,N] or None, y[R,2,2,N]), N = ceil(L / sps)."""
     squeeze = x.dim() == 3
     if squeeze:
         x, W = x.unsqueeze(0), W.unsqueeze(0)
+    x = pad_to_symbols(x, sps)
     dev, R = x.device, x.shape[0]
     N, M = x.shape[-1] // sps, W.shape[-1]
     amp = _f32(amp_levels, dev).reshape(-1)
@@ -230,9 +238,9 @@ class AWGNEngine:
         return out
 
     def forward(self, x, want_q=True):
-        """Validation pass (:313): x[R,2,N*sps] -> (q[R,2n,N] or None, y[R,2,N])."""
+        """Validation pass (:313): x[R,2,L] -> (q[R,2n,N] or None, y[R,2,N]), N = ceil(L / sps) like the reference's Conv1d."""
+        x = pad_to_symbols(x, self.sps).contiguous()
         R, N = x.shape[0], x.shape[-1] // self.sps
-        x = x.contiguous()
         q = torch.empty(R, 2 * self.n_lev, N, dtype=torch.float32, device=self.device) if want_q else None
         y = torch.empty(R, 2, N, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
