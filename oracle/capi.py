@@ -364,6 +364,7 @@ def cma(rx, h, lr, sps=2, mode="CMA", batchlen=100, symb_step=10, R=1.0, dtype=n
     m = {"CMA": 0, "CMAbatch": 1, "CMAflex": 1}[mode]
     step = batchlen if mode == "CMAbatch" else symb_step
     f = getattr(lib(), "vaeq_oracle_cma" + sfx)
-    f.restype = None
-    f(N, sps, M, m, batchlen, step, _p(rx), ct(R), _p(h), C.c_double(lr), _p(out), _p(e))
+    f.restype = C.c_int
+    if f(N, sps, M, m, batchlen, step, _p(rx), ct(R), _p(h), C.c_double(lr), _p(out), _p(e)) != 0:
+        raise IndexError(f"a symbol index of N={N}, sps={sps}, M={M} falls outside the {K} outputs (the reference raises IndexError)")
     return out, e

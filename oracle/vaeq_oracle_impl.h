@@ -877,11 +877,15 @@ void FN(vaeq_oracle_nnbn_forward_eval)(int B, int sps, int n, int k1, int k2, co
  *   the end of the arrays exactly like the reference's tensor indexing does (:357);
  *   mode 0: tap update after every symbol (:371-381); mode 1: the increments of the last `batchlen` symbols are applied when
  *   k % symb_step == 0 and k >= batchlen (CMAflex :475; CMAbatch = the same with symb_step = batchlen, :421).
- * h[2][2][2][M] = [out pol][in pol][re/im][tap], updated in place; out[2][2][K], e[K][2], K = N / sps. */
-void FN(vaeq_oracle_cma)(int N, int sps, int M, int mode, int batchlen, int symb_step, const REAL *rx, REAL R, REAL *h, double lr,
-                         REAL *out, REAL *e)
+ * h[2][2][2][M] = [out pol][in pol][re/im][tap], updated in place; out[2][2][K], e[K][2], K = N / sps.
+ * Returns -2 (and touches nothing) where a symbol index falls outside [-K, K), i.e. where the reference raises IndexError: M = 1 with
+ * N % sps != 0 puts the last symbol at k = K. */
+int FN(vaeq_oracle_cma)(int N, int sps, int M, int mode, int batchlen, int symb_step, const REAL *rx, REAL R, REAL *h, double lr,
+                        REAL *out, REAL *e)
 {
     const int mh = M / 2, Lp = N + 2 * mh, K = N / sps;
+    const int J = (N + sps - 1) / sps;                                 /* symbols: mh + sps j < N + mh */
+    if (mh / sps - mh < -K || (mh + sps * (J - 1)) / sps - mh >= K) return -2;
     REAL *y = (REAL *)calloc((size_t)4 * Lp, sizeof(REAL));
     REAL *gbuf = (REAL *)calloc((size_t)K * 4 + 1, sizeof(REAL));      /* per symbol: out[0][0], out[0][1], out[1][0], out[1][1] at update time */
     int *jof = (int *)malloc(sizeof(int) * (K + 1));                   /* symbol number j stored at index k (to find its window again) */
@@ -949,6 +953,7 @@ void FN(vaeq_oracle_cma)(int N, int sps, int M, int mode, int batchlen, int symb
         }
     }
     free(y); free(gbuf); free(jof);
+    return 0;
 }
 
 #undef FN

@@ -683,6 +683,42 @@ def capture_G12(sfun, awgn):
 
 
 # --------------------------------------------------------------------------
+# G17: CMA / CMAbatch / CMAflex and CPE at shapes G12 does not reach (a tap count above 32, 1 and 3 samples per symbol, a frame length that
+#      sps does not divide, a CMAflex step that does not divide batchlen) and CPE shorter than its window and at the kernel's longest frame
+# --------------------------------------------------------------------------
+def capture_G17(sfun, awgn):
+    cases = (("G17_cma_m41_flex_sps2", dict(M=41, sps=2, N=1200, mode="CMAflex", lr=2e-5, batchlen=100, symb_step=10, seed=171)),
+             ("G17_cma_m63_sps1", dict(M=63, sps=1, N=800, mode="CMA", lr=2e-4, batchlen=100, symb_step=10, seed=172)),
+             ("G17_cma_m25_batch_sps3", dict(M=25, sps=3, N=1201, mode="CMAbatch", lr=1e-4, batchlen=50, symb_step=50, seed=173)),
+             ("G17_cma_flex_step7", dict(M=25, sps=2, N=1000, mode="CMAflex", lr=5e-5, batchlen=30, symb_step=7, seed=174)))
+    # test frames and the CPE frame search live with the float64 restatement the tests use (tests/_ref_cma.py)
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from _ref_cma import cma_frame, conditioned_cpe_frame
+    with torch.no_grad():
+        for name, c in cases:
+            rx, h0 = cma_frame(c["seed"], c["N"], c["sps"], c["M"])
+            h = torch.from_numpy(h0.copy())
+            Rx = torch.from_numpy(rx.copy())
+            if c["mode"] == "CMA":
+                out, h, e = sfun.CMA(Rx, 1, h, c["lr"], c["sps"], True)
+            elif c["mode"] == "CMAbatch":
+                out, h, e = sfun.CMAbatch(Rx, 1, h, c["lr"], c["batchlen"], c["sps"], True)
+            else:
+                out, h, e = sfun.CMAflex(Rx, 1, h, c["lr"], c["batchlen"], c["symb_step"], c["sps"], True)
+            save(name, rx=rx, h0=h0, out=t2n(out), h=t2n(h), e=t2n(e), M=np.int64(c["M"]), sps=np.int64(c["sps"]), lr=np.float64(c["lr"]),
+                 mode=np.str_(c["mode"]), batchlen=np.int64(c["batchlen"]), symb_step=np.int64(c["symb_step"]))
+        # CPE (hard-wired M_ma = 501): N = 300 lies inside one window; N = 12 800 is the longest frame vaeq_cpe takes.  The full output is
+        # kept at N = 300; at N = 12 800 every third sample and the last one (the whole frame would not fit a small capture).
+        # (int8 codes / 64, exact in float32, conditioned so that no float32 rounding can flip a pi/2 rotation between the float32
+        # reference and a float64 restatement)
+        for name, N, kind, seed in (("G17_cpe_n300", 300, "up", 175), ("G17_cpe_n12800", 12800, "down", 176)):
+            seed, codes, y = conditioned_cpe_frame(seed, N, 501, kind)
+            out = t2n(sfun.CPE(torch.from_numpy(y.copy())))
+            idx = np.unique(np.r_[0:N:3, N - 1]) if N > 1000 else np.arange(N)
+            save(name, codes=codes, scale=np.int64(64), seed=np.int64(seed), idx=idx.astype(np.int32), out=out[..., idx])
+
+
+# --------------------------------------------------------------------------
 # G1b: teacher-forced DP steps at config 5's heavy shaping (64-QAM, nu = 0.0872449 / 0.1222578, Eval_run_DP.py:24) -- where the
 #      log P terms of the KL are largest
 # --------------------------------------------------------------------------
@@ -925,7 +961,7 @@ def main():
     torch.set_num_threads(1)
     os.makedirs(OUT, exist_ok=True)
     sfun, awgn = _import_reference()
-    todo = [s for s in args.only.split(",") if s] or ["G0", "G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G1b", "G13a", "G13b", "G13c", "G13d", "G13e", "G13f", "G14", "G15", "G16"]
+    todo = [s for s in args.only.split(",") if s] or ["G0", "G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G1b", "G13a", "G13b", "G13c", "G13d", "G13e", "G13f", "G14", "G15", "G16", "G17"]
     for g in todo:
         print(f"[{g}]")
         if g == "G7":

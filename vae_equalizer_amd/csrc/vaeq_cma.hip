@@ -142,7 +142,7 @@ __global__ __launch_bounds__(64, CMA_WAVES) void cma_kernel(int N, int sps, int 
         }
         if ((j & 63) == 63 || j == J - 1) {                    // uniform: flush the parked symbols (j & ~63) .. j
             const int jl = (j & ~63) + lane;
-            if (jl <= j) {
+            if (jl <= j && !(jl - joff < 0 && jl + K < J)) {   // a wrapped symbol that symbol jl + K overwrites later is not stored (the last write wins)
                 const int kr = jl - joff, kl = kr < 0 ? kr + K : kr;
                 orun[0 * K + kl] = keep[0]; orun[1 * K + kl] = keep[1]; orun[2 * K + kl] = keep[2]; orun[3 * K + kl] = keep[3];
                 if (erun) { erun[kl * 2 + 0] = keep[4]; erun[kl * 2 + 1] = keep[5]; }
@@ -333,22 +333,25 @@ extern "C" int vaeq_cma(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t mo
                         float R_mod, float *h, const float *lr, float *out, float *e, void *stream)
 {
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
-    if (!rx || !h || !lr || !out) return VAEQ_ERR_NULL;
-    if (R < 0 || N <= 0 || N > 0x3fffffff || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63 || N / sps < 2 * M) return VAEQ_ERR_SHAPE;
+    if (R < 0 || N <= 0 || N > 0x1fffffff || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63 || N / sps < 2 * M) return VAEQ_ERR_SHAPE;   // (4 N fits an int)
+    if ((M / 2 + sps * ((N - 1) / sps)) / sps - M / 2 >= N / sps) return VAEQ_ERR_SHAPE;   // the last symbol's index past the end (M = 1, N % sps != 0): IndexError in the reference
     if (!(mode == 0 || mode == 1) || (mode == 1 && (batchlen <= 0 || symb_step <= 0 || batchlen > 4096))) return VAEQ_ERR_SHAPE;
+    if (!rx || !h || !lr || !out) return VAEQ_ERR_NULL;        // (after the shape checks: a refused shape never reaches a pointer)
     if (mode == 0) batchlen = symb_step = 0;                   // plain CMA takes neither: whatever was passed never reaches the sizing below or the kernel
     size_t lds = mode == 1 ? (size_t)batchlen * 8 * sizeof(float) : 0;
     int xcap = 64;                                             // sample ring: a power of two >= sps (batchlen + 2) + M positions
     while (mode == 1 && xcap < sps * (batchlen + 2) + M) xcap <<= 1;   // (mode 1: batchlen <= 4096 was checked above, so this ends)
     // staged samples pay when the 100-term update runs often (CMAflex: every symb_step = 10 symbols); with one update per batchlen symbols (CMAbatch)
     // the per-symbol barrier of the staged form costs more than the update gains (17.7 vs 20.3 ms per 8192-run frame)
-    const bool stage = mode == 1 && lds + (size_t)xcap * 16 <= 24 * 1024 && 4 * symb_step <= batchlen;
+    // (the staging lanes add sps samples per symbol, one each: sps <= 64)
+    const bool stage = mode == 1 && lds + (size_t)xcap * 16 <= 24 * 1024 && 4 * symb_step <= batchlen && sps <= 64;
     if (stage) lds += (size_t)xcap * 16;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     void (*k)(int, int, int, int, int, int, int, const float *, float, float *, const float *, float *, float *) =
         M <= 32 ? (stage ? vaeq::cma_kernel<true, true> : vaeq::cma_kernel<true, false>) : (stage ? vaeq::cma_kernel<false, true> : vaeq::cma_kernel<false, false>);
     if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return VAEQ_ERR_LDS;
+    vaeq::note_kernel("vaeq::cma_kernel<%s, %s>", M <= 32 ? "true" : "false", stage ? "true" : "false");
     hipLaunchKernelGGL(k, dim3(R), dim3(64), lds, st, (int)N, sps, M, mode, batchlen, symb_step, xcap - 1, rx, R_mod, h, lr, out, e);
     return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
 }
@@ -356,13 +359,14 @@ extern "C" int vaeq_cma(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t mo
 extern "C" int vaeq_cpe(int32_t R, int64_t N, int32_t M_ma, const float *y, float *y_out, void *stream)
 {
     if (R == 0 || N == 0) return VAEQ_OK;
-    if (!y || !y_out) return VAEQ_ERR_NULL;
     if (R < 0 || N < 0 || N > 12800 || M_ma <= 0 || (M_ma & 1) == 0) return VAEQ_ERR_SHAPE;   // three N-float tracks of one polarisation live in LDS
+    if (!y || !y_out) return VAEQ_ERR_NULL;
     const size_t lds = (size_t)3 * N * sizeof(float);
     auto k = vaeq::cpe_kernel;
     if (lds > 32 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return VAEQ_ERR_LDS;
+    vaeq::note_kernel("vaeq::cpe_kernel");
     hipLaunchKernelGGL(k, dim3(R), dim3(vaeq::CPE_NT), lds, reinterpret_cast<hipStream_t>(stream), (int)N, M_ma, y, y_out);
     return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
 }
