@@ -1701,9 +1701,11 @@ static int launch_nn_validate(int R, int N, int sps, int M, int k1, int k2, int 
 {
     const size_t lds = (size_t)nn_layout(NN_TILE, sps, M, NLEV, k1, k2, bn != nullptr, true).total * 4 + (((size_t)N + 15) & ~(size_t)15);
     if (lds > 150 * 1024) return VAEQ_ERR_LDS;
-    auto k = (NLEV == 8 && sps == 2 && M == 25 && k1 == 25 && k2 == 3) ? nn_validate_kernel<1024, NLEV, NLEV == 8 ? 1 : 0> : nn_validate_kernel<1024, NLEV, 0>;   // (64-QAM only: see launch_nn_train)
+    const int bk = NLEV == 8 && sps == 2 && M == 25 && k1 == 25 && k2 == 3;                       // (64-QAM only: see launch_nn_train)
+    auto k = bk ? nn_validate_kernel<1024, NLEV, NLEV == 8 ? 1 : 0> : nn_validate_kernel<1024, NLEV, 0>;
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return VAEQ_ERR_LDS;
+    note_kernel("vaeq::nn_validate_kernel<1024, %d, %d>", NLEV, bk);
     hipLaunchKernelGGL(k, dim3(R), dim3(1024), lds, st, N, sps, M, k1, k2, n_shift, x, theta, bn, amp, data, ser, shift);
     return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
 }
@@ -1712,13 +1714,15 @@ template <int NLEV>
 static int launch_nn_train(const vaeq_nn_args &a, size_t lds, hipStream_t st)
 {
     void (*k)(const vaeq_nn_args) = a.batch_norm ? nn_train_kernel<512, NLEV, true, 0> : nn_train_kernel<512, NLEV, false, 0>;
-    if (a.sps == 2) k = a.batch_norm ? nn_train_kernel<512, NLEV, true, 2> : nn_train_kernel<512, NLEV, false, 2>;
+    int sps_t = 0, bk = 0;                                     // template arguments of k, for note_kernel
+    if (a.sps == 2) { k = a.batch_norm ? nn_train_kernel<512, NLEV, true, 2> : nn_train_kernel<512, NLEV, false, 2>; sps_t = 2; }
     // the sweep script's shape baked: fully (layout + trip counts) for 64-QAM, +18 % (Net) / +14 % (Net_BN); for 16-QAM only the LDS layout (+10 % / +7 %:
     // with constant trip counts the compiler unrolls into 54-73 spilled registers there, -1 ... -13 %); 4-QAM keeps the run-time shape (either form
     // costs it a resident workgroup per CU: -20 ... -27 %)
     if ((NLEV == 8 || NLEV == 4) && a.sps == 2 && a.B == 300 && a.M == 25 && a.k1 == 25 && a.k2 == 3) {
         constexpr int BK = NLEV == 8 ? 1 : NLEV == 4 ? 2 : 0;
         k = a.batch_norm ? nn_train_kernel<512, NLEV, true, 2, BK> : nn_train_kernel<512, NLEV, false, 2, BK>;
+        bk = BK;
     }
     int nt = 512;
     if constexpr (NLEV == 8) {
@@ -1730,6 +1734,7 @@ static int launch_nn_train(const vaeq_nn_args &a, size_t lds, hipStream_t st)
             auto kh = nn_train_half_kernel<256, 1>;
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh) != hipSuccess)
                 return VAEQ_ERR_LDS;
+            note_kernel("vaeq::nn_train_half_kernel<256, 1>");
             hipLaunchKernelGGL(kh, dim3(a.R), dim3(256), ldh, st, a);
             return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
         }
@@ -1743,6 +1748,7 @@ static int launch_nn_train(const vaeq_nn_args &a, size_t lds, hipStream_t st)
     }
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return VAEQ_ERR_LDS;
+    note_kernel("vaeq::nn_train_kernel<%d, %d, %s, %d, %d>", nt, NLEV, a.batch_norm ? "true" : "false", sps_t, bk);   // every template argument
     hipLaunchKernelGGL(k, dim3(a.R), dim3(nt), lds, st, a);
     return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
 }
@@ -1756,6 +1762,7 @@ static int launch_nn_forward(int R, int N, int sps, int M, int k1, int k2, const
     auto k = nn_forward_kernel<1024, NLEV>;
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return VAEQ_ERR_LDS;
+    note_kernel("vaeq::nn_forward_kernel<1024, %d>", NLEV);
     hipLaunchKernelGGL(k, dim3(R), dim3(1024), lds, st, N, sps, M, k1, k2, x, theta, bn, q);
     return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
 }

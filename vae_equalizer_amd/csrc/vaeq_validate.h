@@ -49,7 +49,7 @@ __device__ __forceinline__ void validate_tail(int N, int n_shift, const unsigned
     const int sh = *sh_s, len = N - 22 - sh, K = NLEV - 1;
     const float scale = 0.5f * (float)K;
     float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;
-    for (int j = tid; j < len; j += NT) {
+    for (int j = 11 + sh <= 0 ? len : tid; j < len; j += NT) {  // (skipped where the SER is NaN: below -11 decs[11 + sh + j] would read in front of the decisions)
         const int dd = decs[11 + sh + j], dI = dd & 15, dQ = dd >> 4;
         const int aI = (int)rintf(__fadd_rn(__fmul_rn(scale, __half2float(tI[11 + j])), scale));
         const int aQ = (int)rintf(__fadd_rn(__fmul_rn(scale, __half2float(tQ[11 + j])), scale));
@@ -63,7 +63,8 @@ __device__ __forceinline__ void validate_tail(int N, int n_shift, const unsigned
     const float r0 = red[0], r1 = red[1], r2 = red[2];
     __syncthreads();
     block_reduce3<NT>(c3, 0.f, 0.f, red);
-    if (tid == 0) *ser_out = fminf(fminf(r0, r1), fminf(r2, red[0])) / (float)len;
+    // sh <= -11: data[:, 11 : -11-sh] is empty in the reference (and q[:, 11+sh : -11] too below -11): its mean over no symbols is NaN
+    if (tid == 0) *ser_out = 11 + sh <= 0 ? __int_as_float(0x7fc00000) : fminf(fminf(r0, r1), fminf(r2, red[0])) / (float)len;
 }
 
 }  // namespace vaeq
