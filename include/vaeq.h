@@ -314,6 +314,27 @@ int64_t vaeq_nn_lds_bytes(int32_t B, int32_t sps, int32_t M, int32_t n_lev, int3
 int vaeq_nn_forward(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t k1, int32_t k2, const float *x,
                     const float *theta, const float *bn_running, float *q, void *stream);
 
+/* The VAE-NN encoder as a stand-alone differentiable operator (func_VAENN_MQAM.Net :170-188 / Net_BN :190-211; the kernels behind the torch
+ * modules of the same names), batched over R runs.  These calls act on the NETWORK's parameters only (h_est belongs to the loss):
+ *   theta_net = [fc1.weight C*2*k1 | fc1.bias C | fc2.weight C*C*k2 | fc2.bias C]  (Net_BN: ... | batch1.weight C | batch1.bias C),  C = 2 n_lev,
+ * vaeq_nn_enc_param_count() floats = vaeq_nn_param_count() - 2 M.  x[R][2][L] with any L >= 1, q[R][2 n_lev][N], N = ceil(L / sps).
+ * The reference's residual x_res (:183-185) is constant across the levels of an axis and cancels in the softmax; it is left out.
+ * vaeq_nn_enc_forward: training == 0, or Net in either mode: the tiled eval forward of vaeq_nn_forward, no length limit (Net_BN normalises with
+ *   bn_running[R][2][C] = running_mean | running_var, read only).  Net_BN with training != 0: batch statistics over the L samples (biased
+ *   variance, L >= 2); bn_saved[R][2][C] (nullable) receives mean | 1 / std for the backward pass, bn_running (nullable) moves by momentum 0.1
+ *   with the unbiased variance.
+ * vaeq_nn_enc_backward: q = the forward's output, gq[R][2 n_lev][N] = ANY upstream gradient dL/dq -> g_theta_net[R][NPnet]; x gets no gradient.
+ *   bn_stats: Net: ignored; Net_BN training: the forward's bn_saved; Net_BN eval: bn_running.  ELU(fc1(x)) is recomputed, not saved.
+ * The training-mode Net_BN forward and every backward keep a run's whole input in LDS, one workgroup per run: VAEQ_ERR_LDS when
+ * vaeq_nn_enc_lds_bytes() exceeds 160 KiB.  No atomics: results are bit-reproducible and do not depend on R. */
+int64_t vaeq_nn_enc_param_count(int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm);
+int64_t vaeq_nn_enc_lds_bytes(int64_t L, int32_t sps, int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm);
+int vaeq_nn_enc_forward(int32_t R, int64_t L, int32_t sps, int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm, int32_t training,
+                        const float *x, const float *theta_net, float *bn_running, float *bn_saved, float *q, void *stream);
+int vaeq_nn_enc_backward(int32_t R, int64_t L, int32_t sps, int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm, int32_t training,
+                         const float *x, const float *theta_net, const float *q, const float *gq, const float *bn_stats,
+                         float *g_theta_net, void *stream);
+
 /* The whole VAE-NN validation block (:287-301: eval forward, find_shift :147-166, SER_q :97-123) in one call, q not materialised:
  * x[R][2][N*sps], theta[R][NP], data_f16[R][2][N] -> ser[R], shift[R] (nullable). */
 int vaeq_nn_validate(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t k1, int32_t k2, int32_t n_shift, const float *x,
@@ -409,7 +430,7 @@ const char *vaeq_strerror(int code);
 
 /* Measurement helpers (no reference counterpart; SURVEY 8d asks for them).
  * vaeq_last_kernel: name of the kernel instantiation the calling thread's most recent vaeq_dp_train / vaeq_awgn_train / vaeq_cma / vaeq_cpe /
- * vaeq_nn_train / vaeq_nn_forward / vaeq_nn_validate launched (as a profiler prints it, e.g. "vaeq::dp_wave_kernel<25, 8, 100, true, 1, 1>" or "vaeq::cma_kernel<true, false>"), copied into
+ * vaeq_nn_train / vaeq_nn_forward / vaeq_nn_validate / vaeq_nn_enc_forward / vaeq_nn_enc_backward launched (as a profiler prints it, e.g. "vaeq::dp_wave_kernel<25, 8, 100, true, 1, 1>" or "vaeq::cma_kernel<true, false>"), copied into
  * buf[len] -- bench.py names its roofline kernel from this, the tests check which vaeq_cma instantiation a shape reaches.
  * vaeq_stream_copy: dst[bytes] = src[bytes] with a plain 16-byte grid-stride copy kernel (bytes and both pointers multiples of 16): the
  * measured HBM copy bandwidth that stands next to the 8 TB/s spec peak in the roofline. */

@@ -13,8 +13,8 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("VAEQ_LIB") or os.path.join(_PKG, "libvaeq_hip.so")   # VAEQ_LIB: A/B builds of the kernels (tools/build_variant.sh)
-SOURCES = ["vaeq_dp.hip", "vaeq_dp_wave.hip", "vaeq_dp_wave_mw.hip", "vaeq_dp_wave_mw8.hip", "vaeq_dp_wave_bk.hip", "vaeq_dp_wave_b128.hip", "vaeq_dp_wave_fl.hip", "vaeq_awgn.hip", "vaeq_awgn_wave.hip", "vaeq_misc.hip", "vaeq_nn.hip", "vaeq_cma.hip", "vaeq_awgn_cma.hip", "vaeq_awgn_dfe.hip", "vaeq_epilogue.hip", "vaeq_gen.hip"]
-HEADERS = ["vaeq_common.h", "vaeq_wave.h", "vaeq_validate.h", "vaeq_dp_wave_kernel.h", "vaeq_gen_fused.h", "vaeq_epilogue_lds.h", "vaeq_noise.h", "vaeq_awgn_eval.h"]
+SOURCES = ["vaeq_dp.hip", "vaeq_dp_wave.hip", "vaeq_dp_wave_mw.hip", "vaeq_dp_wave_mw8.hip", "vaeq_dp_wave_bk.hip", "vaeq_dp_wave_b128.hip", "vaeq_dp_wave_fl.hip", "vaeq_awgn.hip", "vaeq_awgn_wave.hip", "vaeq_misc.hip", "vaeq_nn.hip", "vaeq_nn_ops.hip", "vaeq_cma.hip", "vaeq_awgn_cma.hip", "vaeq_awgn_dfe.hip", "vaeq_epilogue.hip", "vaeq_gen.hip"]
+HEADERS = ["vaeq_common.h", "vaeq_wave.h", "vaeq_validate.h", "vaeq_dp_wave_kernel.h", "vaeq_gen_fused.h", "vaeq_epilogue_lds.h", "vaeq_noise.h", "vaeq_awgn_eval.h", "vaeq_nn_dev.h"]
 _LIB = None
 
 
@@ -104,7 +104,8 @@ class NNArgs(C.Structure):
 
 # every symbol include/vaeq.h declares; tests check the library exports all of them
 EXPORTS = ["vaeq_dp_train", "vaeq_dp_step_debug", "vaeq_dp_lds_bytes", "vaeq_dp_resident_runs", "vaeq_soft_demap", "vaeq_dp_forward", "vaeq_dp_loss", "vaeq_dp_loss_bwd", "vaeq_dp_forward_bwd", "vaeq_dp_epilogue", "vaeq_dp_epilogue_ws_bytes", "vaeq_dp_epilogue_compact", "vaeq_gen_dp_tx", "vaeq_gen_dp_disperse", "vaeq_gen_dp_finish", "vaeq_gen_dp_frame", "vaeq_awgn_train",
-           "vaeq_awgn_lds_bytes", "vaeq_awgn_forward", "vaeq_awgn_validate", "vaeq_awgn_validate_gen", "vaeq_gen_awgn_clean", "vaeq_awgn_loss", "vaeq_awgn_loss_bwd", "vaeq_awgn_forward_bwd", "vaeq_gen_awgn", "vaeq_nn_train", "vaeq_nn_param_count", "vaeq_nn_lds_bytes", "vaeq_nn_forward", "vaeq_nn_validate", "vaeq_cma", "vaeq_cpe", "vaeq_version", "vaeq_strerror", "vaeq_last_kernel", "vaeq_stream_copy", "vaeq_gen_dp_power_parts", "vaeq_cma_epilogue",
+           "vaeq_awgn_lds_bytes", "vaeq_awgn_forward", "vaeq_awgn_validate", "vaeq_awgn_validate_gen", "vaeq_gen_awgn_clean", "vaeq_awgn_loss", "vaeq_awgn_loss_bwd", "vaeq_awgn_forward_bwd", "vaeq_gen_awgn", "vaeq_nn_train", "vaeq_nn_param_count", "vaeq_nn_lds_bytes", "vaeq_nn_forward", "vaeq_nn_validate", "vaeq_nn_enc_param_count", "vaeq_nn_enc_lds_bytes", "vaeq_nn_enc_forward",
+           "vaeq_nn_enc_backward", "vaeq_cma", "vaeq_cpe", "vaeq_version", "vaeq_strerror", "vaeq_last_kernel", "vaeq_stream_copy", "vaeq_gen_dp_power_parts", "vaeq_cma_epilogue",
            "vaeq_awgn_cma", "vaeq_awgn_cma_validate", "vaeq_awgn_cma_validate_ws_bytes", "vaeq_awgn_lmmse_eval",
            "vaeq_awgn_lmmse_eval_ws_bytes", "vaeq_awgn_dfe", "vaeq_awgn_dfe_ws_bytes"]
 
@@ -171,6 +172,15 @@ def lib():
         L.vaeq_nn_lds_bytes.argtypes = [C.c_int32] * 7
         L.vaeq_nn_forward.restype = C.c_int
         L.vaeq_nn_forward.argtypes = [C.c_int32, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 5
+        if hasattr(L, "vaeq_nn_enc_forward"):               # (absent from older A/B builds loaded through VAEQ_LIB)
+            L.vaeq_nn_enc_param_count.restype = C.c_int64
+            L.vaeq_nn_enc_param_count.argtypes = [C.c_int32] * 4
+            L.vaeq_nn_enc_lds_bytes.restype = C.c_int64
+            L.vaeq_nn_enc_lds_bytes.argtypes = [C.c_int64] + [C.c_int32] * 5
+            L.vaeq_nn_enc_forward.restype = C.c_int
+            L.vaeq_nn_enc_forward.argtypes = [C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 6
+            L.vaeq_nn_enc_backward.restype = C.c_int
+            L.vaeq_nn_enc_backward.argtypes = [C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 7
         L.vaeq_cma.restype = C.c_int
         L.vaeq_cma.argtypes = [C.c_int32, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p, C.c_float] + [C.c_void_p] * 5
         L.vaeq_cpe.restype = C.c_int

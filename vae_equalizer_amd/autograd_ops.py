@@ -1,4 +1,4 @@
-"""torch.autograd.Function wrappers of the two stand-alone operators, forward AND backward on HIP kernels.
+"""torch.autograd.Function wrappers of the stand-alone operators (FIR + demapper, ELBO, VAE-NN encoder), forward AND backward on HIP kernels.
 
 They make a reference-style training loop
 
@@ -154,3 +154,103 @@ def awgn_elbo_loss(q, rx, h_est, amp_levels, P=None):
     dev = q.device
     Pt = None if P is None else _f32(P, dev).reshape(-1).contiguous()
     return _AwgnLoss.apply(q, rx.contiguous().float(), h_est, _f32(amp_levels, dev).reshape(-1).contiguous(), Pt)
+
+
+# ------------------------------------------------------------------ the VAE-NN encoder (func_VAENN_MQAM.Net / Net_BN)
+def _enc_check(code, what):
+    if int(code) == -3:
+        raise nat.VaeqError(f"{what} failed: VAEQ_ERR_LDS: {nat.lib().vaeq_strerror(-3).decode()} -- the training-mode Net_BN forward and "
+                            "the backward pass keep the whole input in LDS (vaeq_nn_enc_lds_bytes); shorten the minibatch (code -3)")
+    nat.check(code, what)
+
+
+def _enc_dims(params, sps, batch_norm):
+    if len(params) != (6 if batch_norm else 4):
+        raise ValueError(f"expected {'6 (fc1, fc2, batch1)' if batch_norm else '4 (fc1, fc2)'} parameter tensors, got {len(params)}")
+    w1, w2 = params[0], params[2]
+    C_ = w2.shape[0]
+    if w1.dim() != 3 or w2.dim() != 3 or tuple(w1.shape[:2]) != (C_, 2) or w2.shape[1] != C_ or C_ % 2:
+        raise ValueError(f"fc1.weight must be [C, 2, k1] and fc2.weight [C, C, k2], got {tuple(w1.shape)} and {tuple(w2.shape)}")
+    return int(sps), C_ // 2, int(w1.shape[-1]), int(w2.shape[-1])
+
+
+def _enc_forward(x, theta, dims, batch_norm, training, bn):
+    """x[R,2,L] contiguous f32, theta[R,NP] -> (q[R,2n,N], saved statistics or None); bn[R,2C] is updated in place in training mode."""
+    sps, n, k1, k2 = dims
+    px, dev, (R, _, L) = nat.ptr(x), x.device, x.shape         # (a CPU tensor is refused here, before anything is allocated)
+    q = torch.empty(R, 2 * n, -(-L // sps), dtype=torch.float32, device=dev)
+    saved = torch.empty(R, 4 * n, dtype=torch.float32, device=dev) if batch_norm and training else None
+    with torch.cuda.device(dev):
+        _enc_check(nat.lib().vaeq_nn_enc_forward(R, L, sps, n, k1, k2, int(batch_norm), int(training), px, nat.ptr(theta), nat.ptr(bn),
+                                                 nat.ptr(saved), nat.ptr(q), nat.current_stream(dev)), "vaeq_nn_enc_forward")
+    return q, saved
+
+
+LAST_BACKWARD_KERNEL = None     # instantiation the latest encoder backward launched: autograd runs backward on a thread of its own, and
+                                # vaeq_last_kernel answers per calling thread
+
+
+def _enc_backward(x, theta, q, gq, stats, dims, batch_norm, training):
+    global LAST_BACKWARD_KERNEL
+    sps, n, k1, k2 = dims
+    dev, (R, _, L) = x.device, x.shape
+    g = torch.empty_like(theta)
+    with torch.cuda.device(dev):
+        _enc_check(nat.lib().vaeq_nn_enc_backward(R, L, sps, n, k1, k2, int(batch_norm), int(training), nat.ptr(x), nat.ptr(theta), nat.ptr(q),
+                                                  nat.ptr(gq), nat.ptr(stats), nat.ptr(g), nat.current_stream(dev)), "vaeq_nn_enc_backward")
+    LAST_BACKWARD_KERNEL = nat.last_kernel()
+    return g
+
+
+class _NNEncode(torch.autograd.Function):
+    """Net.forward / Net_BN.forward (func_VAENN_MQAM.py:178-188, :200-211): (x[1,2,L], the network's parameters) -> q[1,2n,N].  The saved state
+    is x, a flat COPY of the parameters, q and the 2 C BatchNorm statistics: ELU(fc1(x)) is recomputed by the backward kernel."""
+
+    @staticmethod
+    def forward(ctx, x, dims, batch_norm, training, bn, *params):
+        theta = torch.cat([p.detach().reshape(-1) for p in params]).to(torch.float32).reshape(1, -1).contiguous()
+        q, saved = _enc_forward(x, theta, dims, batch_norm, training, bn)
+        stats = saved if batch_norm and training else (bn.clone() if batch_norm else None)
+        ctx.save_for_backward(x, theta, q, stats)
+        ctx.dims, ctx.batch_norm, ctx.training, ctx.shapes = dims, batch_norm, training, [tuple(p.shape) for p in params]
+        return q
+
+    @staticmethod
+    def backward(ctx, gq):
+        x, theta, q, stats = ctx.saved_tensors
+        gq = gq.to(torch.float32).contiguous()                  # a local: lives until the launch is queued
+        g = _enc_backward(x, theta, q, gq, stats, ctx.dims, ctx.batch_norm, ctx.training)[0]
+        parts = torch.split(g, [int(torch.Size(s).numel()) for s in ctx.shapes])
+        grads = tuple(p.reshape(s) if need else None for p, s, need in zip(parts, ctx.shapes, ctx.needs_input_grad[5:]))
+        return (None, None, None, None, None) + grads
+
+
+def nn_encode(x, params, sps, batch_norm=False, training=False, running_mean=None, running_var=None):
+    """Differentiable VAE-NN encoder: x[1,2,L] (or [2,L]) -> q[1,2n,ceil(L/sps)] (or [2n,N]); gradients flow to ``params`` =
+    (fc1.weight, fc1.bias, fc2.weight, fc2.bias[, batch1.weight, batch1.bias]); x is data.  batch_norm + training: batch statistics, and
+    running_mean / running_var (when given) move in place by momentum 0.1; batch_norm without training: they normalise.
+    With autograd off, or no parameter requiring a gradient, this is a plain kernel call."""
+    params = tuple(params)
+    dims = _enc_dims(params, sps, batch_norm)
+    if x.dim() not in (2, 3) or x.shape[-2] != 2 or (x.dim() == 3 and x.shape[0] != 1) or x.shape[-1] < 1:
+        raise ValueError(f"x must be [1, 2, L] or [2, L], got {tuple(x.shape)}")
+    if not x.is_cuda:
+        nat.ptr(x)                                              # raises: the kernels take device tensors (no CPU path)
+    xc = x.detach().to(torch.float32).reshape(1, 2, -1).contiguous()
+    bn = None
+    if batch_norm:
+        if (running_mean is None or running_var is None) and not training:
+            raise ValueError("eval-mode BatchNorm needs running_mean and running_var")
+        if running_mean is not None and running_var is not None:
+            bn = torch.cat([running_mean.detach().reshape(-1), running_var.detach().reshape(-1)]).to(torch.float32).reshape(1, -1).contiguous()
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        q = _NNEncode.apply(xc, dims, bool(batch_norm), bool(training), bn, *params)
+    else:
+        theta = torch.cat([p.detach().reshape(-1) for p in params]).to(torch.float32).reshape(1, -1).contiguous()
+        q = _enc_forward(xc, theta, dims, bool(batch_norm), bool(training), bn)[0]
+    if batch_norm and training and bn is not None:
+        C_ = 2 * dims[1]
+        with torch.no_grad():
+            running_mean.copy_(bn[0, :C_])
+            running_var.copy_(bn[0, C_:])
+    return q if x.dim() == 3 else q[0]

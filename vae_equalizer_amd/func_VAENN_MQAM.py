@@ -1,9 +1,15 @@
 """Drop-in for AWGN_channel/func_VAENN_MQAM.py: same ``processing`` signature (:215) and return value (:304); the
 training loop and the validation pass run on the HIP kernels (engine.NNEngine: vaeq_nn_train, vaeq_nn_validate).
 
-Both topologies of the reference are implemented: ``net_type='Net'`` and ``'Net_BN'`` (BatchNorm1d between the ELU and fc2)."""
+Both topologies of the reference are implemented: ``net_type='Net'`` and ``'Net_BN'`` (BatchNorm1d between the ELU and fc2).
+
+``Net`` and ``Net_BN`` (:170-211) are torch modules with the reference's constructor, submodule names and ``state_dict``; their forward and
+backward passes are the HIP encoder kernels (autograd_ops.nn_encode: vaeq_nn_enc_forward / vaeq_nn_enc_backward), so the reference's loop
+``net(minibatch) -> loss_function -> loss.backward() -> optimizer.step()`` runs unchanged.  ``processing`` does not use them: it trains with the
+fused kernel.  ``net_to_theta`` / ``theta_to_net`` convert between a module plus h_est and the engine's flat vectors."""
 import numpy as np
 import torch
+from torch import nn
 
 from . import channel as ch
 from .dp_runs import _host_pool, default_device
@@ -55,6 +61,80 @@ def loss_function(q, rx, h, device, amp_levels):
         return awgn_elbo_loss(q, rx, h, amp_levels, None)
     from .engine import awgn_loss
     return awgn_loss(q, rx, h.detach(), amp_levels, None)
+
+
+class _Encoder(nn.Module):
+    """fc1 = Conv1d(2, C, k1, pad k1 // 2) -> ELU [-> batch1 = BatchNorm1d(C)] -> fc2 = Conv1d(C, C, k2, pad k2 // 2, stride sps) -> softmax per
+    axis, C = 2 num_lev.  The submodules only hold the parameters and buffers (so that state_dict() has the reference's keys and shapes and
+    checkpoints interchange in both directions); the arithmetic is the HIP kernels'.  The reference's residual x_res (:183-185) is the same
+    for every level of an axis and cancels in the softmax: it is not computed."""
+    _batch_norm = False
+
+    def __init__(self, kernel_1, kernel_2, num_lev, sps):
+        super().__init__()
+        C_ = 2 * num_lev
+        self.fc1 = nn.Conv1d(2, C_, kernel_1, bias=True, padding=kernel_1 // 2)
+        self.fc2 = nn.Conv1d(C_, C_, kernel_2, bias=True, padding=kernel_2 // 2, stride=sps)
+        if self._batch_norm:
+            self.batch1 = nn.BatchNorm1d(C_)
+            nn.init.kaiming_uniform_(self.fc1.weight)
+        else:
+            nn.init.xavier_uniform_(self.fc1.weight, gain=1)
+        nn.init.xavier_uniform_(self.fc2.weight, gain=1)
+
+    def _params(self):
+        p = [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
+        return p + [self.batch1.weight, self.batch1.bias] if self._batch_norm else p
+
+    def forward(self, x):
+        """x[1,2,L] -> netout[1,2 num_lev,ceil(L/sps)] float32.  With autograd on and a parameter requiring a gradient the result carries the
+        HIP-backed graph; self.training selects the BatchNorm mode, and a training-mode forward moves the running statistics (also under
+        no_grad, as PyTorch does).  CPU tensors are refused."""
+        from .autograd_ops import nn_encode
+        if x.dim() != 3 or x.shape[0] != 1 or x.shape[1] != 2:
+            raise ValueError(f"x must be [1, 2, L], got {tuple(x.shape)}")
+        if not self._batch_norm:
+            return nn_encode(x, self._params(), self.fc2.stride[0])
+        b = self.batch1
+        q = nn_encode(x, self._params(), self.fc2.stride[0], True, self.training, b.running_mean, b.running_var)
+        if self.training:
+            b.num_batches_tracked += 1
+        return q
+
+
+class Net(_Encoder):
+    """Net (:170-188): xavier_uniform_ on both convolution weights."""
+
+
+class Net_BN(_Encoder):
+    """Net_BN (:190-211): BatchNorm1d between the ELU and fc2, kaiming_uniform_ on fc1.weight."""
+    _batch_norm = True
+
+
+def net_to_theta(net, h_est):
+    """(module, h_est[2,M]) -> (theta[NP] in NNEngine.offsets() order, bn[2C] = running_mean | running_var, or None for Net)."""
+    parts = [p.detach().reshape(-1) for p in net._params()] + [h_est.detach().reshape(-1)]
+    theta = torch.cat([p.to(torch.float32) for p in parts])
+    bn = torch.cat([net.batch1.running_mean, net.batch1.running_var]).to(torch.float32) if net._batch_norm else None
+    return theta, bn
+
+
+def theta_to_net(theta, net, bn=None):
+    """Load one run's flat engine vector theta[NP] (and bn[2C] for Net_BN) into the module, in place -> h_est[2,M] (a new tensor)."""
+    theta = torch.as_tensor(theta).detach().reshape(-1)
+    params = net._params()
+    sizes = [p.numel() for p in params]
+    n_net = sum(sizes)
+    if theta.numel() <= n_net or (theta.numel() - n_net) % 2:
+        raise ValueError(f"theta has {theta.numel()} entries; the network alone takes {n_net}, h_est an even number more")
+    with torch.no_grad():
+        for p, v in zip(params, torch.split(theta[:n_net], sizes)):
+            p.copy_(v.reshape(p.shape))
+        if net._batch_norm and bn is not None:
+            bn = torch.as_tensor(bn).detach().reshape(2, -1)
+            net.batch1.running_mean.copy_(bn[0])
+            net.batch1.running_var.copy_(bn[1])
+    return theta[n_net:].reshape(2, -1).to(torch.float32).clone()
 
 
 def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_valid, N_train, num_epochs, epe, channel, device=None,
