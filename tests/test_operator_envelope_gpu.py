@@ -76,7 +76,7 @@ def _run(fn_name, *args):
     nat.check(_call(fn_name, *args), fn_name)
 
 
-# ------------------------------------------------------------------ the entry points' LDS formulas (csrc/vaeq_misc.hip, csrc/vaeq_awgn.hip)
+# ------------------------------------------------------------------ the entry points' LDS formulas (csrc/vaeq_ops.hip)
 LDS = {  # bytes of dynamic LDS for size B (or N), sps, M
     "vaeq_dp_loss": lambda B, sps, M: 4 * (8 * B + 8 * M + 2 * M + 64),
     "vaeq_dp_loss_bwd": lambda B, sps, M: 4 * (8 * B + 4 * (B * sps - 2 * (M // 2)) + 10 * M + 64),

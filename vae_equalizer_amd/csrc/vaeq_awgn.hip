@@ -1,4 +1,6 @@
-// vaeq_awgn.hip -- single-polarisation (AWGN / ISI channel) VAE-LE training loop for gfx950.
+// vaeq_awgn.hip -- single-polarisation (AWGN / ISI channel) VAE-LE for gfx950: the generic training kernel (vaeq_awgn_train; the wave-per-run
+// fast path is vaeq_awgn_wave.hip) and the fused validation kernels (vaeq_awgn_validate, vaeq_awgn_validate_gen).  The stand-alone AWGN
+// operators are in vaeq_ops.hip.
 //
 // Same structure as vaeq_dp.hip (one workgroup = one run, everything in LDS) for the 1x1 variant of
 // AWGN_channel/func_VAELE_MQAM_shaping.py:
@@ -17,6 +19,7 @@
 
 #include "vaeq.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 #include "vaeq_noise.h"
 #include "vaeq_wave.h"
 #include "vaeq_validate.h"
@@ -32,8 +35,6 @@ struct AWGNLayout {
     int xs, Ws, hs, mW, vW, xW, mH, vH, xH, gW, gH, ys, mu, vr, t3, kc, gy, es, VS, red, total;
 };
 
-__host__ __device__ inline int apad4(int x) { return (x + 3) & ~3; }
-
 __host__ __device__ inline AWGNLayout awgn_layout(int B, int sps, int M)
 {
     AWGNLayout l;
@@ -41,9 +42,9 @@ __host__ __device__ inline AWGNLayout awgn_layout(int B, int sps, int M)
     l.mh = M / 2;
     l.Mh = 2 * l.mh;
     l.nm = l.L - l.Mh;
-    l.Lp = apad4(l.L + 2 * l.mh);
+    l.Lp = pad4(l.L + 2 * l.mh);
     int o = 0;
-    auto take = [&](int n) { int r = o; o += apad4(n); return r; };
+    auto take = [&](int n) { int r = o; o += pad4(n); return r; };
     l.xs = take(2 * l.Lp);
     l.Ws = take(2 * M); l.hs = take(2 * M);
     l.mW = take(2 * M); l.vW = take(2 * M); l.xW = take(2 * M);
@@ -280,53 +281,6 @@ __global__ __launch_bounds__(NT) void awgn_train_kernel(const vaeq_awgn_args a)
     if (tid == 0 && !a.no_update) a.step[run] = step;
 }
 
-// twoFIR.forward in eval mode on N symbols (validation, :311-313): one workgroup per run, two passes over y.
-template <int NLEV>
-__global__ __launch_bounds__(256) void awgn_forward_kernel(int64_t N, int sps, int M, const float *__restrict__ x, const float *__restrict__ W,
-                                                           const float *__restrict__ amp_g, const float *__restrict__ amp_mean,
-                                                           const float *__restrict__ var, float *__restrict__ q, float *__restrict__ yout)
-{
-    __shared__ float Ws[2 * 64];
-    __shared__ float red[64];
-    const int run = blockIdx.x, tid = threadIdx.x;
-    for (int i = tid; i < 2 * M; i += 256) Ws[i] = W[(size_t)run * 2 * M + i];
-    __syncthreads();
-    const int64_t L = N * sps;
-    const int pad = (M - 1) / 2;
-    const float *x0 = x + (size_t)run * 2 * L, *x1 = x0 + L;
-    float *y0 = yout + (size_t)run * 2 * N, *y1 = y0 + N;
-    float sa0 = 0.f, sa1 = 0.f;
-    for (int64_t n = tid; n < N; n += 256) {
-        float yI = 0.f, yQ = 0.f;
-        for (int k = 0; k < M; k++) {
-            const int64_t s = n * sps + k - pad;
-            if (s < 0 || s >= L) continue;
-            const float a_ = x0[s], b_ = x1[s];
-            yI = fmaf(Ws[k], a_, yI); yI = fmaf(Ws[M + k], b_, yI);
-            yQ = fmaf(Ws[k], b_, yQ); yQ = fmaf(-Ws[M + k], a_, yQ);
-        }
-        y0[n] = yI; y1[n] = yQ;
-        sa0 += fabsf(yI); sa1 += fabsf(yQ);
-    }
-    block_reduce3<256>(sa0, sa1, 0.f, red);
-    if (!q) return;
-    float amp[NLEV], amp2[NLEV];
-#pragma unroll
-    for (int i = 0; i < NLEV; i++) { amp[i] = amp_g[i]; amp2[i] = 0.f; }
-    const float A = amp_mean[run], ivar = 1.0f / var[run];
-    const float s0 = A / (red[0] / (float)N), s1 = A / (red[1] / (float)N);
-    for (int64_t it = tid; it < 2 * N; it += 256) {      // each thread re-reads only the y it wrote? no: any -> fence below
-        const int c = it >= N;
-        const int64_t n = it - (c ? N : 0);
-        float qq[NLEV];
-        // soft_demap computes -(d^2 * i2v + nusc*a^2): i2v = 1/var, nusc = 0 gives (yhat-a)^2/var (:229)
-        soft_demap<NLEV>((c ? y1[n] : y0[n]) * (c ? s1 : s0), amp, amp2, ivar, 0.f, qq);
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) q[((size_t)run * 2 * NLEV + c * NLEV + i) * N + n] = qq[i];
-    }
-}
-
-
 // Fused validation pass of one epoch (func_VAELE_MQAM_shaping.py:308-318) for all runs, one workgroup per run:
 //   twoFIR.forward in eval mode on N symbols (:311-313)  -> y (workspace; also the un-normalised output), mean |y| per axis
 //   hard decisions = argmax_i q_i = nearest level of yhat (q itself is never materialised: 16 floats per symbol saved)
@@ -547,296 +501,41 @@ __global__ __launch_bounds__(256, 4) void awgn_validate_kernel(int N, int sps, i
     validate_tail<256, NLEV>(N, n_shift, decs, E, NE, data + (size_t)run * 2 * N, red, corr, &sh_s, ser_out + run, shift_out ? shift_out + run : nullptr);
 }
 
-template <int NLEV, bool GEN = false>
-static int launch_validate(int R, int N, int sps, int M, int n_shift, const float *x, const float *W, const float *amp, const float *amp_mean,
-                           const float *var, const __half *data, float *yws, float *ser, int *shift, hipStream_t st, const ValGen &vg = ValGen{})
+template <bool GEN>
+static int launch_validate(int n_lev, int R, int N, int sps, int M, int n_shift, const float *x, const float *W, const float *amp,
+                           const float *amp_mean, const float *var, const __half *data, float *yws, float *ser, int *shift, hipStream_t st,
+                           const ValGen &vg = ValGen{})
 {
     const size_t lds = ((size_t)N + 15) & ~(size_t)15;
-#define VAEQ_VAL(MM)                                                                                                         \
-    {                                                                                                                        \
-        auto k = awgn_validate_kernel<NLEV, MM, GEN && (MM > 0)>;                                                            \
-        if (lds > 32 * 1024 &&                                                                                               \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return VAEQ_ERR_LDS;                                                                                             \
-        hipLaunchKernelGGL(k, dim3(R), dim3(256), lds, st, N, sps, M, n_shift, x, W, amp, amp_mean, var, data, yws, ser, shift, vg); \
-    }
-    if (sps == 2 && M == 25) VAEQ_VAL(25)
-    else if (sps == 2 && M == 17) VAEQ_VAL(17)
-    else if (sps == 2 && M == 9) VAEQ_VAL(9)
-    else if (GEN) return VAEQ_ERR_SHAPE;                       // the noise-on-load form exists for the baked tap counts only
-    else VAEQ_VAL(0)
-#undef VAEQ_VAL
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
-}
-
-
-// Stand-alone ELBO of the single-polarisation variants for a given q (values only):
-//   func_VAELE_MQAM_shaping.loss_function (:63-95):  nm log C + sum q log(q / P + 1e-12)      (P != nullptr)
-//   func_VAENN_MQAM.loss_function (:63-95):          nm log C + sum q log(q + 1e-12)          (P == nullptr)
-// One workgroup per run; q[R][2n][B], x[R][2][B*sps], h[R][2][M] -> loss[R].
-template <int NLEV>
-__global__ __launch_bounds__(256) void awgn_loss_kernel(int B, int sps, int M, const float *__restrict__ q, const float *__restrict__ x,
-                                                        const float *__restrict__ h, const float *__restrict__ amp_g, const float *__restrict__ P,
-                                                        float *__restrict__ loss)
-{
-    extern __shared__ float4 smem4[];
-    float *sm = reinterpret_cast<float *>(smem4);
-    __shared__ float red[64];
-    __shared__ float hs[2 * 64], VS[64];
-    const int run = blockIdx.x, tid = threadIdx.x;
-    const int L = B * sps, mh = M / 2, Mh = 2 * mh, nm = L - Mh;
-    float *mu = sm, *vr = sm + 2 * B;
-    float amp[NLEV], invP[NLEV];
-#pragma unroll
-    for (int i = 0; i < NLEV; i++) { amp[i] = amp_g[i]; invP[i] = P ? 1.0f / P[(size_t)run * NLEV + i] : 1.0f; }
-    for (int i = tid; i < 2 * M; i += 256) hs[i] = h[(size_t)run * 2 * M + i];
-    const float *qr = q + (size_t)run * 2 * NLEV * B, *x0 = x + (size_t)run * 2 * L, *x1 = x0 + L;
-    float klsum = 0.f;
-    for (int it = tid; it < 2 * B; it += 256) {
-        const int c = it / B, n = it - c * B;
-        const bool inr = (n >= mh) && (n < B - mh);
-        float qq[NLEV], e1 = 0.f, e2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) { qq[i] = qr[(size_t)(c * NLEV + i) * B + n]; e1 = fmaf(amp[i], qq[i], e1); }
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) {
-            const float d = amp[i] - e1;
-            e2 = fmaf(qq[i] * d, d, e2);
-            if (inr) klsum = fmaf(qq[i], __logf(qq[i] * invP[i] + 1e-12f), klsum);
-        }
-        mu[it] = e1; vr[it] = e2;
-    }
-    __syncthreads();
-    float se = 0.f;
-    for (int t = tid; t < nm; t += 256) {
-        float dr = 0.f, di = 0.f;
-        for (int j = (t + Mh) % sps; j <= Mh; j += sps) {
-            const int np = (t + Mh - j) / sps;
-            const float a_ = mu[np], b_ = mu[B + np], c_ = hs[j], d_ = hs[M + j];
-            dr = fmaf(c_, a_, dr); dr = fmaf(-d_, b_, dr);
-            di = fmaf(c_, b_, di); di = fmaf(d_, a_, di);
-        }
-        const float er = x0[mh + t] - dr, ei = x1[mh + t] - di;
-        se += er * er + ei * ei;
-    }
-    for (int j = tid; j < M; j += 256) {
-        const int lo = (Mh - j + sps - 1) / sps, hi_ = (nm - 1 + Mh - j) / sps;
-        float acc = 0.f;
-        for (int np = lo; np <= hi_; np++) acc += vr[np] + vr[B + np];
-        VS[j] = acc;
-    }
-    block_reduce3<256>(se, klsum, 0.f, red);
-    if (tid == 0) {
-        float C = red[0];
-        for (int j = 0; j < M; j++) C = fmaf(hs[j] * hs[j] + hs[M + j] * hs[M + j], VS[j], C);
-        loss[run] = (float)nm * logf(C) + red[1];
-    }
-}
-
-
-// Backward of the stand-alone AWGN ELBO (for the autograd wrappers; the fused training kernels do not use it):
-// g_up[R] = upstream d/dloss -> gq[R][2n][B] = dL/dq, gh[R][2][M] = dL/dh.  P == nullptr: the VAE-NN form (entropy).
-template <int NLEV>
-__global__ __launch_bounds__(256) void awgn_loss_bwd_kernel(int B, int sps, int M, const float *__restrict__ q, const float *__restrict__ x,
-                                                            const float *__restrict__ h, const float *__restrict__ amp_g,
-                                                            const float *__restrict__ P, const float *__restrict__ g_up, float *__restrict__ gq,
-                                                            float *__restrict__ gh)
-{
-    extern __shared__ float4 smem4[];
-    float *sm = reinterpret_cast<float *>(smem4);
-    __shared__ float red[64];
-    __shared__ float hs[2 * 64], VS[64];
-    const int run = blockIdx.x, tid = threadIdx.x;
-    const int L = B * sps, mh = M / 2, Mh = 2 * mh, nm = L - Mh;
-    float *mu = sm, *vr = sm + 2 * B, *es = sm + 4 * B;       // es[2][nm]
-    float amp[NLEV], invP[NLEV];
-#pragma unroll
-    for (int i = 0; i < NLEV; i++) { amp[i] = amp_g[i]; invP[i] = P ? 1.0f / P[(size_t)run * NLEV + i] : 1.0f; }
-    for (int i = tid; i < 2 * M; i += 256) hs[i] = h[(size_t)run * 2 * M + i];
-    const float *qr = q + (size_t)run * 2 * NLEV * B, *x0 = x + (size_t)run * 2 * L, *x1 = x0 + L;
-    for (int it = tid; it < 2 * B; it += 256) {
-        const int c = it / B, n = it - c * B;
-        float e1 = 0.f, e2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) e1 = fmaf(amp[i], qr[(size_t)(c * NLEV + i) * B + n], e1);
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) { const float d = amp[i] - e1; e2 = fmaf(qr[(size_t)(c * NLEV + i) * B + n] * d, d, e2); }
-        mu[it] = e1; vr[it] = e2;
-    }
-    __syncthreads();
-    float se = 0.f;
-    for (int t = tid; t < nm; t += 256) {
-        float dr = 0.f, di = 0.f;
-        for (int j = (t + Mh) % sps; j <= Mh; j += sps) {
-            const int np = (t + Mh - j) / sps;
-            const float a_ = mu[np], b_ = mu[B + np], c_ = hs[j], d_ = hs[M + j];
-            dr = fmaf(c_, a_, dr); dr = fmaf(-d_, b_, dr);
-            di = fmaf(c_, b_, di); di = fmaf(d_, a_, di);
-        }
-        const float er = x0[mh + t] - dr, ei = x1[mh + t] - di;
-        es[t] = er; es[nm + t] = ei;
-        se += er * er + ei * ei;
-    }
-    for (int j = tid; j < M; j += 256) {
-        const int lo = (Mh - j + sps - 1) / sps, hi_ = (nm - 1 + Mh - j) / sps;
-        float acc = 0.f;
-        for (int np = lo; np <= hi_; np++) acc += vr[np] + vr[B + np];
-        VS[j] = acc;
-    }
-    block_reduce3<256>(se, 0.f, 0.f, red);
-    float C = red[0];
-    for (int j = 0; j < M; j++) C = fmaf(hs[j] * hs[j] + hs[M + j] * hs[M + j], VS[j], C);
-    const float up = g_up[run], gC = up * (float)nm / C;
-    for (int j = tid; j < M; j += 256) {
-        const int lo = (Mh - j + sps - 1) / sps, hi_ = (nm - 1 + Mh - j) / sps;
-        float ar = 0.f, ai = 0.f;
-        for (int np = lo; np <= hi_; np++) {
-            const int t = np * sps - Mh + j;
-            const float a_ = es[t], b_ = es[nm + t], c_ = mu[np], d_ = mu[B + np];
-            ar = fmaf(a_, c_, ar); ar = fmaf(b_, d_, ar);
-            ai = fmaf(b_, c_, ai); ai = fmaf(-a_, d_, ai);
-        }
-        gh[(size_t)run * 2 * M + j] = gC * (-2.0f * ar + 2.0f * hs[j] * VS[j]);
-        gh[(size_t)run * 2 * M + M + j] = gC * (-2.0f * ai + 2.0f * hs[M + j] * VS[j]);
-    }
-    float *gqr = gq + (size_t)run * 2 * NLEV * B;
-    for (int n = tid; n < B; n += 256) {
-        const int sx = n * sps;
-        const int jlo = max(0, Mh - sx), jhi = min(Mh, nm - 1 + Mh - sx);
-        const float *er = es + (sx - Mh), *ei = er + nm;
-        float pr = 0.f, pi = 0.f, ph = 0.f;
-        for (int j = jlo; j <= jhi; j++) {
-            const float a_ = er[j], b_ = ei[j], c_ = hs[j], d_ = hs[M + j];
-            pr = fmaf(a_, c_, pr); pr = fmaf(b_, d_, pr);
-            pi = fmaf(b_, c_, pi); pi = fmaf(-a_, d_, pi);
-            ph = fmaf(c_, c_, ph); ph = fmaf(d_, d_, ph);
-        }
-        const float gv = gC * ph;
-        const bool inr = (n >= mh) && (n < B - mh);
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const float gmu = -2.0f * gC * (c ? pi : pr) - 2.0f * mu[c * B + n] * gv;
-#pragma unroll
-            for (int i = 0; i < NLEV; i++) {
-                const float qq = qr[(size_t)(c * NLEV + i) * B + n];
-                float g = amp[i] * gmu + amp[i] * amp[i] * gv;
-                if (inr) { const float r = qq * invP[i], re = r + 1e-12f; g += up * (__logf(re) + r / re); }
-                gqr[(size_t)(c * NLEV + i) * B + n] = g;
-            }
-        }
-    }
-}
-
-// Backward of twoFIR.forward (func_VAELE_MQAM_shaping.py:214-231): upstream gq[R][2n][N] (and optionally gy on the un-normalised
-// output) -> gW[R][2][M].  Recomputes the forward (y, mean |y|, yhat, q), then softmax backward with dz_i/dyhat = -2 (yhat - a_i) / var,
-// the normalisation's Jacobian and the tap correlation.  One workgroup per run, y and dL/dy in LDS.
-template <int NLEV>
-__global__ __launch_bounds__(256) void awgn_forward_bwd_kernel(int N, int sps, int M, const float *__restrict__ x, const float *__restrict__ W,
-                                                               const float *__restrict__ amp_g, const float *__restrict__ amp_mean,
-                                                               const float *__restrict__ var, const float *__restrict__ gq,
-                                                               const float *__restrict__ gy_up, float *__restrict__ gW)
-{
-    extern __shared__ float4 smem4[];
-    float *ys = reinterpret_cast<float *>(smem4), *gys = ys + 2 * N;
-    __shared__ float Ws[2 * 64];
-    __shared__ float red[64];
-    const int run = blockIdx.x, tid = threadIdx.x;
-    for (int i = tid; i < 2 * M; i += 256) Ws[i] = W[(size_t)run * 2 * M + i];
-    __syncthreads();
-    const int L = N * sps, pad = (M - 1) / 2;
-    const float *x0 = x + (size_t)run * 2 * L, *x1 = x0 + L;
-    float sa0 = 0.f, sa1 = 0.f;
-    for (int n = tid; n < N; n += 256) {
-        float yI = 0.f, yQ = 0.f;
-        for (int k = 0; k < M; k++) {
-            const int sx = n * sps + k - pad;
-            if (sx < 0 || sx >= L) continue;
-            const float a_ = x0[sx], b_ = x1[sx];
-            yI = fmaf(Ws[k], a_, yI); yI = fmaf(Ws[M + k], b_, yI);
-            yQ = fmaf(Ws[k], b_, yQ); yQ = fmaf(-Ws[M + k], a_, yQ);
-        }
-        ys[n] = yI; ys[N + n] = yQ;
-        sa0 += fabsf(yI); sa1 += fabsf(yQ);
-    }
-    block_reduce3<256>(sa0, sa1, 0.f, red);
-    float amp[NLEV];
-#pragma unroll
-    for (int i = 0; i < NLEV; i++) amp[i] = amp_g[i];
-    const float A = amp_mean[run], ivar = 1.0f / var[run];
-    const float m0 = red[0] / (float)N, m1 = red[1] / (float)N;
-    __syncthreads();
-    const float *gqr = gq + (size_t)run * 2 * NLEV * N;
-    float dt0 = 0.f, dt1 = 0.f;
-    for (int it = tid; it < 2 * N; it += 256) {
-        const int c = it / N, n = it - c * N;
-        const float yh = ys[it] / (c ? m1 : m0) * A;
-        float z[NLEV], zmax = -3.0e38f, ssum = 0.f, dot = 0.f, g = 0.f;
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) { const float d = yh - amp[i]; z[i] = -(d * d * ivar); zmax = fmaxf(zmax, z[i]); }
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) { z[i] = __expf(z[i] - zmax); ssum += z[i]; }
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) { z[i] /= ssum; dot = fmaf(z[i], gqr[(size_t)(c * NLEV + i) * N + n], dot); }
-#pragma unroll
-        for (int i = 0; i < NLEV; i++) g = fmaf(z[i] * (gqr[(size_t)(c * NLEV + i) * N + n] - dot), -2.0f * (yh - amp[i]) * ivar, g);
-        gys[it] = g;                                           // dL/dyhat
-        if (c) dt1 = fmaf(g, ys[it], dt1); else dt0 = fmaf(g, ys[it], dt0);
-    }
-    block_reduce3<256>(dt0, dt1, 0.f, red);
-    {
-        const float s0_ = A / m0, s1_ = A / m1, k0_ = red[0] * A / (m0 * m0) / (float)N, k1_ = red[1] * A / (m1 * m1) / (float)N;
-        __syncthreads();
-        for (int n = tid; n < N; n += 256) {                   // normalisation backward (:228) + the upstream gradient on `out`
-            const float yI = ys[n], yQ = ys[N + n];
-            const float sgI = (float)(yI > 0.f) - (float)(yI < 0.f), sgQ = (float)(yQ > 0.f) - (float)(yQ < 0.f);
-            gys[n] = gys[n] * s0_ - k0_ * sgI + (gy_up ? gy_up[(size_t)run * 2 * N + n] : 0.f);
-            gys[N + n] = gys[N + n] * s1_ - k1_ * sgQ + (gy_up ? gy_up[(size_t)run * 2 * N + N + n] : 0.f);
-        }
-    }
-    __syncthreads();
-    for (int k = tid; k < M; k += 256) {                       // dL/dW0[k] = sum gI x0 + gQ x1, dL/dW1[k] = sum gI x1 - gQ x0
-        float g0 = 0.f, g1 = 0.f;
-        for (int n = 0; n < N; n++) {
-            const int sx = n * sps + k - pad;
-            if (sx < 0 || sx >= L) continue;
-            const float a_ = gys[n], b_ = gys[N + n], c_ = x0[sx], d_ = x1[sx];
-            g0 = fmaf(a_, c_, g0); g0 = fmaf(b_, d_, g0);
-            g1 = fmaf(a_, d_, g1); g1 = fmaf(-b_, c_, g1);
-        }
-        gW[(size_t)run * 2 * M + k] = g0;
-        gW[(size_t)run * 2 * M + M + k] = g1;
-    }
-}
-
-template <int NT, int NLEV>
-static int launch_awgn(const vaeq_awgn_args &a, size_t lds, hipStream_t st)
-{
-    auto k = awgn_train_kernel<NT, NLEV>;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
-    note_kernel("vaeq::awgn_train_kernel<%d, %d>", NT, NLEV);
-    hipLaunchKernelGGL(k, dim3(a.R), dim3(NT), lds, st, a);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return dispatch_nlev(n_lev, [&](auto nl) {
+        auto go = [&](auto mm) {                               // mm: the baked tap count (0: run time)
+            constexpr int NLEV = decltype(nl)::value, MM = decltype(mm)::value;
+            return launch(awgn_validate_kernel<NLEV, MM, GEN && (MM > 0)>, dim3(R), dim3(256), lds, st, N, sps, M, n_shift, x, W, amp, amp_mean, var,
+                          data, yws, ser, shift, vg);
+        };
+        if (sps == 2 && M == 25) return go(std::integral_constant<int, 25>{});
+        if (sps == 2 && M == 17) return go(std::integral_constant<int, 17>{});
+        if (sps == 2 && M == 9) return go(std::integral_constant<int, 9>{});
+        if (GEN) return (int)VAEQ_ERR_SHAPE;                   // the noise-on-load form exists for the baked tap counts only
+        return go(std::integral_constant<int, 0>{});
+    });
 }
 
 template <int NT>
-static int launch_awgn_lev(const vaeq_awgn_args &a, size_t lds, hipStream_t st)
+static int launch_awgn(const vaeq_awgn_args &a, size_t lds, hipStream_t st)
 {
-    switch (a.n_lev) {
-    case 2: return launch_awgn<NT, 2>(a, lds, st);
-    case 4: return launch_awgn<NT, 4>(a, lds, st);
-    case 8: return launch_awgn<NT, 8>(a, lds, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(a.n_lev, [&](auto nl) {
+        constexpr int NLEV = decltype(nl)::value;
+        note_kernel("vaeq::awgn_train_kernel<%d, %d>", NT, NLEV);
+        return launch(awgn_train_kernel<NT, NLEV>, dim3(a.R), dim3(NT), lds, st, a);
+    });
 }
 
 }  // namespace vaeq
 
 extern "C" int64_t vaeq_awgn_lds_bytes(int32_t B, int32_t sps, int32_t M, int32_t n_lev)
 {
-    if (B <= 0 || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63 || !(n_lev == 2 || n_lev == 4 || n_lev == 8)) return VAEQ_ERR_SHAPE;
-    if ((int64_t)B * sps - 2 * (M / 2) <= 0 || B <= 2 * (M / 2)) return VAEQ_ERR_SHAPE;
+    if (!vaeq::loss_shape_ok(B, sps, M) || !(n_lev == 2 || n_lev == 4 || n_lev == 8)) return VAEQ_ERR_SHAPE;
     return (int64_t)vaeq::awgn_layout(B, sps, M).total * 4;
 }
 
@@ -850,37 +549,19 @@ extern "C" int vaeq_awgn_train(const vaeq_awgn_args *pa, void *stream)
         return VAEQ_ERR_NULL;
     const int64_t lds = vaeq_awgn_lds_bytes(a.B, a.sps, a.M, a.n_lev);
     if (lds < 0) return (int)lds;
-    if (lds > 160 * 1024) return VAEQ_ERR_LDS;
+    if (lds > (int64_t)vaeq::LDS_MAX) return VAEQ_ERR_LDS;
     if (a.R < 0 || a.steps <= 0) return VAEQ_ERR_SHAPE;
     if ((int64_t)a.steps * a.B * a.sps > a.S) return VAEQ_ERR_SHAPE;
-    if (a.R == 0) return VAEQ_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (a.threads == 1 && !vaeq::awgn_wave_supported(a)) return VAEQ_ERR_SHAPE;
     if ((a.threads == 0 || a.threads == 1) && vaeq::awgn_wave_supported(a)) return vaeq::launch_awgn_wave(a, st);
     switch (a.threads) {
     case 0:
-    case 256: return vaeq::launch_awgn_lev<256>(a, (size_t)lds, st);
-    case 128: return vaeq::launch_awgn_lev<128>(a, (size_t)lds, st);
-    case 64: return vaeq::launch_awgn_lev<64>(a, (size_t)lds, st);
+    case 256: return vaeq::launch_awgn<256>(a, (size_t)lds, st);
+    case 128: return vaeq::launch_awgn<128>(a, (size_t)lds, st);
+    case 64: return vaeq::launch_awgn<64>(a, (size_t)lds, st);
     }
     return VAEQ_ERR_SHAPE;
-}
-
-extern "C" int vaeq_awgn_forward(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, const float *x, const float *W,
-                                 const float *amp, const float *amp_mean, const float *var, float *q, float *y, void *stream)
-{
-    if (R == 0 || N == 0) return VAEQ_OK;                      // an empty batch owns no memory: its pointers may be NULL
-    if (!x || !W || !amp || !amp_mean || !var || !y) return VAEQ_ERR_NULL;
-    if (R < 0 || N < 0 || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63) return VAEQ_ERR_SHAPE;
-    if (R == 0 || N == 0) return VAEQ_OK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (n_lev) {
-    case 2: hipLaunchKernelGGL(vaeq::awgn_forward_kernel<2>, dim3(R), dim3(256), 0, st, N, sps, M, x, W, amp, amp_mean, var, q, y); break;
-    case 4: hipLaunchKernelGGL(vaeq::awgn_forward_kernel<4>, dim3(R), dim3(256), 0, st, N, sps, M, x, W, amp, amp_mean, var, q, y); break;
-    case 8: hipLaunchKernelGGL(vaeq::awgn_forward_kernel<8>, dim3(R), dim3(256), 0, st, N, sps, M, x, W, amp, amp_mean, var, q, y); break;
-    default: return VAEQ_ERR_SHAPE;
-    }
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
 }
 
 extern "C" int vaeq_awgn_validate(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t n_shift, const float *x, const float *W,
@@ -889,16 +570,11 @@ extern "C" int vaeq_awgn_validate(int32_t R, int64_t N, int32_t sps, int32_t M, 
 {
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!x || !W || !amp || !amp_mean || !var || !data_f16 || !y_ws || !ser) return VAEQ_ERR_NULL;
-    if (R < 0 || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63 || n_shift <= 0 || n_shift > vaeq::VAL_MAXSHIFT) return VAEQ_ERR_SHAPE;
+    if (R < 0 || !vaeq::fir_shape_ok(sps, M) || n_shift <= 0 || n_shift > vaeq::VAL_MAXSHIFT) return VAEQ_ERR_SHAPE;
     if (N < 64 || N > 65536) return VAEQ_ERR_SHAPE;           // decisions live in LDS (N bytes); 22 + n_shift symbols are trimmed
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *d = reinterpret_cast<const __half *>(data_f16);
-    switch (n_lev) {
-    case 2: return vaeq::launch_validate<2>(R, (int)N, sps, M, n_shift, x, W, amp, amp_mean, var, d, y_ws, ser, shift, st);
-    case 4: return vaeq::launch_validate<4>(R, (int)N, sps, M, n_shift, x, W, amp, amp_mean, var, d, y_ws, ser, shift, st);
-    case 8: return vaeq::launch_validate<8>(R, (int)N, sps, M, n_shift, x, W, amp, amp_mean, var, d, y_ws, ser, shift, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return vaeq::launch_validate<false>(n_lev, R, (int)N, sps, M, n_shift, x, W, amp, amp_mean, var, d, y_ws, ser, shift, st);
 }
 
 // vaeq_awgn_validate on x = clean frame + noise made while staging (include/vaeq.h)
@@ -914,91 +590,5 @@ extern "C" int vaeq_awgn_validate_gen(int32_t R, int64_t N, int32_t sps, int32_t
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *d = reinterpret_cast<const __half *>(data_f16);
     vaeq::ValGen vg{reinterpret_cast<const float2 *>(sig), power_ws, snr_db, sigma_fixed, sigma_out, seed, frame, Ls, (Ls + 2047) / 2048};
-    switch (n_lev) {
-    case 2: return vaeq::launch_validate<2, true>(R, (int)N, sps, M, n_shift, nullptr, W, amp, amp_mean, var, d, y_ws, ser, shift, st, vg);
-    case 4: return vaeq::launch_validate<4, true>(R, (int)N, sps, M, n_shift, nullptr, W, amp, amp_mean, var, d, y_ws, ser, shift, st, vg);
-    case 8: return vaeq::launch_validate<8, true>(R, (int)N, sps, M, n_shift, nullptr, W, amp, amp_mean, var, d, y_ws, ser, shift, st, vg);
-    }
-    return VAEQ_ERR_SHAPE;
-}
-
-extern "C" int vaeq_awgn_loss(int32_t R, int32_t B, int32_t sps, int32_t M, int32_t n_lev, const float *q, const float *x, const float *h,
-                              const float *amp, const float *P, float *loss, void *stream)
-{
-    if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
-    if (!q || !x || !h || !amp || !loss) return VAEQ_ERR_NULL;
-    if (R < 0 || B <= 0 || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63 || (int64_t)B * sps - 2 * (M / 2) <= 0 || B <= 2 * (M / 2)) return VAEQ_ERR_SHAPE;
-    const size_t lds = (size_t)4 * B * sizeof(float);
-    if (lds > 150 * 1024) return VAEQ_ERR_LDS;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define VAEQ_AL(NL)                                                                                                                     \
-    {                                                                                                                                   \
-        auto k = vaeq::awgn_loss_kernel<NL>;                                                                                            \
-        if (lds > 32 * 1024 &&                                                                                                          \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)  \
-            return VAEQ_ERR_LDS;                                                                                                        \
-        hipLaunchKernelGGL(k, dim3(R), dim3(256), lds, st, B, sps, M, q, x, h, amp, P, loss);                                           \
-    }
-    switch (n_lev) {
-    case 2: VAEQ_AL(2) break;
-    case 4: VAEQ_AL(4) break;
-    case 8: VAEQ_AL(8) break;
-    default: return VAEQ_ERR_SHAPE;
-    }
-#undef VAEQ_AL
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
-}
-
-extern "C" int vaeq_awgn_loss_bwd(int32_t R, int32_t B, int32_t sps, int32_t M, int32_t n_lev, const float *q, const float *x, const float *h,
-                                  const float *amp, const float *P, const float *g_up, float *gq, float *gh, void *stream)
-{
-    if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
-    if (!q || !x || !h || !amp || !g_up || !gq || !gh) return VAEQ_ERR_NULL;
-    if (R < 0 || B <= 0 || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63 || (int64_t)B * sps - 2 * (M / 2) <= 0 || B <= 2 * (M / 2)) return VAEQ_ERR_SHAPE;
-    const size_t lds = ((size_t)4 * B + 2 * ((size_t)B * sps - 2 * (M / 2))) * sizeof(float);
-    if (lds > 150 * 1024) return VAEQ_ERR_LDS;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define VAEQ_ALB(NL)                                                                                                                    \
-    {                                                                                                                                   \
-        auto k = vaeq::awgn_loss_bwd_kernel<NL>;                                                                                        \
-        if (lds > 32 * 1024 &&                                                                                                          \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)  \
-            return VAEQ_ERR_LDS;                                                                                                        \
-        hipLaunchKernelGGL(k, dim3(R), dim3(256), lds, st, B, sps, M, q, x, h, amp, P, g_up, gq, gh);                                   \
-    }
-    switch (n_lev) {
-    case 2: VAEQ_ALB(2) break;
-    case 4: VAEQ_ALB(4) break;
-    case 8: VAEQ_ALB(8) break;
-    default: return VAEQ_ERR_SHAPE;
-    }
-#undef VAEQ_ALB
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
-}
-
-extern "C" int vaeq_awgn_forward_bwd(int32_t R, int32_t N, int32_t sps, int32_t M, int32_t n_lev, const float *x, const float *W, const float *amp,
-                                     const float *amp_mean, const float *var, const float *gq, const float *gy, float *gW, void *stream)
-{
-    if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
-    if (!x || !W || !amp || !amp_mean || !var || !gq || !gW) return VAEQ_ERR_NULL;
-    if (R < 0 || N <= 0 || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63) return VAEQ_ERR_SHAPE;
-    const size_t lds = (size_t)4 * N * sizeof(float);
-    if (lds > 150 * 1024) return VAEQ_ERR_LDS;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define VAEQ_AFB(NL)                                                                                                                    \
-    {                                                                                                                                   \
-        auto k = vaeq::awgn_forward_bwd_kernel<NL>;                                                                                     \
-        if (lds > 32 * 1024 &&                                                                                                          \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)  \
-            return VAEQ_ERR_LDS;                                                                                                        \
-        hipLaunchKernelGGL(k, dim3(R), dim3(256), lds, st, N, sps, M, x, W, amp, amp_mean, var, gq, gy, gW);                            \
-    }
-    switch (n_lev) {
-    case 2: VAEQ_AFB(2) break;
-    case 4: VAEQ_AFB(4) break;
-    case 8: VAEQ_AFB(8) break;
-    default: return VAEQ_ERR_SHAPE;
-    }
-#undef VAEQ_AFB
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::launch_validate<true>(n_lev, R, (int)N, sps, M, n_shift, nullptr, W, amp, amp_mean, var, d, y_ws, ser, shift, st, vg);
 }

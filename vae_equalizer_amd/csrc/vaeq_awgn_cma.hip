@@ -21,6 +21,7 @@
 #include "vaeq.h"
 #include "vaeq_awgn_eval.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 #include "vaeq_wave.h"
 
 #ifndef AWGN_CMA_AHEAD
@@ -249,19 +250,17 @@ __global__ __launch_bounds__(AV_NT) void awgn_cma_validate_kernel(int N, int sps
 extern "C" int vaeq_awgn_cma(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t update, const float *rx, float R_mod, float *h,
                              const float *lr, float *loss, float *out, float *e, void *stream)
 {
-    if (R < 0 || N <= 0 || N > 0x3fffffff || sps < 1 || sps > 8 || N % sps != 0 || M <= 0 || (M & 1) == 0 || M > 63 || N / sps < M)
+    if (R < 0 || N <= 0 || N > 0x3fffffff || sps < 1 || sps > 8 || N % sps != 0 || !vaeq::fir_shape_ok(sps, M) || N / sps < M)
         return VAEQ_ERR_SHAPE;
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!rx || !h || !lr || !loss) return VAEQ_ERR_NULL;
     auto k = M <= 31 ? vaeq::awgn_cma_kernel<true> : vaeq::awgn_cma_kernel<false>;
-    hipLaunchKernelGGL(k, dim3(R), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), (int)N, sps, M, update ? 1 : 0, rx, R_mod, h, lr, loss,
-                       out, e);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::launch(k, dim3(R), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), (int)N, sps, M, update ? 1 : 0, rx, R_mod, h, lr, loss, out, e);
 }
 
 static bool awgn_cma_validate_shape(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t n_shift)
 {
-    return R >= 0 && N > 0 && N <= 0x3fffffff && sps >= 1 && sps <= 8 && N % sps == 0 && M > 0 && (M & 1) == 1 && M <= 63 &&
+    return R >= 0 && N > 0 && N <= 0x3fffffff && sps >= 1 && sps <= 8 && N % sps == 0 && vaeq::fir_shape_ok(sps, M) &&
            (n_lev == 2 || n_lev == 4 || n_lev == 8) && n_shift >= 1 && (n_shift & 1) == 1 && n_shift <= 23 && N / sps >= 1000 + n_shift;
 }
 
@@ -284,16 +283,9 @@ extern "C" int vaeq_awgn_cma_validate(int32_t R, int64_t N, int32_t sps, int32_t
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *d = reinterpret_cast<const __half *>(data_f16);
     float2 *w = reinterpret_cast<float2 *>(ws);
-    if (lds) {
-        const size_t bytes = (size_t)K * sizeof(float2);
-        auto k = vaeq::awgn_cma_validate_kernel<true>;
-        if (bytes > 32 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-            return VAEQ_ERR_LDS;
-        hipLaunchKernelGGL(k, dim3(R), dim3(vaeq::AV_NT), bytes, st, (int)N, sps, M, n_lev, n_shift, rx, h, amp, d, w, ser, shift, cpe_out);
-    } else {
-        hipLaunchKernelGGL(vaeq::awgn_cma_validate_kernel<false>, dim3(R), dim3(vaeq::AV_NT), 0, st, (int)N, sps, M, n_lev, n_shift, rx, h, amp,
-                           d, w, ser, shift, cpe_out);
-    }
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    if (lds)
+        return vaeq::launch(vaeq::awgn_cma_validate_kernel<true>, dim3(R), dim3(vaeq::AV_NT), (size_t)K * sizeof(float2), st, (int)N, sps, M, n_lev, n_shift,
+                            rx, h, amp, d, w, ser, shift, cpe_out);
+    return vaeq::launch(vaeq::awgn_cma_validate_kernel<false>, dim3(R), dim3(vaeq::AV_NT), 0, st, (int)N, sps, M, n_lev, n_shift, rx, h, amp, d, w, ser, shift,
+                        cpe_out);
 }

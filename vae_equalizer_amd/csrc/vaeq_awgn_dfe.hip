@@ -24,6 +24,7 @@
 #include "vaeq.h"
 #include "vaeq_awgn_eval.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 
 namespace vaeq {
 
@@ -367,9 +368,8 @@ extern "C" int vaeq_awgn_lmmse_eval(int32_t R, int64_t N, int32_t sps, int32_t n
     if (R == 0) return VAEQ_OK;
     if (!rx || !taps || !amp || !data_f16 || !ser || (!out && !ws)) return VAEQ_ERR_NULL;
     float2 *track = reinterpret_cast<float2 *>(out ? out : ws);
-    hipLaunchKernelGGL(vaeq::lmmse_eval_kernel, dim3(R), dim3(vaeq::LE_NT), 0, reinterpret_cast<hipStream_t>(stream), (int)N, K, n_lev, n_shift,
-                       n_cut, rx, taps, amp, reinterpret_cast<const __half *>(data_f16), track, dec, ser, shift);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::launch(vaeq::lmmse_eval_kernel, dim3(R), dim3(vaeq::LE_NT), 0, reinterpret_cast<hipStream_t>(stream), (int)N, K, n_lev, n_shift,
+                        n_cut, rx, taps, amp, reinterpret_cast<const __half *>(data_f16), track, dec, ser, shift);
 }
 
 // Chunks of the speculative pass: CH = ceil((N - K2) / C) symbols, C reduced to the number of non-empty chunks.
@@ -402,16 +402,12 @@ extern "C" int vaeq_awgn_dfe(int32_t R, int64_t N, int32_t sps, int32_t n_lev, i
     int8_t *spec = reinterpret_cast<int8_t *>(ws) + (size_t)R * N * sizeof(float2);
     hipLaunchKernelGGL(vaeq::dfe_ff_kernel, dim3((unsigned)((N + 255) / 256), R), dim3(256), 0, st, (int)N, K1, rx, ff_taps, ff);
     const int n = (int)N;
-    if (n_lev == 2) {
-        if (K2 <= 4) vaeq::launch_dfe_recursion<2, 4>(st, R, n, K2, C, CH, W, ff, fb_taps, amp, init_dec, dec, spec, repairs);
-        else vaeq::launch_dfe_recursion<2, 10>(st, R, n, K2, C, CH, W, ff, fb_taps, amp, init_dec, dec, spec, repairs);
-    } else if (n_lev == 4) {
-        if (K2 <= 4) vaeq::launch_dfe_recursion<4, 4>(st, R, n, K2, C, CH, W, ff, fb_taps, amp, init_dec, dec, spec, repairs);
-        else vaeq::launch_dfe_recursion<4, 10>(st, R, n, K2, C, CH, W, ff, fb_taps, amp, init_dec, dec, spec, repairs);
-    } else {
-        if (K2 <= 4) vaeq::launch_dfe_recursion<8, 4>(st, R, n, K2, C, CH, W, ff, fb_taps, amp, init_dec, dec, spec, repairs);
-        else vaeq::launch_dfe_recursion<8, 10>(st, R, n, K2, C, CH, W, ff, fb_taps, amp, init_dec, dec, spec, repairs);
-    }
+    vaeq::dispatch_nlev(n_lev, [&](auto nl) {                  // (n_lev was checked above; a chain of launches reports its status once, below)
+        constexpr int NL = decltype(nl)::value;
+        if (K2 <= 4) vaeq::launch_dfe_recursion<NL, 4>(st, R, n, K2, C, CH, W, ff, fb_taps, amp, init_dec, dec, spec, repairs);
+        else vaeq::launch_dfe_recursion<NL, 10>(st, R, n, K2, C, CH, W, ff, fb_taps, amp, init_dec, dec, spec, repairs);
+        return (int)VAEQ_OK;
+    });
     if (ser)
         hipLaunchKernelGGL(vaeq::dfe_eval_kernel, dim3(R), dim3(vaeq::LE_NT), 0, st, n, n_lev, n_shift, n_cut, dec, amp,
                            reinterpret_cast<const __half *>(data_f16), ser, shift);

@@ -17,6 +17,7 @@
 
 #include "vaeq.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 #include "vaeq_wave.h"
 
 #ifndef VAEQ_AWGN_BAKED_FULL
@@ -153,16 +154,6 @@ template <int M, int NW, int BL = 0> struct TapBlocks {
         }
     }
 };
-
-__device__ __forceinline__ void amsgrad_fast(float &p, float &m, float &v, float &vmax, float g, float step_size, float rbc2s)
-{
-    m = fmaf(g - m, 0.1f, m);
-    v = v * 0.999f;
-    v = v + (0.001f * g) * g;
-    vmax = fmaxf(vmax, v);
-    const float denom = fmaf(__builtin_amdgcn_sqrtf(vmax), rbc2s, 1e-8f);
-    p = fmaf(-step_size * m, __builtin_amdgcn_rcpf(denom), p);
-}
 
 // NW = wavefronts per run (1: no barriers; 2..4 for B > 384, see vaeq_dp_wave_kernel.h): wave wv owns the pairs 64 NR wv + 64 r + lane.
 // BL > 0: the minibatch length baked into the kernel (LDS offsets immediate, trip counts constant)
@@ -551,8 +542,8 @@ __global__ __launch_bounds__(64 * NW, 2) void awgn_wave_kernel(const vaeq_awgn_a
                 gh0 = gC * (-2.0f * acc.x + 2.0f * p0 * vsl);
                 gh1 = gC * (-2.0f * acc.y + 2.0f * p1 * vsl);
                 if (!a.no_update) {
-                    amsgrad_fast(p0, am0, av0, ax0, gh0, ss, rbc2s);
-                    amsgrad_fast(p1, am1, av1, ax1, gh1, ss, rbc2s);
+                    adam_update_amsgrad_fast(p0, am0, av0, ax0, gh0, ss, rbc2s);
+                    adam_update_amsgrad_fast(p1, am1, av1, ax1, gh1, ss, rbc2s);
                 }
             }
         }
@@ -657,8 +648,8 @@ __global__ __launch_bounds__(64 * NW, 2) void awgn_wave_kernel(const vaeq_awgn_a
                 gw0 = acc.x;
                 gw1 = -acc.y;
                 if (!a.no_update) {
-                    amsgrad_fast(p0, am0, av0, ax0, gw0, ss, rbc2s);
-                    amsgrad_fast(p1, am1, av1, ax1, gw1, ss, rbc2s);
+                    adam_update_amsgrad_fast(p0, am0, av0, ax0, gw0, ss, rbc2s);
+                    adam_update_amsgrad_fast(p1, am1, av1, ax1, gw1, ss, rbc2s);
                     Wt[tk] = make_float2(p0, -p1);
                 }
             }
@@ -686,12 +677,8 @@ static int launch_awgn_wave_k(const vaeq_awgn_args &a, hipStream_t st)
 {
     const size_t lds = (size_t)awgn_wave_layout(a.B, M, NW).total;
     auto k = awgn_wave_kernel<M, NLEV, NR, NW, BL>;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
     note_kernel("vaeq::awgn_wave_kernel<%d, %d, %d, %d, %d>", M, NLEV, NR, NW, BL);   // every template argument, as rocprofv3 prints the name
-    hipLaunchKernelGGL(k, dim3(a.R), dim3(64 * NW), lds, st, a);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return launch(k, dim3(a.R), dim3(64 * NW), lds, st, a);
 }
 
 template <int M, int NLEV>
@@ -714,12 +701,7 @@ static int launch_awgn_wave_r(const vaeq_awgn_args &a, hipStream_t st)
 template <int M>
 static int launch_awgn_wave_lev(const vaeq_awgn_args &a, hipStream_t st)
 {
-    switch (a.n_lev) {
-    case 2: return launch_awgn_wave_r<M, 2>(a, st);
-    case 4: return launch_awgn_wave_r<M, 4>(a, st);
-    case 8: return launch_awgn_wave_r<M, 8>(a, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_awgn_wave_r<M, decltype(nl)::value>(a, st); });
 }
 
 // Whether the wave-per-run kernel covers this call (else the generic kernel runs).

@@ -14,6 +14,7 @@
 
 #include "vaeq.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 #include "vaeq_wave.h"
 
 #ifndef CMA_WAVES
@@ -333,7 +334,7 @@ extern "C" int vaeq_cma(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t mo
                         float R_mod, float *h, const float *lr, float *out, float *e, void *stream)
 {
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
-    if (R < 0 || N <= 0 || N > 0x1fffffff || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63 || N / sps < 2 * M) return VAEQ_ERR_SHAPE;   // (4 N fits an int)
+    if (R < 0 || N <= 0 || N > 0x1fffffff || !vaeq::fir_shape_ok(sps, M) || N / sps < 2 * M) return VAEQ_ERR_SHAPE;   // (4 N fits an int)
     if ((M / 2 + sps * ((N - 1) / sps)) / sps - M / 2 >= N / sps) return VAEQ_ERR_SHAPE;   // the last symbol's index past the end (M = 1, N % sps != 0): IndexError in the reference
     if (!(mode == 0 || mode == 1) || (mode == 1 && (batchlen <= 0 || symb_step <= 0 || batchlen > 4096))) return VAEQ_ERR_SHAPE;
     if (!rx || !h || !lr || !out) return VAEQ_ERR_NULL;        // (after the shape checks: a refused shape never reaches a pointer)
@@ -349,11 +350,8 @@ extern "C" int vaeq_cma(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t mo
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     void (*k)(int, int, int, int, int, int, int, const float *, float, float *, const float *, float *, float *) =
         M <= 32 ? (stage ? vaeq::cma_kernel<true, true> : vaeq::cma_kernel<true, false>) : (stage ? vaeq::cma_kernel<false, true> : vaeq::cma_kernel<false, false>);
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
     vaeq::note_kernel("vaeq::cma_kernel<%s, %s>", M <= 32 ? "true" : "false", stage ? "true" : "false");
-    hipLaunchKernelGGL(k, dim3(R), dim3(64), lds, st, (int)N, sps, M, mode, batchlen, symb_step, xcap - 1, rx, R_mod, h, lr, out, e);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::launch(k, dim3(R), dim3(64), lds, st, (int)N, sps, M, mode, batchlen, symb_step, xcap - 1, rx, R_mod, h, lr, out, e);
 }
 
 extern "C" int vaeq_cpe(int32_t R, int64_t N, int32_t M_ma, const float *y, float *y_out, void *stream)
@@ -362,11 +360,6 @@ extern "C" int vaeq_cpe(int32_t R, int64_t N, int32_t M_ma, const float *y, floa
     if (R < 0 || N < 0 || N > 12800 || M_ma <= 0 || (M_ma & 1) == 0) return VAEQ_ERR_SHAPE;   // three N-float tracks of one polarisation live in LDS
     if (!y || !y_out) return VAEQ_ERR_NULL;
     const size_t lds = (size_t)3 * N * sizeof(float);
-    auto k = vaeq::cpe_kernel;
-    if (lds > 32 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
     vaeq::note_kernel("vaeq::cpe_kernel");
-    hipLaunchKernelGGL(k, dim3(R), dim3(vaeq::CPE_NT), lds, reinterpret_cast<hipStream_t>(stream), (int)N, M_ma, y, y_out);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::launch(vaeq::cpe_kernel, dim3(R), dim3(vaeq::CPE_NT), lds, reinterpret_cast<hipStream_t>(stream), (int)N, M_ma, y, y_out);
 }

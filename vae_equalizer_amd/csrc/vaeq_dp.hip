@@ -30,6 +30,7 @@
 
 #include "vaeq.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 
 namespace vaeq {
 
@@ -42,8 +43,6 @@ struct DPLayout {
     int L, mh, Mh, nm, Lp;
     int xs, Ws, hs, mW, vW, mH, vH, gW, gH, mu, vr, t3, kc, gy, es, VS, red, total;  // float offsets
 };
-
-__host__ __device__ inline int pad4(int x) { return (x + 3) & ~3; }
 
 __host__ __device__ inline DPLayout dp_layout(int B, int sps, int M)
 {
@@ -401,35 +400,21 @@ __global__ __launch_bounds__(NT) void dp_train_kernel(const vaeq_dp_args a)
     if (tid == 0 && !a.no_update) a.step[run] = step;
 }
 
-template <int NT, int NLEV>
+template <int NT>
 static int launch_dp(const vaeq_dp_args &a, size_t lds, hipStream_t st)
 {
-    auto k = dp_train_kernel<NT, NLEV>;
-    if (lds > 48 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return VAEQ_ERR_LDS;
-    }
-    note_kernel("vaeq::dp_train_kernel<%d, %d>", NT, NLEV);
-    hipLaunchKernelGGL(k, dim3(a.R), dim3(NT), lds, st, a);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
-}
-
-template <int NT>
-static int launch_dp_lev(const vaeq_dp_args &a, size_t lds, hipStream_t st)
-{
-    switch (a.n_lev) {
-    case 2: return launch_dp<NT, 2>(a, lds, st);
-    case 4: return launch_dp<NT, 4>(a, lds, st);
-    case 8: return launch_dp<NT, 8>(a, lds, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(a.n_lev, [&](auto nl) {
+        constexpr int NLEV = decltype(nl)::value;
+        note_kernel("vaeq::dp_train_kernel<%d, %d>", NT, NLEV);
+        return launch(dp_train_kernel<NT, NLEV>, dim3(a.R), dim3(NT), lds, st, a);
+    });
 }
 
 }  // namespace vaeq
 
 extern "C" int64_t vaeq_dp_lds_bytes(int32_t B, int32_t sps, int32_t M, int32_t n_lev)
 {
-    if (B <= 0 || sps <= 0 || M <= 0 || (M & 1) == 0 || M > 63 || !(n_lev == 2 || n_lev == 4 || n_lev == 8)) return VAEQ_ERR_SHAPE;
+    if (B <= 0 || !vaeq::fir_shape_ok(sps, M) || !(n_lev == 2 || n_lev == 4 || n_lev == 8)) return VAEQ_ERR_SHAPE;
     if ((int64_t)B * sps - 2 * (M / 2) <= 0) return VAEQ_ERR_SHAPE;  // needs nm > 0 residual samples; the KL slice mh <= n < B - mh may be empty (B <= 2 mh:
                                                                      // the reference's short batch_len options, Eval_run_DP.py:38 -- torch sums an empty slice to 0, shared_funcs.py:131-132)
     return (int64_t)vaeq::dp_layout(B, sps, M).total * 4;
@@ -445,19 +430,18 @@ extern "C" int vaeq_dp_train(const vaeq_dp_args *pa, void *stream)
         return VAEQ_ERR_NULL;
     const int64_t lds = vaeq_dp_lds_bytes(a.B, a.sps, a.M, a.n_lev);
     if (lds < 0) return (int)lds;
-    if (lds > 160 * 1024) return VAEQ_ERR_LDS;
+    if (lds > (int64_t)vaeq::LDS_MAX) return VAEQ_ERR_LDS;
     if (a.R < 0 || a.n_frames <= 0 || a.steps <= 0 || a.stride_sym <= 0) return VAEQ_ERR_SHAPE;
     if (a.keep_off < 0 || a.keep_len <= 0 || a.keep_off + a.keep_len > a.B) return VAEQ_ERR_SHAPE;
     if (((int64_t)(a.steps - 1) * a.stride_sym + a.B) * a.sps > a.S) return VAEQ_ERR_SHAPE;  // last window inside the row
-    if (a.R == 0) return VAEQ_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (a.threads == 1 && !vaeq::dp_wave_supported(a)) return VAEQ_ERR_SHAPE;
     if ((a.threads == 0 || a.threads == 1) && vaeq::dp_wave_supported(a)) return vaeq::launch_dp_wave(a, st);
     switch (a.threads) {
     case 0:
-    case 256: return vaeq::launch_dp_lev<256>(a, (size_t)lds, st);
-    case 128: return vaeq::launch_dp_lev<128>(a, (size_t)lds, st);
-    case 64: return vaeq::launch_dp_lev<64>(a, (size_t)lds, st);
+    case 256: return vaeq::launch_dp<256>(a, (size_t)lds, st);
+    case 128: return vaeq::launch_dp<128>(a, (size_t)lds, st);
+    case 64: return vaeq::launch_dp<64>(a, (size_t)lds, st);
     }
     return VAEQ_ERR_SHAPE;
 }
@@ -481,7 +465,8 @@ static int64_t resident_generic(size_t lds)
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return VAEQ_ERR_DEVICE;
     auto k = dp_train_kernel<NT, NLEV>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    // not launch(): this only asks, and a refused attribute is reported by the occupancy query below as VAEQ_ERR_DEVICE (or as 0 resident runs), not as VAEQ_ERR_LDS
+    if (lds > LDS_RAISE_ABOVE) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, NT, lds) != hipSuccess) return VAEQ_ERR_DEVICE;
     return (int64_t)nb * prop.multiProcessorCount;
 }
@@ -495,19 +480,14 @@ extern "C" int64_t vaeq_dp_resident_runs(int32_t B, int32_t sps, int32_t M, int3
     a.B = B; a.sps = sps; a.M = M; a.n_lev = n_lev; a.stride_sym = B; a.keep_len = B; a.S = 4;
     if ((threads == 0 || threads == 1) && vaeq::dp_wave_supported(a)) return vaeq::dp_wave_resident(B, M, n_lev);
     if (threads == 1) return VAEQ_ERR_SHAPE;
-#define VAEQ_RES(NT)                                                          \
-    switch (n_lev) {                                                          \
-    case 2: return vaeq::resident_generic<NT, 2>((size_t)lds);                \
-    case 4: return vaeq::resident_generic<NT, 4>((size_t)lds);                \
-    case 8: return vaeq::resident_generic<NT, 8>((size_t)lds);                \
-    }                                                                         \
-    return VAEQ_ERR_SHAPE;
+    auto resident = [&](auto nt) {
+        return vaeq::dispatch_nlev(n_lev, [&](auto nl) { return vaeq::resident_generic<decltype(nt)::value, decltype(nl)::value>((size_t)lds); });
+    };
     switch (threads) {
     case 0:
-    case 256: VAEQ_RES(256)
-    case 128: VAEQ_RES(128)
-    case 64: VAEQ_RES(64)
+    case 256: return resident(std::integral_constant<int, 256>{});
+    case 128: return resident(std::integral_constant<int, 128>{});
+    case 64: return resident(std::integral_constant<int, 64>{});
     }
-#undef VAEQ_RES
     return VAEQ_ERR_SHAPE;
 }

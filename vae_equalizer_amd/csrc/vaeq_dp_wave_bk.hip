@@ -18,22 +18,12 @@ bool dp_wave_fixl(int B, int M)
 
 int launch_dp_wave_bk(const vaeq_dp_args &a, hipStream_t st)
 {
-    switch (a.n_lev) {
-    case 2: return launch_wave_fixl<25, 2, 128, 1>(a, st);
-    case 4: return launch_wave_fixl<25, 4, 128, 1>(a, st);
-    case 8: return launch_wave_fixl<25, 8, 128, 1>(a, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave_fixl<25, decltype(nl)::value, 128, 1>(a, st); });
 }
 
 int64_t dp_wave_bk_resident(int n_lev)
 {
-    switch (n_lev) {
-    case 2: return wave_resident_fixl<25, 2, 128, 1>();
-    case 4: return wave_resident_fixl<25, 4, 128, 1>();
-    case 8: return wave_resident_fixl<25, 8, 128, 1>();
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident_fixl<25, decltype(nl)::value, 128, 1>(); });
 }
 
 }  // namespace vaeq

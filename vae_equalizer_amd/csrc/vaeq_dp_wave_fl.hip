@@ -9,22 +9,12 @@ namespace vaeq {
 template <int BL, int NW>
 static int launch_fl(const vaeq_dp_args &a, hipStream_t st)
 {
-    switch (a.n_lev) {
-    case 2: return launch_wave_fixl<25, 2, BL, NW>(a, st);
-    case 4: return launch_wave_fixl<25, 4, BL, NW>(a, st);
-    case 8: return launch_wave_fixl<25, 8, BL, NW>(a, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave_fixl<25, decltype(nl)::value, BL, NW>(a, st); });
 }
 template <int BL, int NW>
 static int64_t resident_fl(int n_lev)
 {
-    switch (n_lev) {
-    case 2: return wave_resident_fixl<25, 2, BL, NW>();
-    case 4: return wave_resident_fixl<25, 4, BL, NW>();
-    case 8: return wave_resident_fixl<25, 8, BL, NW>();
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident_fixl<25, decltype(nl)::value, BL, NW>(); });
 }
 
 int launch_dp_wave_fl(const vaeq_dp_args &a, hipStream_t st)

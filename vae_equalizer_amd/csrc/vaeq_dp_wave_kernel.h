@@ -33,6 +33,7 @@
 
 #include "vaeq.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 #include "vaeq_wave.h"
 
 // -DVAEQ_PHASE_STAMPS: shader-clock stamps around the phases of the LAST step of one wave under full load, written over loss[0..] of the launch
@@ -1035,13 +1036,9 @@ static int launch_wave(const vaeq_dp_args &a, hipStream_t st)
         if (!a.eq_out && !a.dec_out) k = pair ? dp_wave_kernel<M, NLEV, BT, true, BT ? 1 : 0, NW> : dp_wave_kernel<M, NLEV, BT, false, BT ? 1 : 0, NW>;
         else if (!a.q_out) k = pair ? dp_wave_kernel<M, NLEV, BT, true, BT ? 2 : 0, NW> : dp_wave_kernel<M, NLEV, BT, false, BT ? 2 : 0, NW>;
     }
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
     const int out = !BT ? 0 : (!a.eq_out && !a.dec_out) ? 1 : !a.q_out ? 2 : 0;
     note_kernel("vaeq::dp_wave_kernel<%d, %d, %d, %s, %d, %d, 0>", M, NLEV, BT, pair ? "true" : "false", out, NW);   // every template argument, as rocprofv3 prints the name
-    hipLaunchKernelGGL(k, dim3(a.R), dim3(64 * NW), lds, st, a);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return launch(k, dim3(a.R), dim3(64 * NW), lds, st, a);
 }
 
 // run-time B <= BL on the fixed LDS layout of BL (immediate offsets and strides, pipelined tap loops), with the output-mode specialisations
@@ -1057,12 +1054,8 @@ static int launch_wave_fixl(const vaeq_dp_args &a, hipStream_t st)
         if (out == 1) k = pair ? dp_wave_kernel<M, NLEV, 0, true, 1, NW, BL> : dp_wave_kernel<M, NLEV, 0, false, 1, NW, BL>;
         else if (out == 2) k = pair ? dp_wave_kernel<M, NLEV, 0, true, 2, NW, BL> : dp_wave_kernel<M, NLEV, 0, false, 2, NW, BL>;
     }
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
     note_kernel("vaeq::dp_wave_kernel<%d, %d, 0, %s, %d, %d, %d>", M, NLEV, pair ? "true" : "false", out, NW, BL);
-    hipLaunchKernelGGL(k, dim3(a.R), dim3(64 * NW), lds, st, a);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return launch(k, dim3(a.R), dim3(64 * NW), lds, st, a);
 }
 
 template <int M, int NLEV, int BL, int NW>
@@ -1079,12 +1072,7 @@ static int64_t wave_resident_fixl()
 template <int M, int BT, int NW>
 static int launch_wave_lev(const vaeq_dp_args &a, hipStream_t st)
 {
-    switch (a.n_lev) {
-    case 2: return launch_wave<M, 2, BT, NW>(a, st);
-    case 4: return launch_wave<M, 4, BT, NW>(a, st);
-    case 8: return launch_wave<M, 8, BT, NW>(a, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave<M, decltype(nl)::value, BT, NW>(a, st); });
 }
 
 template <int M, int NLEV, int BT, int NW>
@@ -1102,12 +1090,7 @@ static int64_t wave_resident(int B)
 template <int M, int BT, int NW>
 static int64_t wave_resident_lev(int B, int n_lev)
 {
-    switch (n_lev) {
-    case 2: return wave_resident<M, 2, BT, NW>(B);
-    case 4: return wave_resident<M, 4, BT, NW>(B);
-    case 8: return wave_resident<M, 8, BT, NW>(B);
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident<M, decltype(nl)::value, BT, NW>(B); });
 }
 
 // every supported M for a given NW (the per-NW translation units instantiate these): M = 25 on the run-time layout (its fixed-layout and baked forms
@@ -1115,22 +1098,12 @@ static int64_t wave_resident_lev(int B, int n_lev)
 template <int M, int NW>
 static int launch_wave_fixl_lev(const vaeq_dp_args &a, hipStream_t st)
 {
-    switch (a.n_lev) {
-    case 2: return launch_wave_fixl<M, 2, 128 * NW, NW, false>(a, st);
-    case 4: return launch_wave_fixl<M, 4, 128 * NW, NW, false>(a, st);
-    case 8: return launch_wave_fixl<M, 8, 128 * NW, NW, false>(a, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave_fixl<M, decltype(nl)::value, 128 * NW, NW, false>(a, st); });
 }
 template <int M, int NW>
 static int64_t wave_resident_fixl_lev(int n_lev)
 {
-    switch (n_lev) {
-    case 2: return wave_resident_fixl<M, 2, 128 * NW, NW>();
-    case 4: return wave_resident_fixl<M, 4, 128 * NW, NW>();
-    case 8: return wave_resident_fixl<M, 8, 128 * NW, NW>();
-    }
-    return VAEQ_ERR_SHAPE;
+    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident_fixl<M, decltype(nl)::value, 128 * NW, NW>(); });
 }
 
 template <int NW>

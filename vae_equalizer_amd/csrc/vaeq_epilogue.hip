@@ -17,6 +17,7 @@
 
 #include "vaeq.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 #include "vaeq_wave.h"
 
 namespace vaeq {
@@ -258,10 +259,7 @@ struct KeepWalk4 {
 };
 
 
-// an LDS read the compiler leaves where the source puts it (a plain read that feeds a short-circuit test is sunk into an exec-masked branch of its own
-// behind its own s_waitcnt lgkmcnt(0): tools/scan_isa.py counted 283 such waits for 426 reads in this kernel)
-typedef const volatile __attribute__((address_space(3))) float epi_lds_cvf;
-__device__ __forceinline__ float epi_ldsv(const float *p) { return *(epi_lds_cvf *)p; }
+// (the loops below read LDS through ldsv, vaeq_wave.h: tools/scan_isa.py counted 283 exposed s_waitcnt lgkmcnt(0) for 426 plain reads in this kernel)
 
 // four consecutive elements of a row: one wide load when the group lies inside the row (and the row is aligned for it), else the kept members one by one
 // (a kept symbol's partner index n + shift never leaves the row: 11 <= n, |shift| <= 10, and the window ends 11 + max|shift| before the row does)
@@ -455,8 +453,8 @@ __global__ __launch_bounds__(EPI_NT, CMA ? EPI_WAVES_CMA : EPI_WAVES) void dp_ep
                         const float rI[4] = {yi, -yi, -yq, yq}, rQ[4] = {yq, -yq, yi, -yi};        // :245-262
                         // d_vec0[lev] <= v < d_vec1[lev] (:267-287): the bounds of the symbol's three TX levels are read ONCE, up front
                         const int lI = min(max((int)dI, 0), NLEV - 1), lQ = min(max((int)dQ, 0), NLEV - 1), lQi = min(max((int)dQi, 0), NLEV - 1);
-                        const float loI = epi_ldsv(sh.lo + lI), hiI = epi_ldsv(sh.hi + lI), loQ = epi_ldsv(sh.lo + lQ), hiQ = epi_ldsv(sh.hi + lQ);
-                        const float loQi = epi_ldsv(sh.lo + lQi), hiQi = epi_ldsv(sh.hi + lQi);
+                        const float loI = ldsv(sh.lo + lI), hiI = ldsv(sh.hi + lI), loQ = ldsv(sh.lo + lQ), hiQ = ldsv(sh.hi + lQ);
+                        const float loQi = ldsv(sh.lo + lQi), hiQi = ldsv(sh.hi + lQi);
 #pragma unroll
                         for (int k = 0; k < 4; k++) {
                             const bool okI = (loI <= rI[k]) & (rI[k] < hiI);
@@ -540,13 +538,10 @@ extern "C" int vaeq_dp_epilogue(int32_t R, int64_t N, int32_t n_lev, int32_t bat
     float *wsE = reinterpret_cast<float *>(workspace);
     int8_t *wsD = reinterpret_cast<int8_t *>(wsE + (size_t)R * 2 * N);
     const __half *tx = reinterpret_cast<const __half *>(tx_f16);
-    switch (n_lev) {
-    case 2: hipLaunchKernelGGL(vaeq::dp_epilogue_kernel<2>, dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    case 4: hipLaunchKernelGGL(vaeq::dp_epilogue_kernel<4>, dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    case 8: hipLaunchKernelGGL(vaeq::dp_epilogue_kernel<8>, dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    default: return VAEQ_ERR_SHAPE;
-    }
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::dispatch_nlev(n_lev, [&](auto nl) {
+        return vaeq::launch(vaeq::dp_epilogue_kernel<decltype(nl)::value>, dim3(R), dim3(vaeq::EPI_NT), 0, st,
+                            N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD);
+    });
 }
 
 extern "C" int vaeq_dp_epilogue_compact(int32_t R, int64_t N, int32_t n_lev, int32_t batch_len, const float *eq, const int8_t *dec, const float *y,
@@ -566,30 +561,19 @@ extern "C" int vaeq_dp_epilogue_compact(int32_t R, int64_t N, int32_t n_lev, int
         const size_t dyn_txc = (size_t)4 * vaeq::nib_words((int)N) * sizeof(uint32_t);
         const bool txc = dyn_txc + sizeof(vaeq::Epi2Shared) <= 53 * 1024 && !(notxc_env && notxc_env[0] == '1');   // three workgroups per CU
         const size_t dyn = txc ? dyn_txc : 0;
-#define VAEQ_EPI2(NL)                                                                                                                     \
-    {                                                                                                                                     \
-        auto k = txc ? vaeq::dp_epilogue_compact_kernel<NL, true> : vaeq::dp_epilogue_compact_kernel<NL, false>;                          \
-        hipLaunchKernelGGL(k, dim3(R), dim3(vaeq::EPI_NT), dyn, st, (int)N, batch_len, eq, dec, y, tx, amp, var, nu_sc, ser, shift, rflag); \
-    }
-        switch (n_lev) {
-        case 2: VAEQ_EPI2(2) break;
-        case 4: VAEQ_EPI2(4) break;
-        case 8: VAEQ_EPI2(8) break;
-        default: return VAEQ_ERR_SHAPE;
-        }
-#undef VAEQ_EPI2
-        return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+        return vaeq::dispatch_nlev(n_lev, [&](auto nl) {
+            constexpr int NL = decltype(nl)::value;
+            auto k = txc ? vaeq::dp_epilogue_compact_kernel<NL, true> : vaeq::dp_epilogue_compact_kernel<NL, false>;
+            return vaeq::launch(k, dim3(R), dim3(vaeq::EPI_NT), dyn, st, (int)N, batch_len, eq, dec, y, tx, amp, var, nu_sc, ser, shift, rflag);
+        });
     }
     float *wsE = const_cast<float *>(eq);
     int8_t *wsD = const_cast<int8_t *>(dec);
     const float *q = nullptr;
-    switch (n_lev) {
-    case 2: hipLaunchKernelGGL(vaeq::dp_epilogue_kernel<2>, dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    case 4: hipLaunchKernelGGL(vaeq::dp_epilogue_kernel<4>, dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    case 8: hipLaunchKernelGGL(vaeq::dp_epilogue_kernel<8>, dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    default: return VAEQ_ERR_SHAPE;
-    }
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::dispatch_nlev(n_lev, [&](auto nl) {
+        return vaeq::launch(vaeq::dp_epilogue_kernel<decltype(nl)::value>, dim3(R), dim3(vaeq::EPI_NT), 0, st,
+                            N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD);
+    });
 }
 
 // The constant-modulus baselines' two-stage epilogue in one launch (func_CMA_DP_MQAM_shaping.py:39-52 after the phase estimation; identical in the
@@ -608,11 +592,8 @@ extern "C" int vaeq_cma_epilogue(int32_t R, int64_t N, int32_t n_lev, const floa
     const __half *tx = reinterpret_cast<const __half *>(tx_f16);
     const float *q = nullptr;
     const int batch_len = 0;
-    switch (n_lev) {
-    case 2: hipLaunchKernelGGL((vaeq::dp_epilogue_kernel<2, true>), dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    case 4: hipLaunchKernelGGL((vaeq::dp_epilogue_kernel<4, true>), dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    case 8: hipLaunchKernelGGL((vaeq::dp_epilogue_kernel<8, true>), dim3(R), dim3(vaeq::EPI_NT), 0, st, N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD); break;
-    default: return VAEQ_ERR_SHAPE;
-    }
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::dispatch_nlev(n_lev, [&](auto nl) {
+        return vaeq::launch(vaeq::dp_epilogue_kernel<decltype(nl)::value, true>, dim3(R), dim3(vaeq::EPI_NT), 0, st,
+                            N, batch_len, q, y, tx, amp, var, nu_sc, ser, shift, rflag, wsE, wsD);
+    });
 }

@@ -26,6 +26,7 @@
 
 #include "vaeq.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 #include "vaeq_noise.h"
 #include "vaeq_wave.h"
 
@@ -453,9 +454,8 @@ extern "C" int vaeq_gen_dp_disperse(int32_t R, int32_t Ls, double fs, double tau
     if (!theta || !spec_complex) return VAEQ_ERR_NULL;
     if (R < 0 || Ls <= 0) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(vaeq::gen_disperse_kernel, dim3((Ls + 255) / 256, R), dim3(256), 0, st, Ls, fs / (double)Ls, tau_cd, tau_pmd,
-                       make_float2(e0_re, e0_im), make_float2(e1_re, e1_im), scale, theta, reinterpret_cast<float2 *>(spec_complex));
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::launch(vaeq::gen_disperse_kernel, dim3((Ls + 255) / 256, R), dim3(256), 0, st, Ls, fs / (double)Ls, tau_cd, tau_pmd,
+                        make_float2(e0_re, e0_im), make_float2(e1_re, e1_im), scale, theta, reinterpret_cast<float2 *>(spec_complex));
 }
 
 extern "C" int vaeq_gen_dp_finish(int32_t R, int32_t N, int32_t sps, int32_t Ls, int32_t Lrow, const float *snr_db, uint64_t seed, uint32_t frame,
@@ -490,11 +490,8 @@ extern "C" int vaeq_gen_awgn(int32_t R, int32_t N, int32_t N_conv, int32_t sps, 
         const char *two_env = getenv("VAEQ_AWGN_TWOPASS");     // A/B switch: the two-pass form for every frame length
         if (grid.x <= 4 && !(two_env && two_env[0] == '1')) {  // short frames (the training frames of both AWGN scripts): one pass, one workgroup per run
             __half *dh = reinterpret_cast<__half *>(data_f16);
-            if (grid.x <= 2)
-                hipLaunchKernelGGL(vaeq::gen_awgn_onepass_kernel<2>, dim3(R), dim3(vaeq::TX_NT), 0, st, N_conv, n_lev, Lg, Ls, amp, cdf, g2, seed, frame, N, ref_offset, dh, fz);
-            else
-                hipLaunchKernelGGL(vaeq::gen_awgn_onepass_kernel<4>, dim3(R), dim3(vaeq::TX_NT), 0, st, N_conv, n_lev, Lg, Ls, amp, cdf, g2, seed, frame, N, ref_offset, dh, fz);
-            return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+            return vaeq::launch(grid.x <= 2 ? vaeq::gen_awgn_onepass_kernel<2> : vaeq::gen_awgn_onepass_kernel<4>, dim3(R), dim3(vaeq::TX_NT), 0, st, N_conv,
+                                n_lev, Lg, Ls, amp, cdf, g2, seed, frame, N, ref_offset, dh, fz);
         }
         if (!sigma_fixed)
             hipLaunchKernelGGL(vaeq::gen_tx_kernel<1>, grid, dim3(vaeq::TX_NT), 0, st, N_conv, n_lev, Lg, Ls, Ls, amp, cdf, g2, seed, frame, 1, sig, N,
@@ -521,10 +518,9 @@ extern "C" int vaeq_gen_awgn_clean(int32_t R, int32_t N, int32_t N_conv, int32_t
     const dim3 grid((Ls + vaeq::TX_TILE - 1) / vaeq::TX_TILE, 1, R);
     vaeq::TxFuse fz{};
     fz.part = power_ws;
-    hipLaunchKernelGGL(vaeq::gen_tx_kernel<3>, grid, dim3(vaeq::TX_NT), 0, st, N_conv, n_lev, Lg, Ls, Ls, amp, cdf,
-                       reinterpret_cast<const float2 *>(g_complex), seed, frame, 1, reinterpret_cast<float2 *>(sig_out), N, ref_offset,
-                       reinterpret_cast<__half *>(data_f16), fz);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return vaeq::launch(vaeq::gen_tx_kernel<3>, grid, dim3(vaeq::TX_NT), 0, st, N_conv, n_lev, Lg, Ls, Ls, amp, cdf,
+                        reinterpret_cast<const float2 *>(g_complex), seed, frame, 1, reinterpret_cast<float2 *>(sig_out), N, ref_offset,
+                        reinterpret_cast<__half *>(data_f16), fz);
 }
 
 // ---- whole DP frame in one call: stage 1 -> hipFFT (in place) -> stage 2 -> inverse hipFFT (in place, 1/Lrow folded into stage 2)

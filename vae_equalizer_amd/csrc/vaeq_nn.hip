@@ -554,10 +554,10 @@ __host__ __device__ inline NNLayout nn_layout_half(int B, int sps, int M, int k1
     // z1h[c][j] holds position b0 - p2 + j of the half starting at sample b0 = n0 sps: what fc2 reads for the half's symbols and what ELU' needs
     const int wa = nh * sps, wb = (nh - 1) * sps + l.p2 + 1;
     const int W = l.p2 + (wa > wb ? wa : wb);
-    l.Lz = npad4(W + 3);
+    l.Lz = pad4(W + 3);
     while ((l.Lz & 7) != 4) l.Lz += 4;                 // an odd multiple of 4: 16 channel rows x 4 consecutive samples hit 64 different banks
-    int o = npad4(l.p2 + 1);                           // front pad: fc1 of half 0 addresses xs[-p2 ...] (masked to fc2's zero padding)
-    auto take = [&](int cnt) { int r = o; o += npad4(cnt); return r; };
+    int o = pad4(l.p2 + 1);                            // front pad: fc1 of half 0 addresses xs[-p2 ...] (masked to fc2's zero padding)
+    auto take = [&](int cnt) { int r = o; o += pad4(cnt); return r; };
     l.xs = take(2 * l.Lx);
     l.z1 = take(l.C * l.Lz); l.zb = l.z1; l.bnst = o;
     l.a2 = take(l.C * B);
@@ -1000,14 +1000,11 @@ static int launch_nn_validate(int R, int N, int sps, int M, int k1, int k2, int 
                               const float *amp, const __half *data, float *ser, int *shift, hipStream_t st)
 {
     const size_t lds = (size_t)nn_layout(NN_TILE, sps, M, NLEV, k1, k2, bn != nullptr, true).total * 4 + (((size_t)N + 15) & ~(size_t)15);
-    if (lds > 150 * 1024) return VAEQ_ERR_LDS;
+    if (lds > LDS_MAX_BESIDE_STATIC) return VAEQ_ERR_LDS;
     const int bk = NLEV == 8 && sps == 2 && M == 25 && k1 == 25 && k2 == 3;                       // (64-QAM only: see launch_nn_train)
     auto k = bk ? nn_validate_kernel<1024, NLEV, NLEV == 8 ? 1 : 0> : nn_validate_kernel<1024, NLEV, 0>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
     note_kernel("vaeq::nn_validate_kernel<1024, %d, %d>", NLEV, bk);
-    hipLaunchKernelGGL(k, dim3(R), dim3(1024), lds, st, N, sps, M, k1, k2, n_shift, x, theta, bn, amp, data, ser, shift);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return launch(k, dim3(R), dim3(1024), lds, st, N, sps, M, k1, k2, n_shift, x, theta, bn, amp, data, ser, shift);
 }
 
 template <int NLEV>
@@ -1032,11 +1029,8 @@ static int launch_nn_train(const vaeq_nn_args &a, size_t lds, hipStream_t st)
         if (k == nn_train_kernel<512, NLEV, false, 2, 1> && he && atoi(he) == 1) {
             const size_t ldh = (size_t)nn_layout_half(300, 2, 25, 25, 3).total * 4;
             auto kh = nn_train_half_kernel<256, 1>;
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh) != hipSuccess)
-                return VAEQ_ERR_LDS;
             note_kernel("vaeq::nn_train_half_kernel<256, 1>");
-            hipLaunchKernelGGL(kh, dim3(a.R), dim3(256), ldh, st, a);
-            return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+            return launch(kh, dim3(a.R), dim3(256), ldh, st, a);
         }
         if (const char *e = getenv("VAEQ_NN_NT")) {            // experiment knob: the baked 64-QAM `Net` kernel on 256 / 1024 threads per run
             const int v = atoi(e);
@@ -1046,11 +1040,8 @@ static int launch_nn_train(const vaeq_nn_args &a, size_t lds, hipStream_t st)
             }
         }
     }
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
     note_kernel("vaeq::nn_train_kernel<%d, %d, %s, %d, %d>", nt, NLEV, a.batch_norm ? "true" : "false", sps_t, bk);   // every template argument
-    hipLaunchKernelGGL(k, dim3(a.R), dim3(nt), lds, st, a);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return launch(k, dim3(a.R), dim3(nt), lds, st, a);
 }
 
 template <int NLEV>
@@ -1058,20 +1049,16 @@ static int launch_nn_forward(int R, int N, int sps, int M, int k1, int k2, const
                              hipStream_t st)
 {
     const size_t lds = (size_t)nn_layout(NN_TILE, sps, M, NLEV, k1, k2, bn != nullptr, true).total * 4;
-    if (lds > 160 * 1024) return VAEQ_ERR_LDS;
+    if (lds > LDS_MAX) return VAEQ_ERR_LDS;
     auto k = nn_forward_kernel<1024, NLEV>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return VAEQ_ERR_LDS;
     note_kernel("vaeq::nn_forward_kernel<1024, %d>", NLEV);
-    hipLaunchKernelGGL(k, dim3(R), dim3(1024), lds, st, N, sps, M, k1, k2, x, theta, bn, q);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return launch(k, dim3(R), dim3(1024), lds, st, N, sps, M, k1, k2, x, theta, bn, q);
 }
 
 static bool nn_shape_ok(int B, int sps, int M, int n_lev, int k1, int k2)
 {
-    if (B <= 0 || sps <= 0 || sps > 8 || M <= 0 || (M & 1) == 0 || M > 63 || !(n_lev == 2 || n_lev == 4 || n_lev == 8)) return false;
-    if (k1 <= 0 || (k1 & 1) == 0 || k1 > 63 || k2 <= 0 || (k2 & 1) == 0 || k2 > 9) return false;
-    return (int64_t)B * sps - 2 * (M / 2) > 0 && B > 2 * (M / 2);
+    if (sps > 8 || !loss_shape_ok(B, sps, M) || !(n_lev == 2 || n_lev == 4 || n_lev == 8)) return false;
+    return k1 > 0 && (k1 & 1) == 1 && k1 <= 63 && k2 > 0 && (k2 & 1) == 1 && k2 <= 9;
 }
 
 }  // namespace vaeq
@@ -1097,15 +1084,10 @@ extern "C" int vaeq_nn_train(const vaeq_nn_args *pa, void *stream)
     if (a.batch_norm && !a.bn_running) return VAEQ_ERR_NULL;
     const int64_t lds = vaeq_nn_lds_bytes(a.B, a.sps, a.M, a.n_lev, a.k1, a.k2, a.batch_norm);
     if (lds < 0) return (int)lds;
-    if (lds > 160 * 1024) return VAEQ_ERR_LDS;
+    if (lds > (int64_t)vaeq::LDS_MAX) return VAEQ_ERR_LDS;
     if (a.R < 0 || a.steps <= 0 || (int64_t)a.steps * a.B * a.sps > a.S || (a.batch_norm && (int64_t)a.B * a.sps < 2)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (a.n_lev) {
-    case 2: return vaeq::launch_nn_train<2>(a, (size_t)lds, st);
-    case 4: return vaeq::launch_nn_train<4>(a, (size_t)lds, st);
-    case 8: return vaeq::launch_nn_train<8>(a, (size_t)lds, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return vaeq::dispatch_nlev(a.n_lev, [&](auto nl) { return vaeq::launch_nn_train<decltype(nl)::value>(a, (size_t)lds, st); });
 }
 
 extern "C" int vaeq_nn_forward(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t k1, int32_t k2, const float *x,
@@ -1115,12 +1097,9 @@ extern "C" int vaeq_nn_forward(int32_t R, int64_t N, int32_t sps, int32_t M, int
     if (!x || !theta || !q) return VAEQ_ERR_NULL;
     if (R < 0 || N < 0 || N > 0x3fffffff || !vaeq::nn_shape_ok(vaeq::NN_TILE, sps, M, n_lev, k1, k2)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (n_lev) {
-    case 2: return vaeq::launch_nn_forward<2>(R, (int)N, sps, M, k1, k2, x, theta, bn_running, q, st);
-    case 4: return vaeq::launch_nn_forward<4>(R, (int)N, sps, M, k1, k2, x, theta, bn_running, q, st);
-    case 8: return vaeq::launch_nn_forward<8>(R, (int)N, sps, M, k1, k2, x, theta, bn_running, q, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return vaeq::dispatch_nlev(n_lev, [&](auto nl) {
+        return vaeq::launch_nn_forward<decltype(nl)::value>(R, (int)N, sps, M, k1, k2, x, theta, bn_running, q, st);
+    });
 }
 
 extern "C" int vaeq_nn_validate(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t k1, int32_t k2, int32_t n_shift,
@@ -1133,10 +1112,7 @@ extern "C" int vaeq_nn_validate(int32_t R, int64_t N, int32_t sps, int32_t M, in
         return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *d = reinterpret_cast<const __half *>(data_f16);
-    switch (n_lev) {
-    case 2: return vaeq::launch_nn_validate<2>(R, (int)N, sps, M, k1, k2, n_shift, x, theta, bn_running, amp, d, ser, shift, st);
-    case 4: return vaeq::launch_nn_validate<4>(R, (int)N, sps, M, k1, k2, n_shift, x, theta, bn_running, amp, d, ser, shift, st);
-    case 8: return vaeq::launch_nn_validate<8>(R, (int)N, sps, M, k1, k2, n_shift, x, theta, bn_running, amp, d, ser, shift, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return vaeq::dispatch_nlev(n_lev, [&](auto nl) {
+        return vaeq::launch_nn_validate<decltype(nl)::value>(R, (int)N, sps, M, k1, k2, n_shift, x, theta, bn_running, amp, d, ser, shift, st);
+    });
 }

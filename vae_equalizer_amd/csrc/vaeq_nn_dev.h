@@ -8,7 +8,9 @@
 
 #include "vaeq.h"
 #include "vaeq_common.h"
+#include "vaeq_launch.h"
 #include "vaeq_validate.h"
+#include "vaeq_wave.h"
 
 #ifndef VAEQ_NN_PREF
 #define VAEQ_NN_PREF 0                                 // 1: baked 64-QAM `Net` kernel fetches the next minibatch into registers during the step (measured: no gain, 16 spilled registers)
@@ -34,14 +36,12 @@ struct NNLayout {
     int xs, z1, zb, bnst, a2, mu, vr, es, VS, th, gr, am, av, ax, w1t, w2t, w2u, red, total;
 };
 
-__host__ __device__ inline int npad4(int x) { return (x + 3) & ~3; }
-
 __host__ __device__ inline NNLayout nn_layout(int B, int sps, int M, int n, int k1, int k2, bool bn = false, bool eval = false)
 {
     NNLayout l;
     l.C = 2 * n; l.L = B * sps; l.p1 = k1 / 2; l.p2 = k2 / 2;
-    l.Lx = npad4(l.L + 2 * l.p1 + 8);                  // zero halo + room for the 4-wide windows of the last quad
-    l.Lz = npad4(l.L + 2 * l.p2 + 4);
+    l.Lx = pad4(l.L + 2 * l.p1 + 8);                   // zero halo + room for the 4-wide windows of the last quad
+    l.Lz = pad4(l.L + 2 * l.p2 + 4);
     const bool mf = nn_mf(n);
     const int CP = nn_cp(n);                           // channel rows in LDS (MFMA path: 16, the rows past C stay zero)
     if (mf)                                            // MFMA path: row stride an odd multiple of 4 dwords, so that 16 channels x 4
@@ -52,7 +52,7 @@ __host__ __device__ inline NNLayout nn_layout(int B, int sps, int M, int n, int 
     l.oG = l.oB2 + l.C; l.oBt = l.oG + l.C;            // BatchNorm weight / bias (Net_BN only)
     l.oH = bn ? l.oBt + l.C : l.oG; l.NP = l.oH + 2 * M;
     int o = 0;
-    auto take = [&](int cnt) { int r = o; o += npad4(cnt); return r; };
+    auto take = [&](int cnt) { int r = o; o += pad4(cnt); return r; };
     const int one = (mf && !eval) ? 1 : 0;         // training on the MFMA path: a row of ones behind the input rows and behind the channel rows (the
                                                        // bias columns of the weight-gradient GEMMs read it like any other operand row: mfma_wgrad16, ROW1)
     l.xs = take((2 + one) * l.Lx);
@@ -71,7 +71,7 @@ __host__ __device__ inline NNLayout nn_layout(int B, int sps, int M, int n, int 
     }
     l.a2 = take(CP * l.AS + 2 * l.A0);
     l.mu = take(2 * B); l.vr = take(2 * B);
-    l.ES = npad4(l.nm + 2 * l.Mh + 4);                 // Mh zeros | nm residual samples | Mh + 4 zeros (nn_train_kernel)
+    l.ES = pad4(l.nm + 2 * l.Mh + 4);                  // Mh zeros | nm residual samples | Mh + 4 zeros (nn_train_kernel)
     l.es = take(2 * l.ES);
     l.VS = take(M);
     l.PH = take(M + 1);
@@ -209,17 +209,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Sum over the 64 lanes on the vector ALU (DPP row operations + four v_readlane; the form of vaeq_wave.h's wave_sum_dpp): vaeq_common.h's wave_sum is
 // a butterfly of six ds_bpermute, i.e. six DEPENDENT LDS round trips -- the BatchNorm statistics take four such sums per channel.  Fixed order.
-template <int CTRL>
-__device__ __forceinline__ float nn_dpp(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
+// (not folded into wave_sum_dpp: with VAEQ_SUM_BCAST = 1 that one ends on two DPP broadcasts + one v_readlane, other instructions than these)
 __device__ __forceinline__ float wave_sum_fast(float v)
 {
-    v += nn_dpp<0xB1>(v);                                      // quad_perm:[1,0,3,2]
-    v += nn_dpp<0x4E>(v);                                      // quad_perm:[2,3,0,1]
-    v += nn_dpp<0x141>(v);                                     // row_half_mirror
-    v += nn_dpp<0x140>(v);                                     // row_mirror: every lane of a 16-lane row holds the row's sum
+    v += dpp_f<0xB1>(v);                                       // quad_perm:[1,0,3,2]
+    v += dpp_f<0x4E>(v);                                       // quad_perm:[2,3,0,1]
+    v += dpp_f<0x141>(v);                                      // row_half_mirror
+    v += dpp_f<0x140>(v);                                      // row_mirror: every lane of a 16-lane row holds the row's sum
     const int b = __builtin_bit_cast(int, v);
     const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
@@ -244,7 +240,7 @@ __device__ __forceinline__ void nn_block_reduce3(float a, float b, float c, floa
     __syncthreads();
 }
 
-// ldsv: a 4-byte LDS read the compiler must leave where the source puts it (volatile, LDS address space -- as lds2 in vaeq_wave.h).  Used wherever a
+// ldsv: a 4-byte LDS read the compiler must leave where the source puts it (vaeq_wave.h, beside lds2).  Used wherever a
 // read from a CLAMPED (always valid) address feeds a select: an ordinary load is sunk into a branch of its own behind its own s_waitcnt lgkmcnt(0)
 // (the backend will not speculate it), i.e. one exposed LDS round trip per operand -- the pattern round 3 found in the epilogue kernel and, with the ISA
 // in hand, here: 35 such branches per tile group of the transposed convolution.
@@ -255,8 +251,6 @@ __device__ __forceinline__ void nn_block_reduce3(float a, float b, float c, floa
 #ifndef VAEQ_NN_PIN
 #define VAEQ_NN_PIN 0                                  // measured: the pinned pipeline is 3.7 % SLOWER than the backend's load-use order (see lds1 below)
 #endif
-typedef const volatile __attribute__((address_space(3))) float lds_cvf;
-__device__ __forceinline__ float ldsv(const float *p) { return *(lds_cvf *)p; }
 __device__ __forceinline__ float lds1(const float *p)
 {
 #if VAEQ_NN_PIN

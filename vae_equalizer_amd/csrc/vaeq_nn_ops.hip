@@ -25,8 +25,8 @@ __host__ __device__ inline NNLayout nn_enc_layout(int L, int sps, int n, int k1,
     NNLayout l = {};
     const int N = (L + sps - 1) / sps;
     l.C = 2 * n; l.L = L; l.p1 = k1 / 2; l.p2 = k2 / 2;
-    l.Lx = npad4(L + 2 * l.p1 + 8);
-    l.Lz = npad4(L + 2 * l.p2 + 4);
+    l.Lx = pad4(L + 2 * l.p1 + 8);
+    l.Lz = pad4(L + 2 * l.p2 + 4);
     const bool mf = nn_mf(n);
     const int CP = nn_cp(n);
     if (mf)
@@ -37,7 +37,7 @@ __host__ __device__ inline NNLayout nn_enc_layout(int L, int sps, int n, int k1,
     l.oG = l.oB2 + l.C; l.oBt = l.oG + l.C;
     l.oH = l.NP = bn ? l.oBt + l.C : l.oG;
     int o = 0;
-    auto take = [&](int cnt) { int r = o; o += npad4(cnt); return r; };
+    auto take = [&](int cnt) { int r = o; o += pad4(cnt); return r; };
     const int one = (mf && bwd) ? 1 : 0;
     l.xs = take((2 + one) * l.Lx);
     l.z1 = take((CP + (bn ? 0 : one)) * l.Lz);
@@ -395,14 +395,6 @@ static bool nn_enc_shape_ok(int sps, int n_lev, int k1, int k2)
 }
 
 constexpr int64_t NN_ENC_LMAX = 1 << 20;                   // far past the LDS ceiling: keeps the layout arithmetic inside 32 bits
-constexpr size_t NN_ENC_LDS = 160 * 1024;
-
-template <typename K>
-static int nn_enc_set_lds(K k, size_t lds)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? VAEQ_OK
-                                                                                                                                   : VAEQ_ERR_LDS;
-}
 
 template <int NLEV>
 static int launch_nn_enc_forward(int R, int L, int sps, int k1, int k2, bool bn, bool training, const float *x, const float *theta,
@@ -410,26 +402,21 @@ static int launch_nn_enc_forward(int R, int L, int sps, int k1, int k2, bool bn,
 {
     if (bn && training) {
         const size_t lds = (size_t)nn_enc_layout(L, sps, NLEV, k1, k2, true, true).total * 4;      // the ceiling of the backward pass, so that what
-        if (lds > NN_ENC_LDS) return VAEQ_ERR_LDS;                                                   // this call accepts can be differentiated
+        if (lds > LDS_MAX) return VAEQ_ERR_LDS;                                                   // this call accepts can be differentiated
         auto k = nn_enc_bn_forward_kernel<512, NLEV>;
         const size_t ldf = (size_t)nn_enc_layout(L, sps, NLEV, k1, k2, true, false).total * 4;
-        if (nn_enc_set_lds(k, ldf) != VAEQ_OK) return VAEQ_ERR_LDS;
         note_kernel("vaeq::nn_enc_bn_forward_kernel<512, %d>", NLEV);
-        hipLaunchKernelGGL(k, dim3(R), dim3(512), ldf, st, L, sps, k1, k2, x, theta, bn_running, bn_saved, q);
-    } else {
-        int tile = NN_TILE;
-        size_t lds = (size_t)nn_layout(tile, sps, 1, NLEV, k1, k2, bn, true).total * 4;
-        while (lds > NN_ENC_LDS && tile > 15) {
-            tile = tile / 2;                                   // 127, 63, 31, 15
-            lds = (size_t)nn_layout(tile, sps, 1, NLEV, k1, k2, bn, true).total * 4;
-        }
-        if (lds > NN_ENC_LDS) return VAEQ_ERR_LDS;
-        auto k = nn_enc_forward_kernel<1024, NLEV>;
-        if (nn_enc_set_lds(k, lds) != VAEQ_OK) return VAEQ_ERR_LDS;
-        note_kernel("vaeq::nn_enc_forward_kernel<1024, %d>", NLEV);
-        hipLaunchKernelGGL(k, dim3(R), dim3(1024), lds, st, L, sps, k1, k2, tile, x, theta, bn ? bn_running : nullptr, q);
+        return launch(k, dim3(R), dim3(512), ldf, st, L, sps, k1, k2, x, theta, bn_running, bn_saved, q);
     }
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    int tile = NN_TILE;
+    size_t lds = (size_t)nn_layout(tile, sps, 1, NLEV, k1, k2, bn, true).total * 4;
+    while (lds > LDS_MAX && tile > 15) {
+        tile = tile / 2;                                       // 127, 63, 31, 15
+        lds = (size_t)nn_layout(tile, sps, 1, NLEV, k1, k2, bn, true).total * 4;
+    }
+    if (lds > LDS_MAX) return VAEQ_ERR_LDS;
+    note_kernel("vaeq::nn_enc_forward_kernel<1024, %d>", NLEV);
+    return launch(nn_enc_forward_kernel<1024, NLEV>, dim3(R), dim3(1024), lds, st, L, sps, k1, k2, tile, x, theta, bn ? bn_running : nullptr, q);
 }
 
 template <int NLEV>
@@ -437,12 +424,10 @@ static int launch_nn_enc_backward(int R, int L, int sps, int k1, int k2, int mod
                                   const float *gq, const float *stats, float *g, hipStream_t st)
 {
     const size_t lds = (size_t)nn_enc_layout(L, sps, NLEV, k1, k2, mode != 0, true).total * 4;
-    if (lds > NN_ENC_LDS) return VAEQ_ERR_LDS;
+    if (lds > LDS_MAX) return VAEQ_ERR_LDS;
     auto k = mode == 0 ? nn_enc_backward_kernel<512, NLEV, 0> : mode == 1 ? nn_enc_backward_kernel<512, NLEV, 1> : nn_enc_backward_kernel<512, NLEV, 2>;
-    if (nn_enc_set_lds(k, lds) != VAEQ_OK) return VAEQ_ERR_LDS;
     note_kernel("vaeq::nn_enc_backward_kernel<512, %d, %d>", NLEV, mode);
-    hipLaunchKernelGGL(k, dim3(R), dim3(512), lds, st, L, sps, k1, k2, x, theta, q, gq, stats, g);
-    return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
+    return launch(k, dim3(R), dim3(512), lds, st, L, sps, k1, k2, x, theta, q, gq, stats, g);
 }
 
 }  // namespace vaeq
@@ -472,12 +457,9 @@ extern "C" int vaeq_nn_enc_forward(int32_t R, int64_t L, int32_t sps, int32_t n_
         if (L > vaeq::NN_ENC_LMAX) return VAEQ_ERR_LDS;
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (n_lev) {
-    case 2: return vaeq::launch_nn_enc_forward<2>(R, (int)L, sps, k1, k2, bn, tr, x, theta_net, bn_running, bn_saved, q, st);
-    case 4: return vaeq::launch_nn_enc_forward<4>(R, (int)L, sps, k1, k2, bn, tr, x, theta_net, bn_running, bn_saved, q, st);
-    case 8: return vaeq::launch_nn_enc_forward<8>(R, (int)L, sps, k1, k2, bn, tr, x, theta_net, bn_running, bn_saved, q, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return vaeq::dispatch_nlev(n_lev, [&](auto nl) {
+        return vaeq::launch_nn_enc_forward<decltype(nl)::value>(R, (int)L, sps, k1, k2, bn, tr, x, theta_net, bn_running, bn_saved, q, st);
+    });
 }
 
 extern "C" int vaeq_nn_enc_backward(int32_t R, int64_t L, int32_t sps, int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm, int32_t training,
@@ -490,10 +472,7 @@ extern "C" int vaeq_nn_enc_backward(int32_t R, int64_t L, int32_t sps, int32_t n
     if (L > vaeq::NN_ENC_LMAX) return VAEQ_ERR_LDS;
     const int mode = batch_norm ? (training ? 1 : 2) : 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (n_lev) {
-    case 2: return vaeq::launch_nn_enc_backward<2>(R, (int)L, sps, k1, k2, mode, x, theta_net, q, gq, bn_stats, g_theta_net, st);
-    case 4: return vaeq::launch_nn_enc_backward<4>(R, (int)L, sps, k1, k2, mode, x, theta_net, q, gq, bn_stats, g_theta_net, st);
-    case 8: return vaeq::launch_nn_enc_backward<8>(R, (int)L, sps, k1, k2, mode, x, theta_net, q, gq, bn_stats, g_theta_net, st);
-    }
-    return VAEQ_ERR_SHAPE;
+    return vaeq::dispatch_nlev(n_lev, [&](auto nl) {
+        return vaeq::launch_nn_enc_backward<decltype(nl)::value>(R, (int)L, sps, k1, k2, mode, x, theta_net, q, gq, bn_stats, g_theta_net, st);
+    });
 }

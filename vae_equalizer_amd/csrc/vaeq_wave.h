@@ -82,6 +82,10 @@ __device__ __forceinline__ void cmacf(cacc &c, v2f t, v2f v)
 typedef const volatile __attribute__((address_space(3))) v2f lds_cv2f;
 __device__ __forceinline__ v2f lds2(const float2 *p) { return *(lds_cv2f *)p; }
 __device__ __forceinline__ v2f lds2(const float *p) { return *(lds_cv2f *)p; }
+// ... and the 4-byte form: wherever a read from a clamped (always valid) address feeds a select or a short-circuit test, which the backend would
+// otherwise sink into a branch of its own behind its own s_waitcnt lgkmcnt(0)
+typedef const volatile __attribute__((address_space(3))) float lds_cvf;
+__device__ __forceinline__ float ldsv(const float *p) { return *(lds_cvf *)p; }
 __device__ __forceinline__ float2 f2(v2f v) { return make_float2(v.x, v.y); }
 // lds2 where the kernel can afford it (V), an ordinary load (free to fuse / reorder: fewer live registers) where it is register-starved
 template <bool V>
