@@ -151,6 +151,18 @@ int vaeq_dp_loss_bwd(int32_t R, int32_t B, int32_t sps, int32_t M, int32_t n_lev
 int vaeq_dp_forward_bwd(int32_t R, int32_t N, int32_t sps, int32_t M, int32_t n_lev, const float *x, const float *q, const float *y,
                         const float *gq, const float *gy, const float *amp, const float *var, float *gW, void *stream);
 
+/* Input gradients of the same two operators (complex gradients packed as d/dRe + j d/dIm, like x itself); fixed summation order, no atomics.
+ *   vaeq_dp_loss_bwd_x   : loss_function_shaping (shared_funcs.py:123-129: rx enters through e = rx[mh:-mh] - D): g_up[R] ->
+ *                          gx[R][2][2][B*sps] = dL/drx = g_up (nm / C_chi) 2 e on the nm inner samples, exactly 0 on the mh samples at either end
+ *   vaeq_dp_forward_bwd_x: twoXtwoFIR.forward (shared_funcs.py:500-516, the two strided Conv1d over the packed input): gq, gy (nullable), the
+ *                          forward's q, y and the taps W[R][2][4][M] -> gx[R][2][2][N*sps] = dL/dx, the transposed strided correlation
+ *                          gx[p][s] = sum_o sum_{n sps + k - M/2 = s} conj(w[o][p][k]) dL/dout[o][n]  (dL/dout as vaeq_dp_forward_bwd forms it)
+ * Ceilings: vaeq_dp_loss_bwd's for the loss; 4 (4 N + 8 M) bytes of LDS for the FIR. */
+int vaeq_dp_loss_bwd_x(int32_t R, int32_t B, int32_t sps, int32_t M, int32_t n_lev, const float *q, const float *x, const float *h,
+                       const float *amp, const float *g_up, float *gx, void *stream);
+int vaeq_dp_forward_bwd_x(int32_t R, int32_t N, int32_t sps, int32_t M, int32_t n_lev, const float *W, const float *q, const float *y,
+                          const float *gq, const float *gy, const float *amp, const float *var, float *gx, void *stream);
+
 /* ------------------------------------------------------------------------
  * Single-polarisation (AWGN / ISI channel) VAE-LE training loop.
  *
@@ -205,6 +217,17 @@ int vaeq_awgn_loss_bwd(int32_t R, int32_t B, int32_t sps, int32_t M, int32_t n_l
                        const float *amp, const float *P, const float *g_up, float *gq, float *gh, void *stream);
 int vaeq_awgn_forward_bwd(int32_t R, int32_t N, int32_t sps, int32_t M, int32_t n_lev, const float *x, const float *W, const float *amp,
                           const float *amp_mean, const float *var, const float *gq, const float *gy, float *gW, void *stream);
+
+/* Input gradients of the two stand-alone AWGN operators:
+ *   vaeq_awgn_loss_bwd_x   : loss_function (func_VAELE_MQAM_shaping.py:84-89 / func_VAENN_MQAM.py:84-89; the prior plays no part): g_up[R] ->
+ *                            gx[R][2][B*sps] = g_up (nm / C) 2 e on the inner samples, exactly 0 on the M/2 samples at either end
+ *   vaeq_awgn_forward_bwd_x: twoFIR.forward (func_VAELE_MQAM_shaping.py:214-231): gq (+ nullable gy on the un-normalised output) ->
+ *                            gx[R][2][N*sps]; dL/dout includes the normalisation's Jacobian (:228) as in vaeq_awgn_forward_bwd, then the
+ *                            transposed strided correlation with w = W0 - j W1.  Same LDS ceilings as the two siblings. */
+int vaeq_awgn_loss_bwd_x(int32_t R, int32_t B, int32_t sps, int32_t M, int32_t n_lev, const float *q, const float *x, const float *h,
+                         const float *amp, const float *g_up, float *gx, void *stream);
+int vaeq_awgn_forward_bwd_x(int32_t R, int32_t N, int32_t sps, int32_t M, int32_t n_lev, const float *x, const float *W, const float *amp,
+                            const float *amp_mean, const float *var, const float *gq, const float *gy, float *gx, void *stream);
 
 /* twoFIR.forward in eval mode (validation pass, func_VAELE_MQAM_shaping.py:311-313) on N symbols per run:
  * x[R][2][N*sps], W[R][2][M] -> q[R][2*n_lev][N] (nullable), y[R][2][N] (un-normalised). */
@@ -326,7 +349,10 @@ int vaeq_nn_forward(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev,
  * vaeq_nn_enc_backward: q = the forward's output, gq[R][2 n_lev][N] = ANY upstream gradient dL/dq -> g_theta_net[R][NPnet]; x gets no gradient.
  *   bn_stats: Net: ignored; Net_BN training: the forward's bn_saved; Net_BN eval: bn_running.  ELU(fc1(x)) is recomputed, not saved.
  * The training-mode Net_BN forward and every backward keep a run's whole input in LDS, one workgroup per run: VAEQ_ERR_LDS when
- * vaeq_nn_enc_lds_bytes() exceeds 160 KiB.  No atomics: results are bit-reproducible and do not depend on R. */
+ * vaeq_nn_enc_lds_bytes() exceeds 160 KiB.  No atomics: results are bit-reproducible and do not depend on R.
+ * vaeq_nn_enc_backward_x: vaeq_nn_enc_backward (the same g_theta_net, bit for bit) plus the input gradient through fc1 (:179 / :201):
+ *   gx[R][2][L]: gx[i][s] = sum_c sum_k fc1.weight[c][i][k] dL/d(fc1 output)[c][s - k + k1 / 2]; x_res (:183-185) cancels in the softmax and adds
+ *   nothing.  It needs no LDS beyond vaeq_nn_enc_lds_bytes(), which is its ceiling too. */
 int64_t vaeq_nn_enc_param_count(int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm);
 int64_t vaeq_nn_enc_lds_bytes(int64_t L, int32_t sps, int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm);
 int vaeq_nn_enc_forward(int32_t R, int64_t L, int32_t sps, int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm, int32_t training,
@@ -334,6 +360,9 @@ int vaeq_nn_enc_forward(int32_t R, int64_t L, int32_t sps, int32_t n_lev, int32_
 int vaeq_nn_enc_backward(int32_t R, int64_t L, int32_t sps, int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm, int32_t training,
                          const float *x, const float *theta_net, const float *q, const float *gq, const float *bn_stats,
                          float *g_theta_net, void *stream);
+int vaeq_nn_enc_backward_x(int32_t R, int64_t L, int32_t sps, int32_t n_lev, int32_t k1, int32_t k2, int32_t batch_norm, int32_t training,
+                           const float *x, const float *theta_net, const float *q, const float *gq, const float *bn_stats,
+                           float *g_theta_net, float *gx, void *stream);
 
 /* The whole VAE-NN validation block (:287-301: eval forward, find_shift :147-166, SER_q :97-123) in one call, q not materialised:
  * x[R][2][N*sps], theta[R][NP], data_f16[R][2][N] -> ser[R], shift[R] (nullable). */
@@ -430,7 +459,7 @@ const char *vaeq_strerror(int code);
 
 /* Measurement helpers (no reference counterpart; SURVEY 8d asks for them).
  * vaeq_last_kernel: name of the kernel instantiation the calling thread's most recent vaeq_dp_train / vaeq_awgn_train / vaeq_cma / vaeq_cpe /
- * vaeq_nn_train / vaeq_nn_forward / vaeq_nn_validate / vaeq_nn_enc_forward / vaeq_nn_enc_backward launched (as a profiler prints it, e.g. "vaeq::dp_wave_kernel<25, 8, 100, true, 1, 1>" or "vaeq::cma_kernel<true, false>"), copied into
+ * vaeq_nn_train / vaeq_nn_forward / vaeq_nn_validate / vaeq_nn_enc_forward / vaeq_nn_enc_backward / any *_bwd_x / vaeq_nn_enc_backward_x launched (as a profiler prints it, e.g. "vaeq::dp_wave_kernel<25, 8, 100, true, 1, 1>" or "vaeq::cma_kernel<true, false>"), copied into
  * buf[len] -- bench.py names its roofline kernel from this, the tests check which vaeq_cma instantiation a shape reaches.
  * vaeq_stream_copy: dst[bytes] = src[bytes] with a plain 16-byte grid-stride copy kernel (bytes and both pointers multiples of 16): the
  * measured HBM copy bandwidth that stands next to the 8 TB/s spec peak in the roofline. */

@@ -14,7 +14,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("VAEQ_LIB") or os.path.join(_PKG, "libvaeq_hip.so")   # VAEQ_LIB: A/B builds of the kernels (tools/build_variant.sh)
 SOURCES = ["vaeq_dp.hip", "vaeq_dp_wave.hip", "vaeq_dp_wave_mw.hip", "vaeq_dp_wave_mw8.hip", "vaeq_dp_wave_bk.hip", "vaeq_dp_wave_b128.hip", "vaeq_dp_wave_fl.hip", "vaeq_awgn.hip", "vaeq_awgn_wave.hip", "vaeq_misc.hip", "vaeq_ops.hip", "vaeq_nn.hip", "vaeq_nn_ops.hip", "vaeq_cma.hip", "vaeq_awgn_cma.hip", "vaeq_awgn_dfe.hip", "vaeq_epilogue.hip", "vaeq_gen.hip"]
-HEADERS = ["vaeq_common.h", "vaeq_launch.h", "vaeq_wave.h", "vaeq_validate.h", "vaeq_dp_wave_kernel.h", "vaeq_gen_fused.h", "vaeq_epilogue_lds.h", "vaeq_noise.h", "vaeq_awgn_eval.h", "vaeq_nn_dev.h"]
+HEADERS = ["vaeq_common.h", "vaeq_launch.h", "vaeq_wave.h", "vaeq_validate.h", "vaeq_dp_wave_kernel.h", "vaeq_gen_fused.h", "vaeq_epilogue_lds.h", "vaeq_noise.h", "vaeq_awgn_eval.h", "vaeq_nn_dev.h", "vaeq_nn_enc_backward_body.h"]
 _LIB = None
 
 
@@ -107,7 +107,8 @@ EXPORTS = ["vaeq_dp_train", "vaeq_dp_step_debug", "vaeq_dp_lds_bytes", "vaeq_dp_
            "vaeq_awgn_lds_bytes", "vaeq_awgn_forward", "vaeq_awgn_validate", "vaeq_awgn_validate_gen", "vaeq_gen_awgn_clean", "vaeq_awgn_loss", "vaeq_awgn_loss_bwd", "vaeq_awgn_forward_bwd", "vaeq_gen_awgn", "vaeq_nn_train", "vaeq_nn_param_count", "vaeq_nn_lds_bytes", "vaeq_nn_forward", "vaeq_nn_validate", "vaeq_nn_enc_param_count", "vaeq_nn_enc_lds_bytes", "vaeq_nn_enc_forward",
            "vaeq_nn_enc_backward", "vaeq_cma", "vaeq_cpe", "vaeq_version", "vaeq_strerror", "vaeq_last_kernel", "vaeq_stream_copy", "vaeq_gen_dp_power_parts", "vaeq_cma_epilogue",
            "vaeq_awgn_cma", "vaeq_awgn_cma_validate", "vaeq_awgn_cma_validate_ws_bytes", "vaeq_awgn_lmmse_eval",
-           "vaeq_awgn_lmmse_eval_ws_bytes", "vaeq_awgn_dfe", "vaeq_awgn_dfe_ws_bytes"]
+           "vaeq_awgn_lmmse_eval_ws_bytes", "vaeq_awgn_dfe", "vaeq_awgn_dfe_ws_bytes",
+           "vaeq_dp_forward_bwd_x", "vaeq_dp_loss_bwd_x", "vaeq_awgn_forward_bwd_x", "vaeq_awgn_loss_bwd_x", "vaeq_nn_enc_backward_x"]
 
 
 def lib():
@@ -205,6 +206,16 @@ def lib():
         L.vaeq_awgn_loss_bwd.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 9
         L.vaeq_awgn_forward_bwd.restype = C.c_int
         L.vaeq_awgn_forward_bwd.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 9
+        L.vaeq_dp_forward_bwd_x.restype = C.c_int
+        L.vaeq_dp_forward_bwd_x.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 9
+        L.vaeq_dp_loss_bwd_x.restype = C.c_int
+        L.vaeq_dp_loss_bwd_x.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 7
+        L.vaeq_awgn_forward_bwd_x.restype = C.c_int
+        L.vaeq_awgn_forward_bwd_x.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 9
+        L.vaeq_awgn_loss_bwd_x.restype = C.c_int
+        L.vaeq_awgn_loss_bwd_x.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 7
+        L.vaeq_nn_enc_backward_x.restype = C.c_int
+        L.vaeq_nn_enc_backward_x.argtypes = [C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 8
         L.vaeq_nn_validate.restype = C.c_int
         L.vaeq_nn_validate.argtypes = [C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 8
         L.vaeq_gen_dp_power_parts.restype = C.c_int32

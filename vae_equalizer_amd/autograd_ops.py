@@ -9,8 +9,17 @@ They make a reference-style training loop
 work on the GPU with torch.optim -- the differentiable form of the drop-in operator surface.  It is NOT how
 the product trains (one fused kernel does forward, loss, backward and Adam: engine.DPEngine); it exists so that code written
 against the reference's operators keeps working.  No CPU path: CPU tensors are refused by _native.ptr().
+
+Every operator is differentiable in its parameters AND in its input signal, so a differentiable stage in front of the equalizer (an IQ
+compensator, a pre-filter, another network) receives its gradient like behind the reference's torch modules:
+    fir_demap, awgn_fir_demap   d/dW (vaeq_dp_forward_bwd, vaeq_awgn_forward_bwd)  and d/dx  (vaeq_dp_forward_bwd_x, vaeq_awgn_forward_bwd_x)
+    elbo_loss, awgn_elbo_loss   d/dq, d/dh_est (vaeq_dp_loss_bwd, vaeq_awgn_loss_bwd)  and d/drx (vaeq_dp_loss_bwd_x, vaeq_awgn_loss_bwd_x)
+    nn_encode                   d/dparams (vaeq_nn_enc_backward)                       and d/dx  (vaeq_nn_enc_backward_x, with d/dparams in the same pass)
+A backward kernel is launched only for the gradients ctx.needs_input_grad asks for.  The backward passes are once_differentiable: a double
+backward raises torch's error.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .engine import _f32, dp_forward, dp_loss, pad_to_symbols
@@ -22,16 +31,19 @@ class _FIRDemap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, amp, var, nu_sc, sps):
         q, y = dp_forward(x, W, amp, var, nu_sc, sps)
-        ctx.save_for_backward(x, q, y, amp, var)
+        ctx.save_for_backward(x, W, q, y, amp, var)
         ctx.sps, ctx.M = sps, W.shape[-1]
         return q, y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gq, gy):
-        x, q, y, amp, var = ctx.saved_tensors
+        x, W, q, y, amp, var = ctx.saved_tensors
         gq = gq.contiguous()
         gy = gy.contiguous() if gy is not None else None
-        return None, _fir_bwd(x, q, y, gq, gy, amp, var, ctx.sps, ctx.M), None, None, None, None
+        gx = _fir_bwd_x(x, W, q, y, gq, gy, amp, var, ctx.sps, ctx.M) if ctx.needs_input_grad[0] else None
+        gW = _fir_bwd(x, q, y, gq, gy, amp, var, ctx.sps, ctx.M) if ctx.needs_input_grad[1] else None
+        return gx, gW, None, None, None, None
 
 
 def _fir_bwd(x, q, y, gq, gy, amp, var, sps, M):
@@ -46,8 +58,20 @@ def _fir_bwd(x, q, y, gq, gy, amp, var, sps, M):
     return gW
 
 
+def _fir_bwd_x(x, W, q, y, gq, gy, amp, var, sps, M):
+    dev, N = x.device, q.shape[-1]
+    gx = torch.empty(x.shape, dtype=torch.float32, device=dev)    # x holds whole symbols here (fir_demap pads inside the graph)
+    var2 = _f32(var, dev).reshape(1, 2).contiguous()
+    W, q, y = W.detach().to(torch.float32).contiguous(), q.contiguous(), y.contiguous()
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_dp_forward_bwd_x(1, N, sps, M, amp.numel(), nat.ptr(W), nat.ptr(q), nat.ptr(y), nat.ptr(gq), nat.ptr(gy),
+                                                  nat.ptr(amp), nat.ptr(var2), nat.ptr(gx), nat.current_stream(dev)), "vaeq_dp_forward_bwd_x")
+    return gx
+
+
 def fir_demap(x, W, amp_levels, var, nu_sc, sps):
-    """Differentiable twoXtwoFIR.forward: gradients flow to W (x is data)."""
+    """Differentiable twoXtwoFIR.forward: gradients flow to W and to x (the zero padding to whole symbols is part of the graph: the gradient
+    of the padded tail is dropped by its slice)."""
     amp = _f32(amp_levels, x.device).reshape(-1)
     var_t = _f32(var, x.device).reshape(2)
     return _FIRDemap.apply(pad_to_symbols(x, sps).contiguous(), W, amp, var_t, float(nu_sc), int(sps))
@@ -64,23 +88,30 @@ class _Loss(torch.autograd.Function):
         return loss, ve
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_loss, g_ve):
         q, rx, h, amp, P = ctx.saved_tensors
         dev, B = q.device, q.shape[-1]
         sps, M, n = rx.shape[-1] // B, h.shape[-1], amp.numel()
-        # the kernel writes row-major: allocate contiguous (empty_like would keep a permuted q's strides) and return in q's / h's shape
-        gq = torch.empty(q.shape, dtype=torch.float32, device=dev)
-        gh = torch.empty(h.shape, dtype=torch.float32, device=dev)
         up = g_loss.reshape(1).to(torch.float32).contiguous()
         qc, rxc, hc = q.contiguous(), rx.contiguous(), h.contiguous()   # locals: temporaries freed before the launch could alias
+        gq = gh = grx = None
         with torch.cuda.device(dev):
-            nat.check(nat.lib().vaeq_dp_loss_bwd(1, B, sps, M, n, nat.ptr(qc), nat.ptr(rxc), nat.ptr(hc), nat.ptr(amp), nat.ptr(P),
-                                                 nat.ptr(up), nat.ptr(gq), nat.ptr(gh), nat.current_stream(dev)), "vaeq_dp_loss_bwd")
-        return gq, None, gh, None, None
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+                # the kernel writes row-major: allocate contiguous (empty_like would keep a permuted q's strides) and return in q's / h's shape
+                gq = torch.empty(q.shape, dtype=torch.float32, device=dev)
+                gh = torch.empty(h.shape, dtype=torch.float32, device=dev)
+                nat.check(nat.lib().vaeq_dp_loss_bwd(1, B, sps, M, n, nat.ptr(qc), nat.ptr(rxc), nat.ptr(hc), nat.ptr(amp), nat.ptr(P),
+                                                     nat.ptr(up), nat.ptr(gq), nat.ptr(gh), nat.current_stream(dev)), "vaeq_dp_loss_bwd")
+            if ctx.needs_input_grad[1]:
+                grx = torch.empty(rx.shape, dtype=torch.float32, device=dev)
+                nat.check(nat.lib().vaeq_dp_loss_bwd_x(1, B, sps, M, n, nat.ptr(qc), nat.ptr(rxc), nat.ptr(hc), nat.ptr(amp), nat.ptr(up),
+                                                       nat.ptr(grx), nat.current_stream(dev)), "vaeq_dp_loss_bwd_x")
+        return gq, grx, gh, None, None
 
 
 def elbo_loss(q, rx, h_est, amp_levels, P):
-    """Differentiable loss_function_shaping: gradients flow to q and h_est."""
+    """Differentiable loss_function_shaping: gradients flow to q, h_est and rx."""
     dev = q.device
     amp = _f32(amp_levels, dev).reshape(-1)
     Pt = _f32(P, dev).reshape(1, -1).contiguous()
@@ -103,21 +134,27 @@ class _AwgnFIRDemap(torch.autograd.Function):
         return q[0], y[0]
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gq, gy):
         x, W, amp, amp_mean, var = ctx.saved_tensors
         dev, N, M = x.device, gq.shape[-1], W.shape[-1]
-        gW = torch.empty(1, 2, M, dtype=torch.float32, device=dev)
         x, gq = x.contiguous(), gq.contiguous()
         gy = gy.contiguous() if gy is not None else None
+        gx = gW = None
         with torch.cuda.device(dev):
-            nat.check(nat.lib().vaeq_awgn_forward_bwd(1, N, ctx.sps, M, amp.numel(), nat.ptr(x), nat.ptr(W), nat.ptr(amp), nat.ptr(amp_mean),
-                                                      nat.ptr(var), nat.ptr(gq), nat.ptr(gy), nat.ptr(gW), nat.current_stream(dev)),
-                      "vaeq_awgn_forward_bwd")
-        return None, gW.reshape(ctx.wshape), None, None, None, None
+            args = (1, N, ctx.sps, M, amp.numel(), nat.ptr(x), nat.ptr(W), nat.ptr(amp), nat.ptr(amp_mean), nat.ptr(var), nat.ptr(gq), nat.ptr(gy))
+            if ctx.needs_input_grad[0]:
+                gx = torch.empty(x.shape, dtype=torch.float32, device=dev)
+                nat.check(nat.lib().vaeq_awgn_forward_bwd_x(*args, nat.ptr(gx), nat.current_stream(dev)), "vaeq_awgn_forward_bwd_x")
+            if ctx.needs_input_grad[1]:
+                gW = torch.empty(1, 2, M, dtype=torch.float32, device=dev)
+                nat.check(nat.lib().vaeq_awgn_forward_bwd(*args, nat.ptr(gW), nat.current_stream(dev)), "vaeq_awgn_forward_bwd")
+                gW = gW.reshape(ctx.wshape)
+        return gx, gW, None, None, None, None
 
 
 def awgn_fir_demap(x, W, amp_levels, amp_mean, var, sps):
-    """Differentiable twoFIR.forward: gradients flow to W (x is data)."""
+    """Differentiable twoFIR.forward: gradients flow to W and to x (the padding to whole symbols stays inside the graph)."""
     return _AwgnFIRDemap.apply(pad_to_symbols(x, sps).contiguous(), W, _f32(amp_levels, x.device).reshape(-1), float(amp_mean), float(var),
                                int(sps))
 
@@ -134,23 +171,32 @@ class _AwgnLoss(torch.autograd.Function):
         return awgn_loss(q.detach(), rx, h.detach(), amp, P)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         q, rx, h, amp, P = ctx.saved_tensors
         dev, B, M, n = q.device, q.shape[-1], h.shape[-1], amp.numel()
-        gq = torch.empty(1, 2 * n, B, dtype=torch.float32, device=dev)
-        gh = torch.empty(1, 2, M, dtype=torch.float32, device=dev)
+        sps = rx.shape[-1] // B
         Pt = P.reshape(1, n).contiguous() if ctx.has_P else None
         up = g.reshape(1).to(torch.float32).contiguous()
         qc, rxc, hc = q.contiguous(), rx.contiguous(), h.contiguous()   # locals: temporaries freed before the launch could alias
+        gq = gh = grx = None
         with torch.cuda.device(dev):
-            nat.check(nat.lib().vaeq_awgn_loss_bwd(1, B, rx.shape[-1] // B, M, n, nat.ptr(qc), nat.ptr(rxc), nat.ptr(hc), nat.ptr(amp),
-                                                   nat.ptr(Pt), nat.ptr(up), nat.ptr(gq), nat.ptr(gh), nat.current_stream(dev)),
-                      "vaeq_awgn_loss_bwd")
-        return gq[0], None, gh[0], None, None
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+                gq = torch.empty(1, 2 * n, B, dtype=torch.float32, device=dev)
+                gh = torch.empty(1, 2, M, dtype=torch.float32, device=dev)
+                nat.check(nat.lib().vaeq_awgn_loss_bwd(1, B, sps, M, n, nat.ptr(qc), nat.ptr(rxc), nat.ptr(hc), nat.ptr(amp),
+                                                       nat.ptr(Pt), nat.ptr(up), nat.ptr(gq), nat.ptr(gh), nat.current_stream(dev)),
+                          "vaeq_awgn_loss_bwd")
+                gq, gh = gq[0], gh[0]
+            if ctx.needs_input_grad[1]:
+                grx = torch.empty(rx.shape, dtype=torch.float32, device=dev)
+                nat.check(nat.lib().vaeq_awgn_loss_bwd_x(1, B, sps, M, n, nat.ptr(qc), nat.ptr(rxc), nat.ptr(hc), nat.ptr(amp), nat.ptr(up),
+                                                         nat.ptr(grx), nat.current_stream(dev)), "vaeq_awgn_loss_bwd_x")
+        return gq, grx, gh, None, None
 
 
 def awgn_elbo_loss(q, rx, h_est, amp_levels, P=None):
-    """Differentiable AWGN loss_function: gradients flow to q and h_est.  P None = the VAE-NN form (entropy instead of KL)."""
+    """Differentiable AWGN loss_function: gradients flow to q, h_est and rx.  P None = the VAE-NN form (entropy instead of KL)."""
     dev = q.device
     Pt = None if P is None else _f32(P, dev).reshape(-1).contiguous()
     return _AwgnLoss.apply(q, rx.contiguous().float(), h_est, _f32(amp_levels, dev).reshape(-1).contiguous(), Pt)
@@ -190,14 +236,18 @@ LAST_BACKWARD_KERNEL = None     # instantiation the latest encoder backward laun
                                 # vaeq_last_kernel answers per calling thread
 
 
-def _enc_backward(x, theta, q, gq, stats, dims, batch_norm, training):
+def _enc_backward(x, theta, q, gq, stats, dims, batch_norm, training, gx=None):
+    """-> dL/dtheta_net[R,NP].  gx[R,2,L] given: vaeq_nn_enc_backward_x fills it with dL/dx in the same pass."""
     global LAST_BACKWARD_KERNEL
     sps, n, k1, k2 = dims
     dev, (R, _, L) = x.device, x.shape
     g = torch.empty_like(theta)
     with torch.cuda.device(dev):
-        _enc_check(nat.lib().vaeq_nn_enc_backward(R, L, sps, n, k1, k2, int(batch_norm), int(training), nat.ptr(x), nat.ptr(theta), nat.ptr(q),
-                                                  nat.ptr(gq), nat.ptr(stats), nat.ptr(g), nat.current_stream(dev)), "vaeq_nn_enc_backward")
+        args = (R, L, sps, n, k1, k2, int(batch_norm), int(training), nat.ptr(x), nat.ptr(theta), nat.ptr(q), nat.ptr(gq), nat.ptr(stats), nat.ptr(g))
+        if gx is not None:
+            _enc_check(nat.lib().vaeq_nn_enc_backward_x(*args, nat.ptr(gx), nat.current_stream(dev)), "vaeq_nn_enc_backward_x")
+        else:
+            _enc_check(nat.lib().vaeq_nn_enc_backward(*args, nat.current_stream(dev)), "vaeq_nn_enc_backward")
     LAST_BACKWARD_KERNEL = nat.last_kernel()
     return g
 
@@ -216,34 +266,37 @@ class _NNEncode(torch.autograd.Function):
         return q
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gq):
         x, theta, q, stats = ctx.saved_tensors
         gq = gq.to(torch.float32).contiguous()                  # a local: lives until the launch is queued
-        g = _enc_backward(x, theta, q, gq, stats, ctx.dims, ctx.batch_norm, ctx.training)[0]
-        parts = torch.split(g, [int(torch.Size(s).numel()) for s in ctx.shapes])
+        gx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
+        g = _enc_backward(x, theta, q, gq, stats, ctx.dims, ctx.batch_norm, ctx.training, gx)
+        parts = torch.split(g[0], [int(torch.Size(s).numel()) for s in ctx.shapes])
         grads = tuple(p.reshape(s) if need else None for p, s, need in zip(parts, ctx.shapes, ctx.needs_input_grad[5:]))
-        return (None, None, None, None, None) + grads
+        return (gx, None, None, None, None) + grads
 
 
 def nn_encode(x, params, sps, batch_norm=False, training=False, running_mean=None, running_var=None):
     """Differentiable VAE-NN encoder: x[1,2,L] (or [2,L]) -> q[1,2n,ceil(L/sps)] (or [2n,N]); gradients flow to ``params`` =
-    (fc1.weight, fc1.bias, fc2.weight, fc2.bias[, batch1.weight, batch1.bias]); x is data.  batch_norm + training: batch statistics, and
+    (fc1.weight, fc1.bias, fc2.weight, fc2.bias[, batch1.weight, batch1.bias]) and, when it requires one, to x.  batch_norm + training: batch statistics, and
     running_mean / running_var (when given) move in place by momentum 0.1; batch_norm without training: they normalise.
-    With autograd off, or no parameter requiring a gradient, this is a plain kernel call."""
+    With autograd off, or neither x nor a parameter requiring a gradient, this is a plain kernel call."""
     params = tuple(params)
     dims = _enc_dims(params, sps, batch_norm)
     if x.dim() not in (2, 3) or x.shape[-2] != 2 or (x.dim() == 3 and x.shape[0] != 1) or x.shape[-1] < 1:
         raise ValueError(f"x must be [1, 2, L] or [2, L], got {tuple(x.shape)}")
     if not x.is_cuda:
         nat.ptr(x)                                              # raises: the kernels take device tensors (no CPU path)
-    xc = x.detach().to(torch.float32).reshape(1, 2, -1).contiguous()
+    graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+    xc = (x if graph and x.requires_grad else x.detach()).to(torch.float32).reshape(1, 2, -1).contiguous()
     bn = None
     if batch_norm:
         if (running_mean is None or running_var is None) and not training:
             raise ValueError("eval-mode BatchNorm needs running_mean and running_var")
         if running_mean is not None and running_var is not None:
             bn = torch.cat([running_mean.detach().reshape(-1), running_var.detach().reshape(-1)]).to(torch.float32).reshape(1, -1).contiguous()
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+    if graph:
         q = _NNEncode.apply(xc, dims, bool(batch_norm), bool(training), bn, *params)
     else:
         theta = torch.cat([p.detach().reshape(-1) for p in params]).to(torch.float32).reshape(1, -1).contiguous()

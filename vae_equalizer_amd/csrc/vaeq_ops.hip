@@ -1,6 +1,6 @@
 // vaeq_ops.hip -- the stand-alone (differentiable) operators of the drop-in surface, one workgroup per run unless noted:
-//   DP    soft_demap, dp_forward (inference-mode butterfly FIR), dp_loss, dp_loss_bwd, dp_forward_bwd
-//   AWGN  awgn_forward, awgn_loss, awgn_loss_bwd, awgn_forward_bwd
+//   DP    soft_demap, dp_forward (inference-mode butterfly FIR), dp_loss, dp_loss_bwd, dp_forward_bwd, and the input gradients dp_loss_bwd_x, dp_forward_bwd_x
+//   AWGN  awgn_forward, awgn_loss, awgn_loss_bwd, awgn_forward_bwd, and the input gradients awgn_loss_bwd_x, awgn_forward_bwd_x
 // so that a reference-style loop
 //     q, out = net(x, ...); loss, _ = loss_function_shaping(q, x, h_est, ...); loss.backward(); optimizer.step()
 // runs on HIP kernels through the torch.autograd.Function wrappers (vae_equalizer_amd/autograd_ops.py).  None of this is the training
@@ -275,6 +275,39 @@ __global__ __launch_bounds__(256) void dp_loss_bwd_kernel(int B, int sps, int M,
     }
 }
 
+// d loss / d x of loss_function_shaping (shared_funcs.py:92-137), times the upstream gradient g_up[run]: e = x - D enters C_chi as |e|^2, so
+// gx[chi][c][mh + t] = g_up (nm / C_chi) 2 e[chi][c][t] on the nm inner samples and exactly 0 on the mh samples at either end.
+template <int NLEV>
+__global__ __launch_bounds__(256) void dp_loss_bwd_x_kernel(int B, int sps, int M, const float *__restrict__ q, const float *__restrict__ x,
+                                                            const float *__restrict__ h, const float *__restrict__ amp_g,
+                                                            const float *__restrict__ g_up, float *__restrict__ gx)
+{
+    extern __shared__ float4 smem4[];
+    float *sm = reinterpret_cast<float *>(smem4);
+    const int run = blockIdx.x, tid = threadIdx.x;
+    const int L = B * sps, mh = M / 2, Mh = 2 * mh, nm = L - Mh;
+    float *mu = sm, *vr = mu + 4 * B, *es = vr + 4 * B, *hs = es + 4 * nm, *VS = hs + 8 * M, *red = VS + 2 * M;
+    float amp[NLEV], invP[NLEV];
+#pragma unroll
+    for (int i = 0; i < NLEV; i++) { amp[i] = amp_g[i]; invP[i] = 1.0f; }       // (the KL term does not depend on x)
+    const float *qr = q + (size_t)run * 4 * NLEV * B, *xr = x + (size_t)run * 4 * L;
+    for (int i = tid; i < 8 * M; i += 256) hs[i] = h[(size_t)run * 8 * M + i];
+    dp_moments<NLEV, false>(B, mh, qr, amp, invP, mu, vr);
+    __syncthreads();
+    float se0 = 0.f, se1 = 0.f;
+    dp_residual<true>(B, sps, M, xr, hs, mu, es, se0, se1);
+    dp_var_sums(B, sps, M, vr, VS);
+    block_reduce3<256>(se0, se1, 0.f, red);
+    float C0 = red[0], C1 = red[1];
+    dp_C(M, hs, VS, C0, C1);
+    const float up = g_up[run], gC0 = up * (float)nm / C0, gC1 = up * (float)nm / C1;
+    float *gxr = gx + (size_t)run * 4 * L;
+    for (int it = tid; it < 4 * L; it += 256) {
+        const int xc = it / L, s = it - xc * L, t = s - mh;
+        gxr[it] = (t >= 0 && t < nm) ? (xc >> 1 ? gC1 : gC0) * (2.0f * es[xc * nm + t]) : 0.f;
+    }
+}
+
 // d loss / d W of twoXtwoFIR.forward (shared_funcs.py:500-527) given d loss / d q and (optionally) d loss / d out.
 template <int NLEV>
 __global__ __launch_bounds__(256) void dp_forward_bwd_kernel(int N, int sps, int M, const float *__restrict__ x, const float *__restrict__ q,
@@ -314,6 +347,65 @@ __global__ __launch_bounds__(256) void dp_forward_bwd_kernel(int N, int sps, int
         }
         gW[(size_t)run * 8 * M + (o * 4 + p) * M + k] = ar;
         gW[(size_t)run * 8 * M + (o * 4 + 2 + p) * M + k] = ai;
+    }
+}
+
+// dL/dout of twoXtwoFIR.forward into gy[2][2][N] (LDS): softmin backward (:521-523) plus the upstream gradient on `out` (gy_in, nullable) -- the
+// first phase of dp_forward_bwd_kernel above, statement for statement (that kernel keeps it inline: moving it here changes its register
+// allocation, and its instruction stream is held fixed)
+template <int NLEV>
+__device__ __forceinline__ void dp_dy(int run, int N, const float *qr, const float *gqr, const float *yr,
+                                      const float *gy_in, const float (&amp)[NLEV], const float *var, float *gy)
+{
+    for (int it = threadIdx.x; it < 4 * N; it += 256) {
+        const int oc = it / N, n = it - oc * N, o = oc >> 1;
+        float qq[NLEV], dot = 0.f;
+#pragma unroll
+        for (int i = 0; i < NLEV; i++) { qq[i] = qr[((size_t)oc * NLEV + i) * N + n]; dot = fmaf(qq[i], gqr[((size_t)oc * NLEV + i) * N + n], dot); }
+        const float yy = yr[(size_t)oc * N + n], iv = 1.0f / var[run * 2 + o];
+        float g = gy_in ? gy_in[((size_t)run * 4 + oc) * N + n] : 0.f;
+#pragma unroll
+        for (int i = 0; i < NLEV; i++) g = fmaf(qq[i] * (gqr[((size_t)oc * NLEV + i) * N + n] - dot), -(yy - amp[i]) * iv, g);
+        gy[it] = g;
+    }
+}
+
+// d loss / d x of twoXtwoFIR.forward (shared_funcs.py:500-516), the transposed strided correlation in gather form:
+//   gx[p][s] = sum_o sum_{k : (s + mh - k) % sps == 0, n = (s + mh - k) / sps in [0, N)} conj(w[o][p][k]) dy[o][n]
+// one thread per (polarisation, sample); o ascending, then k ascending: a fixed order, no atomics.  gy[2][2][N] and the taps in LDS.
+template <int NLEV>
+__global__ __launch_bounds__(256) void dp_forward_bwd_x_kernel(int N, int sps, int M, const float *__restrict__ W, const float *__restrict__ q,
+                                                               const float *__restrict__ y, const float *__restrict__ gq, const float *__restrict__ gy_in,
+                                                               const float *__restrict__ amp_g, const float *__restrict__ var,
+                                                               float *__restrict__ gx)
+{
+    extern __shared__ float4 smem4[];
+    float *gy = reinterpret_cast<float *>(smem4), *Ws = gy + 4 * N;     // [2][2][N] | [2][4][M]
+    const int run = blockIdx.x, tid = threadIdx.x, L = N * sps, mh = M / 2;
+    float amp[NLEV];
+#pragma unroll
+    for (int i = 0; i < NLEV; i++) amp[i] = amp_g[i];
+    const float *qr = q + (size_t)run * 4 * NLEV * N, *gqr = gq + (size_t)run * 4 * NLEV * N, *yr = y + (size_t)run * 4 * N;
+    for (int i = tid; i < 8 * M; i += 256) Ws[i] = W[(size_t)run * 8 * M + i];
+    dp_dy<NLEV>(run, N, qr, gqr, yr, gy_in, amp, var, gy);
+    __syncthreads();
+    float *gxr = gx + (size_t)run * 4 * L;
+    for (int it = tid; it < 2 * L; it += 256) {
+        const int p = it / L, s = it - p * L, c = s + mh;
+        // the taps that reach a symbol: k = c (mod sps), c - (N - 1) sps <= k <= c (both bounds are congruent to c already)
+        const int klo = max(c % sps, c - (N - 1) * sps), khi = min(M - 1, c);
+        float ar = 0.f, ai = 0.f;
+        for (int o = 0; o < 2; o++) {
+            const float *wr = Ws + (o * 4 + p) * M, *wi = Ws + (o * 4 + 2 + p) * M;
+            const float *gI = gy + (o * 2 + 0) * N, *gQ = gI + N;
+            for (int k = klo, n = (c - klo) / sps; k <= khi; k += sps, n--) {
+                const float a_ = gI[n], b_ = gQ[n], c_ = wr[k], d_ = wi[k];
+                ar = fmaf(c_, a_, ar); ar = fmaf(d_, b_, ar);
+                ai = fmaf(c_, b_, ai); ai = fmaf(-d_, a_, ai);
+            }
+        }
+        gxr[(size_t)(p * 2 + 0) * L + s] = ar;
+        gxr[(size_t)(p * 2 + 1) * L + s] = ai;
     }
 }
 
@@ -534,6 +626,39 @@ __global__ __launch_bounds__(256) void awgn_loss_bwd_kernel(int B, int sps, int 
     }
 }
 
+// d loss / d x of the stand-alone AWGN ELBO: gx[c][mh + t] = g_up (nm / C) 2 e[c][t] on the nm inner samples, exactly 0 on the mh samples
+// at either end (the KL / entropy term does not depend on x, so P plays no part).
+template <int NLEV>
+__global__ __launch_bounds__(256) void awgn_loss_bwd_x_kernel(int B, int sps, int M, const float *__restrict__ q, const float *__restrict__ x,
+                                                              const float *__restrict__ h, const float *__restrict__ amp_g,
+                                                              const float *__restrict__ g_up, float *__restrict__ gx)
+{
+    extern __shared__ float4 smem4[];
+    float *sm = reinterpret_cast<float *>(smem4);
+    __shared__ float red[64];
+    __shared__ float hs[2 * 64], VS[64];
+    const int run = blockIdx.x, tid = threadIdx.x;
+    const int L = B * sps, mh = M / 2, Mh = 2 * mh, nm = L - Mh;
+    float *mu = sm, *vr = sm + 2 * B, *es = sm + 4 * B;       // es[2][nm]
+    float amp[NLEV], invP[NLEV];
+#pragma unroll
+    for (int i = 0; i < NLEV; i++) { amp[i] = amp_g[i]; invP[i] = 1.0f; }
+    for (int i = tid; i < 2 * M; i += 256) hs[i] = h[(size_t)run * 2 * M + i];
+    const float *qr = q + (size_t)run * 2 * NLEV * B, *x0 = x + (size_t)run * 2 * L, *x1 = x0 + L;
+    awgn_moments<NLEV, false>(B, mh, qr, amp, invP, mu, vr);
+    __syncthreads();
+    const float se = awgn_residual<true>(B, sps, M, x0, x1, hs, mu, es);
+    awgn_var_sums(B, sps, M, vr, VS);
+    block_reduce3<256>(se, 0.f, 0.f, red);
+    const float C = awgn_C(M, hs, VS, red[0]);
+    const float gC = g_up[run] * (float)nm / C;
+    float *gxr = gx + (size_t)run * 2 * L;
+    for (int it = tid; it < 2 * L; it += 256) {
+        const int c = it / L, s = it - c * L, t = s - mh;
+        gxr[it] = (t >= 0 && t < nm) ? gC * (2.0f * es[c * nm + t]) : 0.f;
+    }
+}
+
 // Backward of twoFIR.forward (func_VAELE_MQAM_shaping.py:214-231): upstream gq[R][2n][N] (and optionally gy on the un-normalised
 // output) -> gW[R][2][M].  Recomputes the forward (y, mean |y|, yhat, q), then softmax backward with dz_i/dyhat = -2 (yhat - a_i) / var,
 // the normalisation's Jacobian and the tap correlation.  One workgroup per run, y and dL/dy in LDS.
@@ -601,6 +726,90 @@ __global__ __launch_bounds__(256) void awgn_forward_bwd_kernel(int N, int sps, i
         }
         gW[(size_t)run * 2 * M + k] = g0;
         gW[(size_t)run * 2 * M + M + k] = g1;
+    }
+}
+
+// dL/dy of twoFIR.forward (func_VAELE_MQAM_shaping.py:214-231) -- everything awgn_forward_bwd_kernel above does before its tap correlation, statement
+// for statement (that kernel keeps it inline: its instruction stream is held fixed) -- into gys[2][N], with the forward's un-normalised y recomputed into ys[2][N] (both LDS): y, mean |y|, yhat, q again, then softmax backward
+// with dz_i/dyhat = -2 (yhat - a_i) / var, the normalisation's Jacobian (:228) and the upstream gradient gy_up (nullable) on `out`.
+// The caller puts a barrier between this and its reads of gys.
+template <int NLEV>
+__device__ __forceinline__ void awgn_dy(int run, int N, int sps, int M, const float *x0, const float *x1, const float *Ws,
+                                        float *red, const float *amp_g, const float *amp_mean,
+                                        const float *var, const float *gq, const float *gy_up, float *ys,
+                                        float *gys)
+{
+    const int tid = threadIdx.x;
+    float sa0 = 0.f, sa1 = 0.f;
+    awgn_fir_abs<int>(N, sps, M, x0, x1, Ws, ys, ys + N, sa0, sa1);
+    block_reduce3<256>(sa0, sa1, 0.f, red);
+    float amp[NLEV];
+#pragma unroll
+    for (int i = 0; i < NLEV; i++) amp[i] = amp_g[i];
+    const float A = amp_mean[run], ivar = 1.0f / var[run];
+    const float m0 = red[0] / (float)N, m1 = red[1] / (float)N;
+    __syncthreads();
+    const float *gqr = gq + (size_t)run * 2 * NLEV * N;
+    float dt0 = 0.f, dt1 = 0.f;
+    for (int it = tid; it < 2 * N; it += 256) {
+        const int c = it / N, n = it - c * N;
+        const float yh = ys[it] / (c ? m1 : m0) * A;
+        float z[NLEV], zmax = -3.0e38f, ssum = 0.f, dot = 0.f, g = 0.f;
+#pragma unroll
+        for (int i = 0; i < NLEV; i++) { const float d = yh - amp[i]; z[i] = -(d * d * ivar); zmax = fmaxf(zmax, z[i]); }
+#pragma unroll
+        for (int i = 0; i < NLEV; i++) { z[i] = __expf(z[i] - zmax); ssum += z[i]; }
+#pragma unroll
+        for (int i = 0; i < NLEV; i++) { z[i] /= ssum; dot = fmaf(z[i], gqr[(size_t)(c * NLEV + i) * N + n], dot); }
+#pragma unroll
+        for (int i = 0; i < NLEV; i++) g = fmaf(z[i] * (gqr[(size_t)(c * NLEV + i) * N + n] - dot), -2.0f * (yh - amp[i]) * ivar, g);
+        gys[it] = g;                                           // dL/dyhat
+        if (c) dt1 = fmaf(g, ys[it], dt1); else dt0 = fmaf(g, ys[it], dt0);
+    }
+    block_reduce3<256>(dt0, dt1, 0.f, red);
+    {
+        const float s0_ = A / m0, s1_ = A / m1, k0_ = red[0] * A / (m0 * m0) / (float)N, k1_ = red[1] * A / (m1 * m1) / (float)N;
+        __syncthreads();
+        for (int n = tid; n < N; n += 256) {                   // normalisation backward (:228) + the upstream gradient on `out`
+            const float yI = ys[n], yQ = ys[N + n];
+            const float sgI = (float)(yI > 0.f) - (float)(yI < 0.f), sgQ = (float)(yQ > 0.f) - (float)(yQ < 0.f);
+            gys[n] = gys[n] * s0_ - k0_ * sgI + (gy_up ? gy_up[(size_t)run * 2 * N + n] : 0.f);
+            gys[N + n] = gys[N + n] * s1_ - k1_ * sgQ + (gy_up ? gy_up[(size_t)run * 2 * N + N + n] : 0.f);
+        }
+    }
+}
+
+// d loss / d x of twoFIR.forward: dL/dy (awgn_dy, normalisation Jacobian and gy_up included), then the transposed strided correlation in
+// gather form with w = W0 - j W1:  gx[s] = sum_{k : (s + pad - k) % sps == 0, n = (s + pad - k) / sps in [0, N)} conj(w[k]) dy[n],
+// one thread per sample, k ascending.
+template <int NLEV>
+__global__ __launch_bounds__(256) void awgn_forward_bwd_x_kernel(int N, int sps, int M, const float *__restrict__ x, const float *__restrict__ W,
+                                                                 const float *__restrict__ amp_g, const float *__restrict__ amp_mean,
+                                                                 const float *__restrict__ var, const float *__restrict__ gq,
+                                                                 const float *__restrict__ gy_up, float *__restrict__ gx)
+{
+    extern __shared__ float4 smem4[];
+    float *ys = reinterpret_cast<float *>(smem4), *gys = ys + 2 * N;
+    __shared__ float Ws[2 * 64];
+    __shared__ float red[64];
+    const int run = blockIdx.x, tid = threadIdx.x;
+    for (int i = tid; i < 2 * M; i += 256) Ws[i] = W[(size_t)run * 2 * M + i];
+    __syncthreads();
+    const int L = N * sps, pad = (M - 1) / 2;
+    const float *x0 = x + (size_t)run * 2 * L, *x1 = x0 + L;
+    awgn_dy<NLEV>(run, N, sps, M, x0, x1, Ws, red, amp_g, amp_mean, var, gq, gy_up, ys, gys);
+    __syncthreads();
+    float *gx0 = gx + (size_t)run * 2 * L, *gx1 = gx0 + L;
+    for (int s = tid; s < L; s += 256) {
+        const int c = s + pad, klo = max(c % sps, c - (N - 1) * sps), khi = min(M - 1, c);
+        float g0 = 0.f, g1 = 0.f;
+        for (int k = klo, n = (c - klo) / sps; k <= khi; k += sps, n--) {
+            const float a_ = gys[n], b_ = gys[N + n], c_ = Ws[k], d_ = Ws[M + k];
+            g0 = fmaf(c_, a_, g0); g0 = fmaf(-d_, b_, g0);     // yI = W0 x0 + W1 x1, yQ = W0 x1 - W1 x0
+            g1 = fmaf(d_, a_, g1); g1 = fmaf(c_, b_, g1);
+        }
+        gx0[s] = g0;
+        gx1[s] = g1;
     }
 }
 
@@ -732,5 +941,71 @@ extern "C" int vaeq_awgn_forward_bwd(int32_t R, int32_t N, int32_t sps, int32_t 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dispatch_nlev(n_lev, [&](auto nl) {
         return launch(vaeq::awgn_forward_bwd_kernel<decltype(nl)::value>, dim3(R), dim3(256), lds, st, N, sps, M, x, W, amp, amp_mean, var, gq, gy, gW);
+    });
+}
+
+// ---- input gradients (d/dx): the same checks as the sibling that yields the parameter gradients, and the instantiation reported to vaeq_last_kernel
+
+extern "C" int vaeq_dp_forward_bwd_x(int32_t R, int32_t N, int32_t sps, int32_t M, int32_t n_lev, const float *W, const float *q, const float *y,
+                                     const float *gq, const float *gy, const float *amp, const float *var, float *gx, void *stream)
+{
+    if (R == 0) return VAEQ_OK;
+    if (!W || !q || !y || !gq || !amp || !var || !gx) return VAEQ_ERR_NULL;
+    if (R < 0 || N <= 0 || !vaeq::fir_shape_ok(sps, M)) return VAEQ_ERR_SHAPE;
+    const size_t lds = sizeof(float) * ((size_t)4 * N + 8 * M);
+    if (lds > vaeq::LDS_MAX) return VAEQ_ERR_LDS;
+    if ((int64_t)N * sps > 0x1fffffff) return VAEQ_ERR_SHAPE;           // (4 N sps gradient samples are indexed in 32 bits)
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dispatch_nlev(n_lev, [&](auto nl) {
+        vaeq::note_kernel("vaeq::dp_forward_bwd_x_kernel<%d>", (int)decltype(nl)::value);
+        return launch(vaeq::dp_forward_bwd_x_kernel<decltype(nl)::value>, dim3(R), dim3(256), lds, st, N, sps, M, W, q, y, gq, gy, amp, var, gx);
+    });
+}
+
+extern "C" int vaeq_dp_loss_bwd_x(int32_t R, int32_t B, int32_t sps, int32_t M, int32_t n_lev, const float *q, const float *x, const float *h,
+                                  const float *amp, const float *g_up, float *gx, void *stream)
+{
+    if (R == 0) return VAEQ_OK;
+    if (!q || !x || !h || !amp || !g_up || !gx) return VAEQ_ERR_NULL;
+    if (R < 0 || !vaeq::loss_shape_ok(B, sps, M)) return VAEQ_ERR_SHAPE;
+    const size_t lds = sizeof(float) * (size_t)(8 * B + 4 * (B * sps - 2 * (M / 2)) + 10 * M + 64);
+    if (lds > vaeq::LDS_MAX) return VAEQ_ERR_LDS;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dispatch_nlev(n_lev, [&](auto nl) {
+        vaeq::note_kernel("vaeq::dp_loss_bwd_x_kernel<%d>", (int)decltype(nl)::value);
+        return launch(vaeq::dp_loss_bwd_x_kernel<decltype(nl)::value>, dim3(R), dim3(256), lds, st, B, sps, M, q, x, h, amp, g_up, gx);
+    });
+}
+
+extern "C" int vaeq_awgn_forward_bwd_x(int32_t R, int32_t N, int32_t sps, int32_t M, int32_t n_lev, const float *x, const float *W,
+                                       const float *amp, const float *amp_mean, const float *var, const float *gq, const float *gy, float *gx,
+                                       void *stream)
+{
+    if (R == 0) return VAEQ_OK;
+    if (!x || !W || !amp || !amp_mean || !var || !gq || !gx) return VAEQ_ERR_NULL;
+    if (R < 0 || N <= 0 || !vaeq::fir_shape_ok(sps, M)) return VAEQ_ERR_SHAPE;
+    const size_t lds = (size_t)4 * N * sizeof(float);
+    if (lds > vaeq::LDS_MAX_BESIDE_STATIC) return VAEQ_ERR_LDS;
+    if ((int64_t)N * sps > 0x3fffffff) return VAEQ_ERR_SHAPE;           // (2 N sps gradient samples are indexed in 32 bits)
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dispatch_nlev(n_lev, [&](auto nl) {
+        vaeq::note_kernel("vaeq::awgn_forward_bwd_x_kernel<%d>", (int)decltype(nl)::value);
+        return launch(vaeq::awgn_forward_bwd_x_kernel<decltype(nl)::value>, dim3(R), dim3(256), lds, st, N, sps, M, x, W, amp, amp_mean, var, gq, gy,
+                      gx);
+    });
+}
+
+extern "C" int vaeq_awgn_loss_bwd_x(int32_t R, int32_t B, int32_t sps, int32_t M, int32_t n_lev, const float *q, const float *x, const float *h,
+                                    const float *amp, const float *g_up, float *gx, void *stream)
+{
+    if (R == 0) return VAEQ_OK;
+    if (!q || !x || !h || !amp || !g_up || !gx) return VAEQ_ERR_NULL;
+    if (R < 0 || !vaeq::loss_shape_ok(B, sps, M)) return VAEQ_ERR_SHAPE;
+    const size_t lds = ((size_t)4 * B + 2 * ((size_t)B * sps - 2 * (M / 2))) * sizeof(float);
+    if (lds > vaeq::LDS_MAX_BESIDE_STATIC) return VAEQ_ERR_LDS;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dispatch_nlev(n_lev, [&](auto nl) {
+        vaeq::note_kernel("vaeq::awgn_loss_bwd_x_kernel<%d>", (int)decltype(nl)::value);
+        return launch(vaeq::awgn_loss_bwd_x_kernel<decltype(nl)::value>, dim3(R), dim3(256), lds, st, B, sps, M, q, x, h, amp, g_up, gx);
     });
 }

@@ -55,8 +55,8 @@ def generate_data(N, M, constellation, SNR, h_channel, sps, device, rng=None):
 
 
 def loss_function(q, rx, h, device, amp_levels):
-    """ELBO of one minibatch (:63-95): q[2n,B], rx[2,B*sps], h[2,M] (HIP: vaeq_awgn_loss with the entropy term; differentiable)."""
-    if torch.is_grad_enabled() and (q.requires_grad or h.requires_grad):
+    """ELBO of one minibatch (:63-95): q[2n,B], rx[2,B*sps], h[2,M] (HIP: vaeq_awgn_loss with the entropy term; differentiable in q, h and rx)."""
+    if torch.is_grad_enabled() and (q.requires_grad or h.requires_grad or rx.requires_grad):
         from .autograd_ops import awgn_elbo_loss
         return awgn_elbo_loss(q, rx, h, amp_levels, None)
     from .engine import awgn_loss
@@ -87,8 +87,8 @@ class _Encoder(nn.Module):
         return p + [self.batch1.weight, self.batch1.bias] if self._batch_norm else p
 
     def forward(self, x):
-        """x[1,2,L] -> netout[1,2 num_lev,ceil(L/sps)] float32.  With autograd on and a parameter requiring a gradient the result carries the
-        HIP-backed graph; self.training selects the BatchNorm mode, and a training-mode forward moves the running statistics (also under
+        """x[1,2,L] -> netout[1,2 num_lev,ceil(L/sps)] float32.  With autograd on and a parameter or x requiring a gradient the result carries the
+        HIP-backed graph (x then receives its gradient too: vaeq_nn_enc_backward_x); self.training selects the BatchNorm mode, and a training-mode forward moves the running statistics (also under
         no_grad, as PyTorch does).  CPU tensors are refused."""
         from .autograd_ops import nn_encode
         if x.dim() != 3 or x.shape[0] != 1 or x.shape[1] != 2:

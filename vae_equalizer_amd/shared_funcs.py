@@ -5,6 +5,8 @@ What runs where:
   * ``init``, ``generate_data_shaping``            -- host (numpy), like the reference;
   * ``twoXtwoFIR.forward``, ``soft_dec``           -- HIP kernels (vaeq_dp_forward / vaeq_soft_demap);
   * ``loss_function_shaping``                      -- HIP (the fused step kernel run with ``no_update``);
+  * their gradients under autograd                 -- HIP, for the parameters (vaeq_dp_forward_bwd, vaeq_dp_loss_bwd) and for the input
+    signal (vaeq_dp_forward_bwd_x, vaeq_dp_loss_bwd_x): see autograd_ops.fir_demap / elbo_loss;
   * ``find_shift*``, ``SER_*``                     -- torch ops on the tensors' device (epilogue.py);
   * training itself                                -- ``engine.DPEngine`` (the fused kernel); a
     ``net(...); loss.backward(); optimizer.step()`` loop written against these mirrors is NOT how the product trains.
@@ -68,7 +70,9 @@ class twoXtwoFIR(nn.Module):
     """Complex 2x2 butterfly FIR + per-axis soft demapper (shared_funcs.py:490-527).
 
     ``conv_w.weight`` keeps the reference's Conv1d(4,2,M) layout so checkpoints/state_dicts interchange.
-    forward() runs the HIP kernel (inference: no autograd graph is built; training goes through engine.DPEngine)."""
+    forward() runs the HIP kernel.  With autograd on and the weight OR the input requiring a gradient the result carries the HIP-backed
+    graph (gradients for both; a frozen equalizer behind a trainable front end works); otherwise no graph is built.  The product trains
+    through engine.DPEngine."""
 
     def __init__(self, M_est, sps):
         super().__init__()
@@ -77,8 +81,8 @@ class twoXtwoFIR(nn.Module):
         nn.init.dirac_(self.conv_w.weight)
 
     def forward(self, x, amp_levels, var, nu_sc):
-        if torch.is_grad_enabled() and self.conv_w.weight.requires_grad:
-            from .autograd_ops import fir_demap                  # HIP forward + HIP backward (vaeq_dp_forward / _bwd)
+        if torch.is_grad_enabled() and (self.conv_w.weight.requires_grad or x.requires_grad):
+            from .autograd_ops import fir_demap                  # HIP forward + HIP backward (vaeq_dp_forward / _bwd / _bwd_x)
             return fir_demap(x, self.conv_w.weight, amp_levels, var, nu_sc, self.sps)
         q, y = _engine.dp_forward(x, self.conv_w.weight.detach(), amp_levels, var, nu_sc, self.sps)
         return q, y
@@ -92,8 +96,9 @@ def soft_dec(out, var, amp_levels, nu_sc):
 def loss_function_shaping(q, rx, h_est, amp_levels, P):
     """ELBO of one minibatch (shared_funcs.py:92-137) -> (loss, var_est[2]); q[2,2n,B], rx[2,2,B*sps], h_est[2,2,2,M].
 
-    HIP kernels: vaeq_dp_loss (values) and, when q or h_est require grad, vaeq_dp_loss_bwd through autograd_ops.elbo_loss."""
-    if torch.is_grad_enabled() and (q.requires_grad or h_est.requires_grad):
+    HIP kernels: vaeq_dp_loss (values) and, when q, h_est or rx require grad, vaeq_dp_loss_bwd / vaeq_dp_loss_bwd_x through
+    autograd_ops.elbo_loss."""
+    if torch.is_grad_enabled() and (q.requires_grad or h_est.requires_grad or rx.requires_grad):
         from .autograd_ops import elbo_loss
         return elbo_loss(q, rx, h_est, amp_levels, P)
     return _engine.dp_loss(q, rx, h_est.detach(), amp_levels, P)
