@@ -64,8 +64,51 @@
 #ifndef VAEQ_WPS
 #define VAEQ_WPS 2                                     // workgroups per SIMD the register budget is sized for (3 would need <= 168 VGPRs: it spills)
 #endif
+#ifndef VAEQ_CHAIN_BOUND
+#define VAEQ_CHAIN_BOUND 0                             // 1: TIMING ONLY, RESULTS ARE WRONG -- the serial stretches between the tap loops cut short (a constant for every wave sum,
+                                                       // the lane's own value for every scan and for the dL/dh half exchange, Adam without arithmetic but with its LDS traffic, VS /
+                                                       // C / bias corrections as constants): what hiding them behind the tap loops could reach at most (profiles/r04/kernel_variants_ab.txt)
+#endif
+#ifndef VAEQ_HALF_SWAP
+#define VAEQ_HALF_SWAP 1                               // the cross-half exchange of the two tap gradients as v_permlane32_swap (one swap + one add per kept value) instead of
+                                                       // 16 ds_bpermute_b32 through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms
+                                                       // (+2.2 %, profiles/r04/kernel_variants_ab.txt).  Applied to the baked B = 100 kernels only (SWAPH below); 0: A/B knob
+#endif
 
 namespace vaeq {
+
+// The serial stretches between the tap loops, as the kernel calls them (VAEQ_CHAIN_BOUND = 0: the plain operations).
+#if VAEQ_CHAIN_BOUND
+__device__ __forceinline__ float chain_sum(float v) { asm volatile("" :: "v"(v)); return 1.0f; }
+__device__ __forceinline__ float chain_scan(float v) { return v; }
+__device__ __forceinline__ float chain_half_scan(float v) { return v; }
+__device__ __forceinline__ float chain_rcp(float v) { asm volatile("" :: "v"(v)); return 1.0f; }
+__device__ __forceinline__ float chain_log(float v) { asm volatile("" :: "v"(v)); return 1.0f; }
+__device__ __forceinline__ void chain_adam(float &, float &m, float &v, float g, float, float) { m = g; v = g; }
+#define VAEQ_CUT(real, cut) (cut)
+#else
+#define VAEQ_CUT(real, cut) (real)
+__device__ __forceinline__ float chain_sum(float v) { return wave_sum_dpp(v); }
+__device__ __forceinline__ float chain_scan(float v) { return wave_incl_scan_dpp(v); }
+__device__ __forceinline__ float chain_half_scan(float v) { return half_incl_scan_dpp(v); }
+__device__ __forceinline__ float chain_rcp(float v) { return __builtin_amdgcn_rcpf(v); }
+__device__ __forceinline__ float chain_log(float v) { return __builtin_amdgcn_logf(v); }
+__device__ __forceinline__ void chain_adam(float &p, float &m, float &v, float g, float ss, float bc) { adam_update_fast(p, m, v, g, ss, bc); }
+#endif
+
+// Sum of a tap-gradient component over the two 32-lane halves, for the half that keeps it: a0 belongs to the taps the lower half owns, a1 to the upper
+// half's; returns a0[lane] + a0[lane ^ 32] in the lower and a1[lane] + a1[lane ^ 32] in the upper half (in either form the lane's own part is one addend and
+// its partner's the other: IEEE addition commutes, the sums are bitwise the same).  DH: the exchange belongs to the dL/dh stretch (VAEQ_CHAIN_BOUND).
+template <bool DH>
+__device__ __forceinline__ float half_sum(float a0, float a1, int half)
+{
+#if VAEQ_CHAIN_BOUND
+    if constexpr (DH) return half ? a1 : a0;
+#endif
+    // swap a0's upper half with a1's lower half: the lower lanes then hold (a0 own, a0 partner), the upper lanes (a1 partner, a1 own)
+    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a0), __builtin_bit_cast(unsigned, a1), false, false);
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+}
 
 struct WaveLayout {
     int Lph, Uph;                                      // float2 per polyphase component of x/e and of mu
@@ -231,6 +274,9 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     constexpr bool FIXL = BT > 0 || (BL > 0 && M != 13 && M != 17 && !(M == 31 && NW == 1));
     constexpr bool PIPE = VAEQ_PIPE && FIXL;               // run-time layouts keep more addresses live: there one operand set,
     constexpr bool WIDE = FIXL;                            // ... 8 accumulator chains and one chi at a time in dL/dU (fits the register file)
+    // the halves of the two tap gradients meet on the vector ALU (half_sum): the baked B = 100 kernels, where it is measured and its bits are pinned
+    // (tests/test_dp_wave_bits_gpu.py); every other instantiation keeps the shuffles, instruction for instruction
+    constexpr bool SWAPH = VAEQ_HALF_SWAP && BT == 100 && NW == 1;
     constexpr bool PIPE_DU = VAEQ_PIPE_DU;                 // dL/dU runs at the kernel's register peak (moments of the demapper still live): no second operand set there
     const int B = BT ? BT : a.B;
     const int BS = BT ? BT : BL ? BL : B;                      // the minibatch length the LDS layout (offsets, row strides) is made for
@@ -551,7 +597,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             {
                 float inc[2];
 #pragma unroll
-                for (int o = 0; o < 2; o++) inc[o] = wave_incl_scan_dpp(vv[o][0] + vv[o][1]);
+                for (int o = 0; o < 2; o++) inc[o] = chain_scan(vv[o][0] + vv[o][1]);
                 if constexpr (NW > 1) {                        // add the totals of the waves below (fixed order)
                     if (lane == 63) { RED[wv] = inc[0]; RED[NW + wv] = inc[1]; }
                     sync_lds<NW>();
@@ -571,7 +617,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             sync_lds<NW>();
             if (owner) {                                       // VS[nu][j]: lane = (j = tk, nu = half)
                 const int lo = (Mh - tk + 1) >> 1, hi_ = (nm - 1 + Mh - tk) >> 1;
-                VS[half * M + tk] = PSv[half * (BS + 1) + hi_ + 1] - PSv[half * (BS + 1) + lo];
+                VS[half * M + tk] = VAEQ_CUT(PSv[half * (BS + 1) + hi_ + 1] - PSv[half * (BS + 1) + lo], 1.0f);
             }
             sync_lds<NW>();
 
@@ -586,7 +632,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 hq0 = h0.x * h0.x + h0.y * h0.y;
                 hq1 = h1.x * h1.x + h1.y * h1.y;
             }
-            const float vsl = worker ? VS[half * M + tk] : 0.f;
+            const float vsl = worker ? VAEQ_CUT(VS[half * M + tk], 1.0f) : 0.f;
             {
                 cacc D[2][4];                                  // [chi][i], i = 2*dl + par; lanes without a quad shadow lane 0 (no divergence, unused)
                 constexpr int NA = mh + 1, NB = NA / 2;        // a = 0..mh; pairs (2b, 2b+1)
@@ -647,9 +693,9 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         }
                 }
             }
-            se0 = wave_sum_dpp(se0);
-            se1 = wave_sum_dpp(se1);
-            klsum = wave_sum_dpp(klsum);
+            se0 = chain_sum(se0);
+            se1 = chain_sum(se1);
+            klsum = chain_sum(klsum);
             if constexpr (NW > 1) {                            // totals over the run's waves, same order in every wave
                 if (lane == 0) { RED[16 + wv] = se0; RED[16 + NW + wv] = se1; RED[16 + 2 * NW + wv] = klsum; }
                 sync_lds<NW>();
@@ -658,13 +704,13 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 for (int w = 1; w < NW; w++) { se0 += RED[16 + w]; se1 += RED[16 + NW + w]; klsum += RED[16 + 2 * NW + w]; }
             }
             // C[chi] = sum|e|^2 + sum_{nu,j} |h|^2 VS   (lanes (j, nu) hold one term each for both chi; hq, vsl were read before the D loop)
-            const float C0 = se0 + wave_sum_dpp(hq0 * vsl), C1 = se1 + wave_sum_dpp(hq1 * vsl);
+            const float C0 = se0 + chain_sum(hq0 * vsl), C1 = se1 + chain_sum(hq1 * vsl);
             // C is uniform: hardware reciprocal / log2 (1 ulp: 6e-8 on the gradients' common scale, 1e-7 relative on the ELBO) instead of the IEEE
             // division and logf expansions (~60 instructions per step that every lane would execute for lane 0's two stores)
-            const float gC0 = (float)nm * __builtin_amdgcn_rcpf(C0), gC1 = (float)nm * __builtin_amdgcn_rcpf(C1);
+            const float gC0 = (float)nm * chain_rcp(C0), gC1 = (float)nm * chain_rcp(C1);
             {
                 const uint32_t vo = gl == 0 ? 0u : OOB;        // lane 0 stores; row offsets ride in the scalar offset
-                if (a.loss) bst32((float)nm * LN2 * (__builtin_amdgcn_logf(C0) + __builtin_amdgcn_logf(C1)) + klsum, lr_, vo, (uint32_t)s * 4u);
+                if (a.loss) bst32((float)nm * LN2 * (chain_log(C0) + chain_log(C1)) + klsum, lr_, vo, (uint32_t)s * 4u);
                 if (a.var_est) {
                     bst32(C0 * rnm, vr_, vo, (uint32_t)s * 4u);
                     bst32(C1 * rnm, vr_, vo, ((uint32_t)a.steps + (uint32_t)s) * 4u);
@@ -672,7 +718,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             }
             // prefix sums over j of H2[nu][j] = sum_chi gC[chi] |h[chi,nu,j]|^2  -> G_V by two lookups per symbol
             {
-                const float inc = half_incl_scan_dpp(gC0 * hq0 + gC1 * hq1);   // inclusive scan within each 32-lane half
+                const float inc = chain_half_scan(gC0 * hq0 + gC1 * hq1);   // inclusive scan within each 32-lane half
                 if (owner) PSh[half * MP + tk + 1] = inc;
                 if (tk == 0) PSh[half * MP] = 0.f;
             }
@@ -683,8 +729,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             step += 1;
             b1t *= 0.9;
             b2t *= 0.999;
-            const float rbc1 = __builtin_amdgcn_rcpf((float)(1.0 - b1t));                 // bias corrections: beta^t in double,
-            const float bc2s = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf((float)(1.0 - b2t)));   // the rest in float
+            const float rbc1 = VAEQ_CUT(__builtin_amdgcn_rcpf((float)(1.0 - b1t)), 1.0f);                 // bias corrections: beta^t in double,
+            const float bc2s = VAEQ_CUT(__builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf((float)(1.0 - b2t))), 1.0f);   // the rest in float
             const float ssW = lrW * rbc1, ssH = lrH * rbc1;
             float2 hnew[2];
             hnew[0] = hnew[1] = make_float2(0.f, 0.f);
@@ -699,7 +745,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 #pragma unroll
                     for (int v = 0; v < 2; v++) {
                         ph_h[v] = Ht[(half * 2 + v) * MP + tk];
-                        ph_vs[v] = VS[v * M + tk];
+                        ph_vs[v] = VAEQ_CUT(VS[v * M + tk], 1.0f);
                     }
                 }
                 cacc ca[2][2];
@@ -757,13 +803,21 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 #pragma unroll
                     for (int v = 0; v < 2; v++) acc[chi][v] = cfinc(ca[chi][v]);             // e * conj(U)
                 // combine the two halves; lane (j, half) keeps chi = half
+                if constexpr (SWAPH || VAEQ_CHAIN_BOUND) {
 #pragma unroll
-                for (int chi = 0; chi < 2; chi++)
-#pragma unroll
-                    for (int v = 0; v < 2; v++) {
-                        acc[chi][v].x += __shfl_xor(acc[chi][v].x, 32, 64);
-                        acc[chi][v].y += __shfl_xor(acc[chi][v].y, 32, 64);
+                    for (int v = 0; v < 2; v++) {               // (both entries get the kept sum: the selects below pick either)
+                        acc[0][v].x = acc[1][v].x = half_sum<true>(acc[0][v].x, acc[1][v].x, half);
+                        acc[0][v].y = acc[1][v].y = half_sum<true>(acc[0][v].y, acc[1][v].y, half);
                     }
+                } else {
+#pragma unroll
+                    for (int chi = 0; chi < 2; chi++)
+#pragma unroll
+                        for (int v = 0; v < 2; v++) {
+                            acc[chi][v].x += __shfl_xor(acc[chi][v].x, 32, 64);
+                            acc[chi][v].y += __shfl_xor(acc[chi][v].y, 32, 64);
+                        }
+                }
                 if constexpr (NW > 1) {                        // waves 1.. hand their partial sums to wave 0 (read after the next barrier)
 #pragma unroll
                     for (int v = 0; v < 2; v++) {
@@ -786,8 +840,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         ghi[v] = g * (-2.0f * ac.y + 2.0f * hh.y * vs);
                         hnew[v] = hh;
                         if (!a.no_update) {
-                            adam_update_fast(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
-                            adam_update_fast(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
+                            chain_adam(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
+                            chain_adam(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
                         }
                     }
                 }
@@ -849,8 +903,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         ghi[v] = g * (-2.0f * ac.y + 2.0f * hh.y * vs);
                         hnew[v] = hh;
                         if (!a.no_update) {
-                            adam_update_fast(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
-                            adam_update_fast(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
+                            chain_adam(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
+                            chain_adam(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
                         }
                     }
                 }
@@ -932,13 +986,21 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 for (int o = 0; o < 2; o++)
 #pragma unroll
                     for (int pp = 0; pp < 2; pp++) acc[o][pp] = cfinc(ca[o][pp]);            // gy * conj(x)
+                if constexpr (SWAPH) {
 #pragma unroll
-                for (int o = 0; o < 2; o++)
-#pragma unroll
-                    for (int p = 0; p < 2; p++) {
-                        acc[o][p].x += __shfl_xor(acc[o][p].x, 32, 64);
-                        acc[o][p].y += __shfl_xor(acc[o][p].y, 32, 64);
+                    for (int p = 0; p < 2; p++) {               // lane (k, half) keeps o = half (see dL/dh)
+                        acc[0][p].x = acc[1][p].x = half_sum<false>(acc[0][p].x, acc[1][p].x, half);
+                        acc[0][p].y = acc[1][p].y = half_sum<false>(acc[0][p].y, acc[1][p].y, half);
                     }
+                } else {
+#pragma unroll
+                    for (int o = 0; o < 2; o++)
+#pragma unroll
+                        for (int p = 0; p < 2; p++) {
+                            acc[o][p].x += __shfl_xor(acc[o][p].x, 32, 64);
+                            acc[o][p].y += __shfl_xor(acc[o][p].y, 32, 64);
+                        }
+                }
                 if constexpr (NW > 1) {                        // as for dL/dh: wave 0 adds the other waves' parts after the barrier
 #pragma unroll
                     for (int p = 0; p < 2; p++) {
@@ -967,8 +1029,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         if (!a.no_update) {
                             float *wq = reinterpret_cast<float *>(&Wt[p * M + tk]) + half * 2;
                             float wr = pw_w[p][0], wi = pw_w[p][1];
-                            adam_update_fast(wr, pw_m[p][0], pw_v[p][0], gwr[p], ssW, bc2s);
-                            adam_update_fast(wi, pw_m[p][1], pw_v[p][1], gwi[p], ssW, bc2s);
+                            chain_adam(wr, pw_m[p][0], pw_v[p][0], gwr[p], ssW, bc2s);
+                            chain_adam(wi, pw_m[p][1], pw_v[p][1], gwi[p], ssW, bc2s);
                             wq[0] = wr;
                             wq[1] = wi;
                             mWr(p) = pw_m[p][0]; mWi(p) = pw_m[p][1];
