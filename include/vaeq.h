@@ -459,7 +459,7 @@ const char *vaeq_strerror(int code);
 
 /* Measurement helpers (no reference counterpart; SURVEY 8d asks for them).
  * vaeq_last_kernel: name of the kernel instantiation the calling thread's most recent vaeq_dp_train / vaeq_awgn_train / vaeq_cma / vaeq_cpe /
- * vaeq_nn_train / vaeq_nn_forward / vaeq_nn_validate / vaeq_nn_enc_forward / vaeq_nn_enc_backward / any *_bwd_x / vaeq_nn_enc_backward_x launched (as a profiler prints it, e.g. "vaeq::dp_wave_kernel<25, 8, 100, true, 1, 1>" or "vaeq::cma_kernel<true, false>"), copied into
+ * vaeq_nn_train / vaeq_nn_forward / vaeq_nn_validate / vaeq_nn_enc_forward / vaeq_nn_enc_backward / any *_bwd_x / vaeq_nn_enc_backward_x launched (as a profiler prints it, e.g. "vaeq::dp_wave_kernel<25, 8, 100, true, 1, 1, 0>" or "vaeq::cma_kernel<true, false>"), copied into
  * buf[len] -- bench.py names its roofline kernel from this, the tests check which vaeq_cma instantiation a shape reaches.
  * vaeq_stream_copy: dst[bytes] = src[bytes] with a plain 16-byte grid-stride copy kernel (bytes and both pointers multiples of 16): the
  * measured HBM copy bandwidth that stands next to the 8 TB/s spec peak in the roofline. */

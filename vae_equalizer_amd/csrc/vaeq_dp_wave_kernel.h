@@ -74,6 +74,22 @@
                                                        // 16 ds_bpermute_b32 through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms
                                                        // (+2.2 %, profiles/r04/kernel_variants_ab.txt).  Applied to the baked B = 100 kernels only (SWAPH below); 0: A/B knob
 #endif
+// The q stores of a step and what they cost beyond their bytes (profiles/r05/):
+#ifndef VAEQ_QST_OFF
+#define VAEQ_QST_OFF 0                                 // 1: TIMING ONLY, q IS NOT WRITTEN -- the q stores compiled out, everything else textually the same: what the 32 stores
+                                                       // of a step cost in total (profiles/r05/q_store_bound.txt)
+#endif
+#ifndef VAEQ_QST_NOWAIT
+#define VAEQ_QST_NOWAIT 1                              // the next window's prefetch is issued without a branch around it (the launch's very last step fetches with every lane out of
+                                                       // range: zeros, no memory access).  Behind the branch the four loads fed a phi: the backend copied their results right
+                                                       // after the issue, behind s_waitcnt vmcnt(3..0) -- every step stood there for the loads' HBM latency and, vmcnt retiring in
+                                                       // order, for every q / y store still in flight.  Now the first wait for them is P0 of the next step.  Applied to the baked
+                                                       // B = 100 kernels only (PFLAT below); 0: A/B knob
+#endif
+#ifndef VAEQ_QST_NT
+#define VAEQ_QST_NT 1                                  // the q stores leave with the streaming ("nt") cache policy: 32 rows x 400 B per wave-step that nothing reads back before the
+                                                       // launch ends.  Same gate as VAEQ_QST_NOWAIT (QAUX below); 0: A/B knob.  Numbers for both: profiles/r05/kernel_variants_ab.txt
+#endif
 
 namespace vaeq {
 
@@ -277,6 +293,9 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     // the halves of the two tap gradients meet on the vector ALU (half_sum): the baked B = 100 kernels, where it is measured and its bits are pinned
     // (tests/test_dp_wave_bits_gpu.py); every other instantiation keeps the shuffles, instruction for instruction
     constexpr bool SWAPH = VAEQ_HALF_SWAP && BT == 100 && NW == 1;
+    // the window prefetch without a branch (VAEQ_QST_NOWAIT): the baked B = 100 kernels, like SWAPH
+    constexpr bool PFLAT = VAEQ_QST_NOWAIT && BT == 100 && NW == 1;
+    constexpr int QAUX = VAEQ_QST_NT && BT == 100 && NW == 1 ? 2 : 0;   // cache policy of the q stores
     constexpr bool PIPE_DU = VAEQ_PIPE_DU;                 // dL/dU runs at the kernel's register peak (moments of the demapper still live): no second operand set there
     const int B = BT ? BT : a.B;
     const int BS = BT ? BT : BL ? BL : B;                      // the minibatch length the LDS layout (offsets, row strides) is made for
@@ -387,7 +406,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             b2t = BTW[1][f];                                    // (dp_runs.run_dp_batch groups the frames of small sweeps)
         }
         // one buffer descriptor per output array and frame; rows are addressed by scalar offsets (row * No4) folded into the stores
-        const bool qf = OUT != 2 && a.q_out, yf = a.y_out, ef = OUT != 1 && a.eq_out, df = OUT != 1 && a.dec_out;
+        const bool qf = !VAEQ_QST_OFF && OUT != 2 && a.q_out, yf = a.y_out, ef = OUT != 1 && a.eq_out, df = OUT != 1 && a.dec_out;
         const uint32_t No4 = (uint32_t)No * 4u;
         const size_t fr = (size_t)run * a.n_frames + f;
         const __amdgpu_buffer_rsrc_t qr = make_rsrc(qf ? a.q_out + fr * (4 * NLEV) * No : nullptr, qf ? 4u * NLEV * No4 : 0u);
@@ -576,8 +595,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 #else
                             const uint32_t ro = (uint32_t)(o * 2 * NLEV + c * NLEV + i) * No4;
 #endif
-                            if (pairst) bst64(q[i], qr, vo0, ro);
-                            else { bst32(q[i].x, qr, vo0, ro); bst32(q[i].y, qr, vo1, ro); }
+                            if (pairst) bst64<QAUX>(q[i], qr, vo0, ro);
+                            else { bst32<QAUX>(q[i].x, qr, vo0, ro); bst32<QAUX>(q[i].y, qr, vo1, ro); }
 #if VAEQ_ROW_STEP
                             qrow += No4;
                             asm volatile("" : "+s"(qrow));     // keeps it a running value (the optimiser would turn it back into products)
@@ -853,7 +872,12 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             // for these loads at the top of the next step does not also wait for fresh stores (vmcnt retires in order)
             {
                 const bool last_s = s + 1 == a.steps;
-                if (!(last_s && f + 1 == a.n_frames)) fetch(last_s ? xn : xr, last_s ? 0 : s + 1);
+                if constexpr (PFLAT) {                         // no branch: the loads' results are not copied (and waited for) here
+                    const bool more = !(last_s && f + 1 == a.n_frames);
+                    const uint32_t vo = ldl && more ? ((uint32_t)(last_s ? 0 : s + 1) * (uint32_t)a.stride_sym * 2u + 4u * gl) * 4u : OOB;   // the launch's last step: nothing is read
+#pragma unroll
+                    for (int r = 0; r < 4; r++) pf[r] = bld128(last_s ? xn : xr, vo, (uint32_t)r * S4);
+                } else if (!(last_s && f + 1 == a.n_frames)) fetch(last_s ? xn : xr, last_s ? 0 : s + 1);
             }
             VAEQ_XSTAMP(3);
             VAEQ_STAMP(8);

@@ -106,13 +106,16 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, uint3
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);   // raw buffer, gfx9 dword 3
 }
+// AUX = the store's cache policy bits (gfx950: 1 = sc0, 2 = nt, 16 = sc1; 0 = the default policy)
+template <int AUX = 0>
 __device__ __forceinline__ void bst64(v2f v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff)
 {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)voff, (int)soff, 0);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)voff, (int)soff, AUX);
 }
+template <int AUX = 0>
 __device__ __forceinline__ void bst32(float v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff)
 {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), r, (int)voff, (int)soff, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), r, (int)voff, (int)soff, AUX);
 }
 __device__ __forceinline__ void bst16(unsigned short v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff)
 {
