@@ -240,7 +240,12 @@ int vaeq_awgn_forward(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_le
  *   or func_VAEflex_DP_MQAM_shaping.py:72-84 (batch_len = 0: no per-minibatch cut).
  * q[R][2][2*n_lev][N] (out_train), y[R][2][2][N] (out_const), tx_f16[R][2][2][N] IEEE half (data_tensor, shared_funcs.py:89),
  * var[R][2], nu_sc[R] -> ser[R][4] (rows: constellation x, y; soft demapper x, y), shift[R][2 path][2] (path 0 = q, 1 = y),
- * rflag[R][2].  workspace: vaeq_dp_epilogue_ws_bytes(R, N) bytes of device memory. */
+ * rflag[R][2].  workspace: vaeq_dp_epilogue_ws_bytes(R, N) bytes of device memory.
+ * The cuts are Python slices, as in the reference.  Of every minibatch [: batch_len - shift[0] - 10] is kept: all of it when that end is
+ * >= batch_len, nothing when it is 0, and batch_len + end symbols when it is NEGATIVE (batch_len < shift[0] + 10, so only for batch_len < 20),
+ * since a negative end counts from the minibatch's end.  Of the (N / batch_len) * kept symbols that remain, [11 : -11 - max|shift|] is kept.
+ * A path whose window is empty (N >= 43 does not exclude that when batch_len > 0) reports NaN in its two ser rows -- the mean of an
+ * empty slice -- never 0. */
 int vaeq_dp_epilogue(int32_t R, int64_t N, int32_t n_lev, int32_t batch_len, const float *q, const float *y, const void *tx_f16,
                      const float *amp, const float *var, const float *nu_sc, float *ser, int32_t *shift, int32_t *rflag,
                      void *workspace, void *stream);

@@ -184,12 +184,20 @@ __device__ __forceinline__ void epi_count_add(int *dst, int v)
     if ((threadIdx.x & 63) == 0) atomicAdd(dst, tot);
 }
 
+// symbols kept of every minibatch by the reference's slice [: batch_len - shift[0] - 10] (:73-77), with Python's slice semantics: an end past the
+// minibatch keeps all of it, an end of 0 keeps nothing, and a NEGATIVE end e (batch_len < shift[0] + 10, so only for batch_len < 20) counts from the
+// minibatch's end and keeps batch_len + e symbols (none when that is negative, too)
+__device__ __forceinline__ int epi_lk(int batch_len, int shift0)
+{
+    const int e = batch_len - shift0 - N_CUT;
+    return e < 0 ? max(batch_len + e, 0) : min(e, batch_len);
+}
+
 // symbols that survive the per-minibatch cut (:73-77) and the frame-edge slice (:79)
 __device__ __forceinline__ bool epi_keep(int n, int N, int batch_len, int shift0, int ms)
 {
     if (batch_len <= 0) return n >= EDGE && n < N - EDGE - ms;
-    int Lk = batch_len - shift0 - N_CUT;
-    Lk = Lk < 0 ? 0 : (Lk > batch_len ? batch_len : Lk);
+    const int Lk = epi_lk(batch_len, shift0);
     const int mb = n / batch_len, j = n - mb * batch_len, k = mb * Lk + j, K = (N / batch_len) * Lk;
     return j < Lk && k >= EDGE && k < K - EDGE - ms;
 }
@@ -202,8 +210,7 @@ struct KeepWalk {
     {
         Lk = K = mb = j = dq = dr = 0;
         if (batch_len > 0) {
-            Lk = batch_len - shift0 - N_CUT;
-            Lk = Lk < 0 ? 0 : (Lk > batch_len ? batch_len : Lk);
+            Lk = epi_lk(batch_len, shift0);
             K = (N / batch_len) * Lk;
             mb = n0 / batch_len; j = n0 - mb * batch_len;
             dq = EPI_NT / batch_len; dr = EPI_NT - dq * batch_len;
@@ -230,8 +237,7 @@ struct KeepWalk4 {
     {
         Lk = K = mb = j = dq = dr = 0;
         if (batch_len > 0) {
-            Lk = batch_len - shift0 - N_CUT;
-            Lk = Lk < 0 ? 0 : (Lk > batch_len ? batch_len : Lk);
+            Lk = epi_lk(batch_len, shift0);
             K = (N / batch_len) * Lk;
             mb = n0 / batch_len; j = n0 - mb * batch_len;
             dq = (4 * EPI_NT) / batch_len; dr = 4 * EPI_NT - dq * batch_len;
@@ -473,9 +479,10 @@ __global__ __launch_bounds__(EPI_NT, CMA ? EPI_WAVES_CMA : EPI_WAVES) void dp_ep
         epi_count_add(&sh.kept, kept);
         __syncthreads();
         if (tid < 2) {                                          // min over the 8 hypotheses (:221 / :264)
-            const float den = (float)max(sh.kept, 1);
+            const float den = (float)sh.kept;
             float best = 2.0f;
             for (int k = 0; k < 8; k++) best = fminf(best, (float)sh.cnt[k * 2 + tid] / den);
+            if (sh.kept == 0) best = NAN;                       // the mean of an empty slice: nothing kept is no measurement, not a perfect one
             ser[(size_t)run * 4 + (path == 0 ? 2 : 0) + tid] = best;       // rows 0-1 constellation, 2-3 soft demapper (:79,89)
         }
         if (CMA && path == 1) {
@@ -554,7 +561,7 @@ extern "C" int vaeq_dp_epilogue_compact(int32_t R, int64_t N, int32_t n_lev, int
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *tx = reinterpret_cast<const __half *>(tx_f16);
     // dp_epilogue_compact_kernel (vaeq_epilogue_lds.h): both correlations on one staged TX tile, branch-free walks, TX levels resident in LDS when the
-    // frame's packed rows fit beside the tiles (N <= ~60 000 symbols).  VAEQ_EPI_REREAD=1 keeps the re-reading dp_epilogue_kernel, VAEQ_EPI_NOTXC=1 the
+    // frame's packed rows fit beside the tiles (2 N bytes: N <= 12 712 symbols).  VAEQ_EPI_REREAD=1 keeps the re-reading dp_epilogue_kernel, VAEQ_EPI_NOTXC=1 the
     // new kernel without the TX level cache (A/B switches and cross-checks: all three agree bit for bit)
     const char *old_env = getenv("VAEQ_EPI_REREAD"), *notxc_env = getenv("VAEQ_EPI_NOTXC");
     if ((batch_len == 0 || batch_len >= 4) && !(old_env && old_env[0] == '1')) {

@@ -40,6 +40,8 @@ struct Epi2Shared {
     } u;
 };
 
+static_assert(sizeof(Epi2Shared) == 28768, "tests/_ref_epilogue.py (EPI2_SHARED_BYTES) derives the frame length of the LDS-residency switch from this size");
+
 constexpr int NIB_FRONT = 16, NIB_BACK = 24;  // pad nibbles around a row
 __host__ __device__ inline int nib_words(int N) { return (N + NIB_FRONT + NIB_BACK + 7) / 8; }   // u32 per row
 
@@ -551,9 +553,10 @@ __global__ __launch_bounds__(EPI_NT, 3) void dp_epilogue_compact_kernel(int N, i
         epi_count_add(&sh.kept, kept);
         __syncthreads();
         if (tid < 2) {                                          // min over the 8 hypotheses (:221 / :264)
-            const float den = (float)max(sh.kept, 1);
+            const float den = (float)sh.kept;
             float best = 2.0f;
             for (int k = 0; k < 8; k++) best = fminf(best, (float)sh.cnt[k * 2 + tid] / den);
+            if (sh.kept == 0) best = NAN;                       // the mean of an empty slice: nothing kept is no measurement, not a perfect one
             ser[(size_t)run * 4 + (path == 0 ? 2 : 0) + tid] = best;       // rows 0-1 constellation, 2-3 soft demapper (:79,89)
         }
         __syncthreads();

@@ -51,7 +51,8 @@ def _keep_mask(shift, N, batch_len, device):
     n = torch.arange(N, device=device).unsqueeze(0)
     if batch_len is None:                                                    # VAEflex: only [11 : -11-ms]
         return (n >= EDGE) & (n < (N - EDGE - ms).unsqueeze(1))
-    Lk = (batch_len - shift[:, 0] - N_CUT).clamp(0, batch_len).unsqueeze(1)  # kept per minibatch
+    e = batch_len - shift[:, 0] - N_CUT                                      # end of the slice [:e] of every minibatch, Python semantics:
+    Lk = torch.where(e < 0, (batch_len + e).clamp(min=0), e.clamp(max=batch_len)).unsqueeze(1)   # a negative end counts from the minibatch's end
     m, j = n // batch_len, n % batch_len
     k = m * Lk + j                                                           # rank in the compacted sequence
     K = (N // batch_len) * Lk
@@ -66,8 +67,8 @@ def _levels(tx, n_lev):
 
 
 def _masked_rate(err, mask):
-    """err[R,2,N] bool, mask[R,N] -> error rate per (run, pol) over the kept symbols."""
-    cnt = mask.sum(dim=1).clamp(min=1).unsqueeze(1).float()
+    """err[R,2,N] bool, mask[R,N] -> error rate per (run, pol) over the kept symbols; NaN where nothing is kept (the mean of an empty slice)."""
+    cnt = mask.sum(dim=1).unsqueeze(1).float()
     return (err & mask.unsqueeze(1)).sum(dim=-1).float() / cnt
 
 
