@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Shader-clock cycles per phase of the last step of one wave of the DP wave kernel under full load (library built with the phase
-stamps: tools/snap_variant.sh stamps -DVAEQ_PHASE_STAMPS -> gpurun_variants/libvaeq_stamps.so).  VAEQ_LIB=... python tools/probe_dp_phases.py [R]"""
+stamps: tools/build_phase_probe.sh dp_wave prints the path of the library it builds).  VAEQ_LIB=... python tools/probe_dp_phases.py [R]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

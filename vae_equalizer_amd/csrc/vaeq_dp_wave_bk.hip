@@ -16,14 +16,8 @@ bool dp_wave_fixl(int B, int M)
     return M == 25 && B != 100 && !(e && e[0] == '1');
 }
 
-int launch_dp_wave_bk(const vaeq_dp_args &a, hipStream_t st)
-{
-    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave_fixl<25, decltype(nl)::value, 128, 1>(a, st); });
-}
+int launch_dp_wave_bk(const vaeq_dp_args &a, hipStream_t st) { return launch_wave_fixl_lev<25, 128, 1, true>(a, st); }
 
-int64_t dp_wave_bk_resident(int n_lev)
-{
-    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident_fixl<25, decltype(nl)::value, 128, 1>(); });
-}
+int64_t dp_wave_bk_resident(int n_lev) { return wave_resident_fixl_lev<25, 128, 1>(n_lev); }
 
 }  // namespace vaeq

@@ -6,21 +6,10 @@
 
 namespace vaeq {
 
-template <int BL, int NW>
-static int launch_fl(const vaeq_dp_args &a, hipStream_t st)
-{
-    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave_fixl<25, decltype(nl)::value, BL, NW>(a, st); });
-}
-template <int BL, int NW>
-static int64_t resident_fl(int n_lev)
-{
-    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident_fixl<25, decltype(nl)::value, BL, NW>(); });
-}
-
 int launch_dp_wave_fl(const vaeq_dp_args &a, hipStream_t st)
 {
-    return a.B <= 256 ? launch_fl<256, 2>(a, st) : a.B <= 512 ? launch_fl<512, 4>(a, st) : launch_fl<1024, 8>(a, st);
+    return a.B <= 256 ? launch_wave_fixl_lev<25, 256, 2, true>(a, st) : a.B <= 512 ? launch_wave_fixl_lev<25, 512, 4, true>(a, st) : launch_wave_fixl_lev<25, 1024, 8, true>(a, st);
 }
-int64_t dp_wave_fl_resident(int B, int n_lev) { return B <= 256 ? resident_fl<256, 2>(n_lev) : B <= 512 ? resident_fl<512, 4>(n_lev) : resident_fl<1024, 8>(n_lev); }
+int64_t dp_wave_fl_resident(int B, int n_lev) { return B <= 256 ? wave_resident_fixl_lev<25, 256, 2>(n_lev) : B <= 512 ? wave_resident_fixl_lev<25, 512, 4>(n_lev) : wave_resident_fixl_lev<25, 1024, 8>(n_lev); }
 
 }  // namespace vaeq

@@ -37,7 +37,7 @@
 #include "vaeq_wave.h"
 
 // -DVAEQ_PHASE_STAMPS: shader-clock stamps around the phases of the LAST step of one wave under full load, written over loss[0..] of the launch
-// (tools/probe_dp_phases.py reads them; the build is for that probe only: tools/snap_variant.sh stamps -DVAEQ_PHASE_STAMPS).
+// (tools/probe_dp_phases.py reads them; the build is for that probe only: tools/build_phase_probe.sh dp_wave).
 #ifdef VAEQ_PHASE_STAMPS
 #define VAEQ_STAMP(i) do { if (s == a.steps - 1) tst[i] = __builtin_readcyclecounter(); } while (0)
 #define VAEQ_XSTAMP(i) do { if (s == a.steps - 1) tsx[i] = __builtin_readcyclecounter(); } while (0)   // inside the two tap-gradient phases
@@ -46,81 +46,22 @@
 #define VAEQ_XSTAMP(i) do { } while (0)
 #endif
 #define VAEQ_NSTAMP 12
-// Experiment knobs of tools/snap_variant.sh builds (the defaults are what ships): software pipelining of the tap loops / of dL/dU
+// Experiment knob of tools/snap_variant.sh builds (the default is what ships): software pipelining of the tap loops
 #ifndef VAEQ_PIPE
 #define VAEQ_PIPE 1
 #endif
-#ifndef VAEQ_PIPE_DU
-#define VAEQ_PIPE_DU 0
-#endif
-#ifndef VAEQ_ROW_STEP
-#define VAEQ_ROW_STEP 1                                // q row offsets as one running scalar (0: products row * No4, A/B knob)
-#endif
 #define VAEQ_BT_FRAMES 16                              // frames per launch whose Adam bias corrections restart exactly like a launch's (vaeq_dp_train)
-#ifndef VAEQ_DEMAP_SHIFT
-#define VAEQ_DEMAP_SHIFT 0                             // 1: softmax shift from the nearest level instead of a maximum search -- 32 instructions fewer per step, but
-                                                       // the fused form spills 7 VGPRs at the 254-register limit: 8.65 vs 8.45 ms (profiles/r03/kernel_variants_ab.txt); off
-#endif
 #ifndef VAEQ_WPS
 #define VAEQ_WPS 2                                     // workgroups per SIMD the register budget is sized for (3 would need <= 168 VGPRs: it spills)
-#endif
-#ifndef VAEQ_CHAIN_BOUND
-#define VAEQ_CHAIN_BOUND 0                             // 1: TIMING ONLY, RESULTS ARE WRONG -- the serial stretches between the tap loops cut short (a constant for every wave sum,
-                                                       // the lane's own value for every scan and for the dL/dh half exchange, Adam without arithmetic but with its LDS traffic, VS /
-                                                       // C / bias corrections as constants): what hiding them behind the tap loops could reach at most (profiles/r04/kernel_variants_ab.txt)
-#endif
-#ifndef VAEQ_HALF_SWAP
-#define VAEQ_HALF_SWAP 1                               // the cross-half exchange of the two tap gradients as v_permlane32_swap (one swap + one add per kept value) instead of
-                                                       // 16 ds_bpermute_b32 through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms
-                                                       // (+2.2 %, profiles/r04/kernel_variants_ab.txt).  Applied to the baked B = 100 kernels only (SWAPH below); 0: A/B knob
-#endif
-// The q stores of a step and what they cost beyond their bytes (profiles/r05/):
-#ifndef VAEQ_QST_OFF
-#define VAEQ_QST_OFF 0                                 // 1: TIMING ONLY, q IS NOT WRITTEN -- the q stores compiled out, everything else textually the same: what the 32 stores
-                                                       // of a step cost in total (profiles/r05/q_store_bound.txt)
-#endif
-#ifndef VAEQ_QST_NOWAIT
-#define VAEQ_QST_NOWAIT 1                              // the next window's prefetch is issued without a branch around it (the launch's very last step fetches with every lane out of
-                                                       // range: zeros, no memory access).  Behind the branch the four loads fed a phi: the backend copied their results right
-                                                       // after the issue, behind s_waitcnt vmcnt(3..0) -- every step stood there for the loads' HBM latency and, vmcnt retiring in
-                                                       // order, for every q / y store still in flight.  Now the first wait for them is P0 of the next step.  Applied to the baked
-                                                       // B = 100 kernels only (PFLAT below); 0: A/B knob
-#endif
-#ifndef VAEQ_QST_NT
-#define VAEQ_QST_NT 1                                  // the q stores leave with the streaming ("nt") cache policy: 32 rows x 400 B per wave-step that nothing reads back before the
-                                                       // launch ends.  Same gate as VAEQ_QST_NOWAIT (QAUX below); 0: A/B knob.  Numbers for both: profiles/r05/kernel_variants_ab.txt
 #endif
 
 namespace vaeq {
 
-// The serial stretches between the tap loops, as the kernel calls them (VAEQ_CHAIN_BOUND = 0: the plain operations).
-#if VAEQ_CHAIN_BOUND
-__device__ __forceinline__ float chain_sum(float v) { asm volatile("" :: "v"(v)); return 1.0f; }
-__device__ __forceinline__ float chain_scan(float v) { return v; }
-__device__ __forceinline__ float chain_half_scan(float v) { return v; }
-__device__ __forceinline__ float chain_rcp(float v) { asm volatile("" :: "v"(v)); return 1.0f; }
-__device__ __forceinline__ float chain_log(float v) { asm volatile("" :: "v"(v)); return 1.0f; }
-__device__ __forceinline__ void chain_adam(float &, float &m, float &v, float g, float, float) { m = g; v = g; }
-#define VAEQ_CUT(real, cut) (cut)
-#else
-#define VAEQ_CUT(real, cut) (real)
-__device__ __forceinline__ float chain_sum(float v) { return wave_sum_dpp(v); }
-__device__ __forceinline__ float chain_scan(float v) { return wave_incl_scan_dpp(v); }
-__device__ __forceinline__ float chain_half_scan(float v) { return half_incl_scan_dpp(v); }
-__device__ __forceinline__ float chain_rcp(float v) { return __builtin_amdgcn_rcpf(v); }
-__device__ __forceinline__ float chain_log(float v) { return __builtin_amdgcn_logf(v); }
-__device__ __forceinline__ void chain_adam(float &p, float &m, float &v, float g, float ss, float bc) { adam_update_fast(p, m, v, g, ss, bc); }
-#endif
-
 // Sum of a tap-gradient component over the two 32-lane halves, for the half that keeps it: a0 belongs to the taps the lower half owns, a1 to the upper
 // half's; returns a0[lane] + a0[lane ^ 32] in the lower and a1[lane] + a1[lane ^ 32] in the upper half (in either form the lane's own part is one addend and
-// its partner's the other: IEEE addition commutes, the sums are bitwise the same).  DH: the exchange belongs to the dL/dh stretch (VAEQ_CHAIN_BOUND).
-template <bool DH>
-__device__ __forceinline__ float half_sum(float a0, float a1, int half)
+// its partner's the other: IEEE addition commutes, the sums are bitwise the same).
+__device__ __forceinline__ float half_sum(float a0, float a1)
 {
-#if VAEQ_CHAIN_BOUND
-    if constexpr (DH) return half ? a1 : a0;
-#endif
     // swap a0's upper half with a1's lower half: the lower lanes then hold (a0 own, a0 partner), the upper lanes (a1 partner, a1 own)
     const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a0), __builtin_bit_cast(unsigned, a1), false, false);
     return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
@@ -198,7 +139,7 @@ __device__ __forceinline__ void pair_fir(cacc (&acc)[2][2], cacc (&accx)[2][2], 
 // dL/dU for the lane's symbol pair: the FIR's shape on the residual e with conjugated channel taps, acc[chi][sym][nu] += e[chi] * conj(h[chi][nu]),
 // BOTH chi in one loop (16 independent accumulator chains, see pair_fir).  ep = phase-0 pointer of the lane into e[chi = 0] (chi = 1: + 4 Lph);
 // ht[chi * 2 + nu] = the tap rows (float2, MP apart).  Runs at the kernel's register peak (the demapper's moments are live): one operand set.
-template <int M, bool PIPE = false, bool MERGE = true>
+template <int M, bool MERGE = true>
 __device__ __forceinline__ void pair_du(cacc (&acc)[2][2][2], const float2 *ep, int Lph, const float2 *ht, int MP)
 {
     constexpr int G = M / 4;
@@ -221,7 +162,7 @@ __device__ __forceinline__ void pair_du(cacc (&acc)[2][2][2], const float2 *ep, 
 #pragma unroll
             for (int t = 1; t < 4; t++) { fma1(0, r, t, std::false_type{}); fma1(1, r + 14, t, std::false_type{}); }
         };
-        pipe2<28, true, PIPE>(G, load, fma);
+        pipe2<28, true, false>(G, load, fma);
     } else {                                           // one chi after the other (half the operand registers)
 #pragma unroll
         for (int chi = 0; chi < 2; chi++) {
@@ -231,7 +172,7 @@ __device__ __forceinline__ void pair_du(cacc (&acc)[2][2][2], const float2 *ep, 
 #pragma unroll
                 for (int t = 1; t < 4; t++) fma1(chi, r, t, std::false_type{});
             };
-            pipe2<14, true, PIPE>(G, load, fma);
+            pipe2<14, true, false>(G, load, fma);
         }
     }
 #pragma unroll
@@ -290,13 +231,18 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     constexpr bool FIXL = BT > 0 || (BL > 0 && M != 13 && M != 17 && !(M == 31 && NW == 1));
     constexpr bool PIPE = VAEQ_PIPE && FIXL;               // run-time layouts keep more addresses live: there one operand set,
     constexpr bool WIDE = FIXL;                            // ... 8 accumulator chains and one chi at a time in dL/dU (fits the register file)
-    // the halves of the two tap gradients meet on the vector ALU (half_sum): the baked B = 100 kernels, where it is measured and its bits are pinned
-    // (tests/test_dp_wave_bits_gpu.py); every other instantiation keeps the shuffles, instruction for instruction
-    constexpr bool SWAPH = VAEQ_HALF_SWAP && BT == 100 && NW == 1;
-    // the window prefetch without a branch (VAEQ_QST_NOWAIT): the baked B = 100 kernels, like SWAPH
-    constexpr bool PFLAT = VAEQ_QST_NOWAIT && BT == 100 && NW == 1;
-    constexpr int QAUX = VAEQ_QST_NT && BT == 100 && NW == 1 ? 2 : 0;   // cache policy of the q stores
-    constexpr bool PIPE_DU = VAEQ_PIPE_DU;                 // dL/dU runs at the kernel's register peak (moments of the demapper still live): no second operand set there
+    // B100: the baked B = 100 kernel on one wave, the shape that is measured step by step and whose bits are pinned (tests/test_dp_wave_bits_gpu.py).
+    // It alone takes three forms; every other instantiation keeps the plain one, instruction for instruction:
+    //  * the halves of the two tap gradients meet on v_permlane32_swap (half_sum: one swap + one add per kept value) instead of 16 ds_bpermute_b32
+    //    through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms (profiles/r04/kernel_variants_ab.txt)
+    //  * the next window's prefetch is issued without a branch around it (the launch's very last step fetches with every lane out of range: zeros, no
+    //    memory access).  Behind the branch the four loads fed a phi: the backend copied their results right after the issue, behind
+    //    s_waitcnt vmcnt(3..0) -- every step stood there for the loads' HBM latency and, vmcnt retiring in order, for every q / y store still in
+    //    flight.  Now the first wait for them is P0 of the next step (profiles/r05/kernel_variants_ab.txt)
+    //  * the q stores leave with the streaming ("nt") cache policy: 32 rows x 400 B per wave-step that nothing reads back before the launch ends
+    //    (profiles/r05/kernel_variants_ab.txt; what the stores cost in total: profiles/r05/q_store_bound.txt)
+    constexpr bool B100 = BT == 100 && NW == 1;
+    constexpr int QAUX = B100 ? 2 : 0;                         // cache policy of the q stores
     const int B = BT ? BT : a.B;
     const int BS = BT ? BT : BL ? BL : B;                      // the minibatch length the LDS layout (offsets, row strides) is made for
     // ODDB: on a class layout (BL) the minibatch length may be odd -- the last lane's pair is (B - 1, phantom): the phantom symbol is computed like
@@ -326,7 +272,6 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     }
     const float var0 = a.var[run * 2 + 0], var1 = a.var[run * 2 + 1];
     const float lrW = a.lr_W[run], lrH = a.lr_h[run];
-    const float lev_delta = amp[NLEV - 1] - amp[NLEV - 2], lev_inv = 1.0f / lev_delta, lev_off = -amp[0] * lev_inv;   // the (equidistant) level grid
 
     // ---- zero the halo'd buffers once; load taps; owner lanes load their Adam moments
     for (int i = gl; i < (lay.W - lay.X) / 8; i += NT) Xs[i] = make_float2(0.f, 0.f);     // X, E, U, PSv
@@ -406,7 +351,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             b2t = BTW[1][f];                                    // (dp_runs.run_dp_batch groups the frames of small sweeps)
         }
         // one buffer descriptor per output array and frame; rows are addressed by scalar offsets (row * No4) folded into the stores
-        const bool qf = !VAEQ_QST_OFF && OUT != 2 && a.q_out, yf = a.y_out, ef = OUT != 1 && a.eq_out, df = OUT != 1 && a.dec_out;
+        const bool qf = OUT != 2 && a.q_out, yf = a.y_out, ef = OUT != 1 && a.eq_out, df = OUT != 1 && a.dec_out;
         const uint32_t No4 = (uint32_t)No * 4u;
         const size_t fr = (size_t)run * a.n_frames + f;
         const __amdgpu_buffer_rsrc_t qr = make_rsrc(qf ? a.q_out + fr * (4 * NLEV) * No : nullptr, qf ? 4u * NLEV * No4 : 0u);
@@ -462,21 +407,15 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             if (yf) {
                 uint32_t yrow = 0u;                            // rows (o, re / im) in ascending order: a running scalar offset (see qrow below)
                 auto next_row = [&]() {
-#if VAEQ_ROW_STEP
                     yrow += No4;
                     asm volatile("" : "+s"(yrow));
-#endif
                 };
 #pragma unroll
                 for (int o = 0; o < 2; o++) {
-#if VAEQ_ROW_STEP
                     const uint32_t r0 = yrow;
                     next_row();
                     const uint32_t r1 = yrow;
                     next_row();
-#else
-                    const uint32_t r0 = (uint32_t)(o * 2 + 0) * No4, r1 = (uint32_t)(o * 2 + 1) * No4;
-#endif
                     if (pairst) {
                         bst64(v2f{y[0][o].x, y[1][o].x}, yr, vo0, r0);
                         bst64(v2f{y[0][o].y, y[1][o].y}, yr, vo0, r1);
@@ -490,11 +429,9 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             VAEQ_STAMP(3);
             // ============ P2: soft demap + moments (registers), mu -> LDS, prefix sums of the variances
             float mv[2][2][2], mt3[2][2][2], mkc[2][2][2];     // [sym][o][c]: Var_q, 3rd central moment, KL-gradient moment
-#if VAEQ_ROW_STEP
             // the 4 n rows of q leave in ascending order: their byte offset is ONE running scalar (an s_add per row) -- as 32 products row * No4 they
             // were 32 live scalars, spilled and fetched back with v_readlane + hazard s_nops in front of every store
             uint32_t qrow = 0u;
-#endif
             float klsum = 0.f, vv[2][2];                       // vv[o][sym] = v_I + v_Q
 #pragma unroll
             for (int o = 0; o < 2; o++) {
@@ -506,25 +443,6 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                     const v2f yy = c ? v2f{y[0][o].y, y[1][o].y} : v2f{y[0][o].x, y[1][o].x};
                     v2f z[NLEV], q[NLEV];
                     v2f ssum = {0.f, 0.f};
-#if VAEQ_DEMAP_SHIFT
-                    // softmax shift without a maximum search: the squared distance to the NEAREST level (found by rounding on the equidistant level
-                    // grid) is taken out of every d^2 -- z_i = -c2 (d_i^2 - dmin^2) - b2_i <= 0 for every level and >= -max b2 for the nearest one
-                    // (no overflow, the sum never underflows); it rides in the FMA that squares d: 8 subtractions and 8 maxima per axis gone
-                    v2f dm2;
-                    {
-                        const v2f t = yy * lev_inv + lev_off;  // level index coordinate (y - amp[0]) / delta
-                        const v2f r = {__builtin_amdgcn_fmed3f(__builtin_rintf(t.x), 0.f, (float)(NLEV - 1)), __builtin_amdgcn_fmed3f(__builtin_rintf(t.y), 0.f, (float)(NLEV - 1))};
-                        const v2f dm = (t - r) * lev_delta;
-                        dm2 = dm * dm;
-                    }
-#pragma unroll
-                    for (int i = 0; i < NLEV; i++) {
-                        const v2f d = yy - amp[i];
-                        z[i] = -((d * d - dm2) * c2 + b2[i]);
-                        q[i] = v2f{__builtin_amdgcn_exp2f(z[i].x), __builtin_amdgcn_exp2f(z[i].y)};
-                        ssum += q[i];
-                    }
-#else
                     float zm0 = -3.0e38f, zm1 = -3.0e38f;
 #pragma unroll
                     for (int i = 0; i < NLEV; i++) {
@@ -540,7 +458,6 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         q[i] = v2f{__builtin_amdgcn_exp2f(z[i].x), __builtin_amdgcn_exp2f(z[i].y)};
                         ssum += q[i];
                     }
-#endif
                     const v2f rs = {__builtin_amdgcn_rcpf(ssum.x), __builtin_amdgcn_rcpf(ssum.y)};
                     v2f m1 = {0.f, 0.f};
 #pragma unroll
@@ -590,17 +507,11 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                     if (qf) {
 #pragma unroll
                         for (int i = 0; i < NLEV; i++) {
-#if VAEQ_ROW_STEP
                             const uint32_t ro = qrow;
-#else
-                            const uint32_t ro = (uint32_t)(o * 2 * NLEV + c * NLEV + i) * No4;
-#endif
                             if (pairst) bst64<QAUX>(q[i], qr, vo0, ro);
                             else { bst32<QAUX>(q[i].x, qr, vo0, ro); bst32<QAUX>(q[i].y, qr, vo1, ro); }
-#if VAEQ_ROW_STEP
                             qrow += No4;
                             asm volatile("" : "+s"(qrow));     // keeps it a running value (the optimiser would turn it back into products)
-#endif
                         }
                     }
                 }
@@ -616,7 +527,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             {
                 float inc[2];
 #pragma unroll
-                for (int o = 0; o < 2; o++) inc[o] = chain_scan(vv[o][0] + vv[o][1]);
+                for (int o = 0; o < 2; o++) inc[o] = wave_incl_scan_dpp(vv[o][0] + vv[o][1]);
                 if constexpr (NW > 1) {                        // add the totals of the waves below (fixed order)
                     if (lane == 63) { RED[wv] = inc[0]; RED[NW + wv] = inc[1]; }
                     sync_lds<NW>();
@@ -636,7 +547,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             sync_lds<NW>();
             if (owner) {                                       // VS[nu][j]: lane = (j = tk, nu = half)
                 const int lo = (Mh - tk + 1) >> 1, hi_ = (nm - 1 + Mh - tk) >> 1;
-                VS[half * M + tk] = VAEQ_CUT(PSv[half * (BS + 1) + hi_ + 1] - PSv[half * (BS + 1) + lo], 1.0f);
+                VS[half * M + tk] = PSv[half * (BS + 1) + hi_ + 1] - PSv[half * (BS + 1) + lo];
             }
             sync_lds<NW>();
 
@@ -651,7 +562,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 hq0 = h0.x * h0.x + h0.y * h0.y;
                 hq1 = h1.x * h1.x + h1.y * h1.y;
             }
-            const float vsl = worker ? VAEQ_CUT(VS[half * M + tk], 1.0f) : 0.f;
+            const float vsl = worker ? VS[half * M + tk] : 0.f;
             {
                 cacc D[2][4];                                  // [chi][i], i = 2*dl + par; lanes without a quad shadow lane 0 (no divergence, unused)
                 constexpr int NA = mh + 1, NB = NA / 2;        // a = 0..mh; pairs (2b, 2b+1)
@@ -712,9 +623,9 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         }
                 }
             }
-            se0 = chain_sum(se0);
-            se1 = chain_sum(se1);
-            klsum = chain_sum(klsum);
+            se0 = wave_sum_dpp(se0);
+            se1 = wave_sum_dpp(se1);
+            klsum = wave_sum_dpp(klsum);
             if constexpr (NW > 1) {                            // totals over the run's waves, same order in every wave
                 if (lane == 0) { RED[16 + wv] = se0; RED[16 + NW + wv] = se1; RED[16 + 2 * NW + wv] = klsum; }
                 sync_lds<NW>();
@@ -723,13 +634,13 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 for (int w = 1; w < NW; w++) { se0 += RED[16 + w]; se1 += RED[16 + NW + w]; klsum += RED[16 + 2 * NW + w]; }
             }
             // C[chi] = sum|e|^2 + sum_{nu,j} |h|^2 VS   (lanes (j, nu) hold one term each for both chi; hq, vsl were read before the D loop)
-            const float C0 = se0 + chain_sum(hq0 * vsl), C1 = se1 + chain_sum(hq1 * vsl);
+            const float C0 = se0 + wave_sum_dpp(hq0 * vsl), C1 = se1 + wave_sum_dpp(hq1 * vsl);
             // C is uniform: hardware reciprocal / log2 (1 ulp: 6e-8 on the gradients' common scale, 1e-7 relative on the ELBO) instead of the IEEE
             // division and logf expansions (~60 instructions per step that every lane would execute for lane 0's two stores)
-            const float gC0 = (float)nm * chain_rcp(C0), gC1 = (float)nm * chain_rcp(C1);
+            const float gC0 = (float)nm * __builtin_amdgcn_rcpf(C0), gC1 = (float)nm * __builtin_amdgcn_rcpf(C1);
             {
                 const uint32_t vo = gl == 0 ? 0u : OOB;        // lane 0 stores; row offsets ride in the scalar offset
-                if (a.loss) bst32((float)nm * LN2 * (chain_log(C0) + chain_log(C1)) + klsum, lr_, vo, (uint32_t)s * 4u);
+                if (a.loss) bst32((float)nm * LN2 * (__builtin_amdgcn_logf(C0) + __builtin_amdgcn_logf(C1)) + klsum, lr_, vo, (uint32_t)s * 4u);
                 if (a.var_est) {
                     bst32(C0 * rnm, vr_, vo, (uint32_t)s * 4u);
                     bst32(C1 * rnm, vr_, vo, ((uint32_t)a.steps + (uint32_t)s) * 4u);
@@ -737,7 +648,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             }
             // prefix sums over j of H2[nu][j] = sum_chi gC[chi] |h[chi,nu,j]|^2  -> G_V by two lookups per symbol
             {
-                const float inc = chain_half_scan(gC0 * hq0 + gC1 * hq1);   // inclusive scan within each 32-lane half
+                const float inc = half_incl_scan_dpp(gC0 * hq0 + gC1 * hq1);   // inclusive scan within each 32-lane half
                 if (owner) PSh[half * MP + tk + 1] = inc;
                 if (tk == 0) PSh[half * MP] = 0.f;
             }
@@ -748,8 +659,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             step += 1;
             b1t *= 0.9;
             b2t *= 0.999;
-            const float rbc1 = VAEQ_CUT(__builtin_amdgcn_rcpf((float)(1.0 - b1t)), 1.0f);                 // bias corrections: beta^t in double,
-            const float bc2s = VAEQ_CUT(__builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf((float)(1.0 - b2t))), 1.0f);   // the rest in float
+            const float rbc1 = __builtin_amdgcn_rcpf((float)(1.0 - b1t));                 // bias corrections: beta^t in double,
+            const float bc2s = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf((float)(1.0 - b2t)));   // the rest in float
             const float ssW = lrW * rbc1, ssH = lrH * rbc1;
             float2 hnew[2];
             hnew[0] = hnew[1] = make_float2(0.f, 0.f);
@@ -764,7 +675,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 #pragma unroll
                     for (int v = 0; v < 2; v++) {
                         ph_h[v] = Ht[(half * 2 + v) * MP + tk];
-                        ph_vs[v] = VAEQ_CUT(VS[v * M + tk], 1.0f);
+                        ph_vs[v] = VS[v * M + tk];
                     }
                 }
                 cacc ca[2][2];
@@ -822,11 +733,11 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 #pragma unroll
                     for (int v = 0; v < 2; v++) acc[chi][v] = cfinc(ca[chi][v]);             // e * conj(U)
                 // combine the two halves; lane (j, half) keeps chi = half
-                if constexpr (SWAPH || VAEQ_CHAIN_BOUND) {
+                if constexpr (B100) {
 #pragma unroll
                     for (int v = 0; v < 2; v++) {               // (both entries get the kept sum: the selects below pick either)
-                        acc[0][v].x = acc[1][v].x = half_sum<true>(acc[0][v].x, acc[1][v].x, half);
-                        acc[0][v].y = acc[1][v].y = half_sum<true>(acc[0][v].y, acc[1][v].y, half);
+                        acc[0][v].x = acc[1][v].x = half_sum(acc[0][v].x, acc[1][v].x);
+                        acc[0][v].y = acc[1][v].y = half_sum(acc[0][v].y, acc[1][v].y);
                     }
                 } else {
 #pragma unroll
@@ -859,8 +770,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         ghi[v] = g * (-2.0f * ac.y + 2.0f * hh.y * vs);
                         hnew[v] = hh;
                         if (!a.no_update) {
-                            chain_adam(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
-                            chain_adam(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
+                            adam_update_fast(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
+                            adam_update_fast(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
                         }
                     }
                 }
@@ -872,7 +783,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             // for these loads at the top of the next step does not also wait for fresh stores (vmcnt retires in order)
             {
                 const bool last_s = s + 1 == a.steps;
-                if constexpr (PFLAT) {                         // no branch: the loads' results are not copied (and waited for) here
+                if constexpr (B100) {                         // no branch: the loads' results are not copied (and waited for) here
                     const bool more = !(last_s && f + 1 == a.n_frames);
                     const uint32_t vo = ldl && more ? ((uint32_t)(last_s ? 0 : s + 1) * (uint32_t)a.stride_sym * 2u + 4u * gl) * 4u : OOB;   // the launch's last step: nothing is read
 #pragma unroll
@@ -887,7 +798,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 float2 au0[2][2], au1[2][2];                   // chi = 0 / 1: [sym][nu]
                 {
                     cacc cu[2][2][2];                          // [chi][sym][nu]
-                    pair_du<M, PIPE_DU, WIDE>(cu, Ea, Lph, Ht, MP);
+                    pair_du<M, WIDE>(cu, Ea, Lph, Ht, MP);
 #pragma unroll
                     for (int sy = 0; sy < 2; sy++)
 #pragma unroll
@@ -927,8 +838,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         ghi[v] = g * (-2.0f * ac.y + 2.0f * hh.y * vs);
                         hnew[v] = hh;
                         if (!a.no_update) {
-                            chain_adam(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
-                            chain_adam(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
+                            adam_update_fast(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
+                            adam_update_fast(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
                         }
                     }
                 }
@@ -1010,11 +921,11 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 for (int o = 0; o < 2; o++)
 #pragma unroll
                     for (int pp = 0; pp < 2; pp++) acc[o][pp] = cfinc(ca[o][pp]);            // gy * conj(x)
-                if constexpr (SWAPH) {
+                if constexpr (B100) {
 #pragma unroll
                     for (int p = 0; p < 2; p++) {               // lane (k, half) keeps o = half (see dL/dh)
-                        acc[0][p].x = acc[1][p].x = half_sum<false>(acc[0][p].x, acc[1][p].x, half);
-                        acc[0][p].y = acc[1][p].y = half_sum<false>(acc[0][p].y, acc[1][p].y, half);
+                        acc[0][p].x = acc[1][p].x = half_sum(acc[0][p].x, acc[1][p].x);
+                        acc[0][p].y = acc[1][p].y = half_sum(acc[0][p].y, acc[1][p].y);
                     }
                 } else {
 #pragma unroll
@@ -1053,8 +964,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         if (!a.no_update) {
                             float *wq = reinterpret_cast<float *>(&Wt[p * M + tk]) + half * 2;
                             float wr = pw_w[p][0], wi = pw_w[p][1];
-                            chain_adam(wr, pw_m[p][0], pw_v[p][0], gwr[p], ssW, bc2s);
-                            chain_adam(wi, pw_m[p][1], pw_v[p][1], gwi[p], ssW, bc2s);
+                            adam_update_fast(wr, pw_m[p][0], pw_v[p][0], gwr[p], ssW, bc2s);
+                            adam_update_fast(wi, pw_m[p][1], pw_v[p][1], gwi[p], ssW, bc2s);
                             wq[0] = wr;
                             wq[1] = wi;
                             mWr(p) = pw_m[p][0]; mWi(p) = pw_m[p][1];
@@ -1112,96 +1023,70 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 }
 
 
-template <int M, int NLEV, int BT, int NW>
+// Launch of dp_wave_kernel<M, NLEV, BT, PAIR, OUT, NW, BL>: PAIR from the parity of the keep window, OUT from the outputs the call asks for.
+// BT > 0: the baked shape (a.B == BT); BL > 0 (BT == 0): run-time B <= BL on the fixed LDS layout of BL; both 0: the layout follows a.B.
+// SPEC = false: only the all-outputs-nullable instantiation (OUT = 0) exists -- the run-time layouts and the tap counts that are not the reference's default.
+template <int M, int NLEV, int BT, int NW, int BL, bool SPEC>
 static int launch_wave(const vaeq_dp_args &a, hipStream_t st)
 {
-    const size_t lds = (size_t)wave_layout(a.B, M, NW).total;
-    const bool pair = ((a.keep_len | a.keep_off) & 1) == 0;
-    void (*k)(const vaeq_dp_args) = pair ? dp_wave_kernel<M, NLEV, BT, true, 0, NW> : dp_wave_kernel<M, NLEV, BT, false, 0, NW>;
-    if (BT) {                                                  // the tuned shape also gets the output-mode specialisations
-        if (!a.eq_out && !a.dec_out) k = pair ? dp_wave_kernel<M, NLEV, BT, true, BT ? 1 : 0, NW> : dp_wave_kernel<M, NLEV, BT, false, BT ? 1 : 0, NW>;
-        else if (!a.q_out) k = pair ? dp_wave_kernel<M, NLEV, BT, true, BT ? 2 : 0, NW> : dp_wave_kernel<M, NLEV, BT, false, BT ? 2 : 0, NW>;
-    }
-    const int out = !BT ? 0 : (!a.eq_out && !a.dec_out) ? 1 : !a.q_out ? 2 : 0;
-    note_kernel("vaeq::dp_wave_kernel<%d, %d, %d, %s, %d, %d, 0>", M, NLEV, BT, pair ? "true" : "false", out, NW);   // every template argument, as rocprofv3 prints the name
-    return launch(k, dim3(a.R), dim3(64 * NW), lds, st, a);
-}
-
-// run-time B <= BL on the fixed LDS layout of BL (immediate offsets and strides, pipelined tap loops), with the output-mode specialisations
-// (SPEC = false: only the all-outputs-nullable instantiation, for the tap counts that are not the reference's default)
-template <int M, int NLEV, int BL, int NW, bool SPEC = true>
-static int launch_wave_fixl(const vaeq_dp_args &a, hipStream_t st)
-{
-    const size_t lds = (size_t)wave_layout(BL, M, NW).total;
+    const size_t lds = (size_t)wave_layout(BL ? BL : a.B, M, NW).total;
     const bool pair = ((a.keep_len | a.keep_off) & 1) == 0;
     const int out = !SPEC ? 0 : (!a.eq_out && !a.dec_out) ? 1 : !a.q_out ? 2 : 0;
-    void (*k)(const vaeq_dp_args) = pair ? dp_wave_kernel<M, NLEV, 0, true, 0, NW, BL> : dp_wave_kernel<M, NLEV, 0, false, 0, NW, BL>;
-    if constexpr (SPEC) {
-        if (out == 1) k = pair ? dp_wave_kernel<M, NLEV, 0, true, 1, NW, BL> : dp_wave_kernel<M, NLEV, 0, false, 1, NW, BL>;
-        else if (out == 2) k = pair ? dp_wave_kernel<M, NLEV, 0, true, 2, NW, BL> : dp_wave_kernel<M, NLEV, 0, false, 2, NW, BL>;
-    }
-    note_kernel("vaeq::dp_wave_kernel<%d, %d, 0, %s, %d, %d, %d>", M, NLEV, pair ? "true" : "false", out, NW, BL);
-    return launch(k, dim3(a.R), dim3(64 * NW), lds, st, a);
+    constexpr int O1 = SPEC ? 1 : 0, O2 = SPEC ? 2 : 0;
+    void (*const k[2][3])(const vaeq_dp_args) = {
+        {dp_wave_kernel<M, NLEV, BT, false, 0, NW, BL>, dp_wave_kernel<M, NLEV, BT, false, O1, NW, BL>, dp_wave_kernel<M, NLEV, BT, false, O2, NW, BL>},
+        {dp_wave_kernel<M, NLEV, BT, true, 0, NW, BL>, dp_wave_kernel<M, NLEV, BT, true, O1, NW, BL>, dp_wave_kernel<M, NLEV, BT, true, O2, NW, BL>}};
+    note_kernel("vaeq::dp_wave_kernel<%d, %d, %d, %s, %d, %d, %d>", M, NLEV, BT, pair ? "true" : "false", out, NW, BL);   // every template argument, as rocprofv3 prints the name
+    return launch(k[pair][out], dim3(a.R), dim3(64 * NW), lds, st, a);
 }
 
-template <int M, int NLEV, int BL, int NW>
-static int64_t wave_resident_fixl()
-{
-    int nb = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return VAEQ_ERR_DEVICE;
-    auto k = dp_wave_kernel<M, NLEV, 0, true, 0, NW, BL>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * NW, (size_t)wave_layout(BL, M, NW).total) != hipSuccess) return VAEQ_ERR_DEVICE;
-    return (int64_t)nb * prop.multiProcessorCount;
-}
-
-template <int M, int BT, int NW>
-static int launch_wave_lev(const vaeq_dp_args &a, hipStream_t st)
-{
-    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave<M, decltype(nl)::value, BT, NW>(a, st); });
-}
-
-template <int M, int NLEV, int BT, int NW>
+// Runs of that shape resident on the device at once (B: the minibatch length the layout follows when neither BT nor BL fixes it)
+template <int M, int NLEV, int BT, int NW, int BL>
 static int64_t wave_resident(int B)
 {
     int nb = 0, dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return VAEQ_ERR_DEVICE;
-    const size_t lds = (size_t)wave_layout(B, M, NW).total;
-    auto k = dp_wave_kernel<M, NLEV, BT, true, 0, NW>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * NW, lds) != hipSuccess) return VAEQ_ERR_DEVICE;
+    auto k = dp_wave_kernel<M, NLEV, BT, true, 0, NW, BL>;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * NW, (size_t)wave_layout(BL ? BL : B, M, NW).total) != hipSuccess) return VAEQ_ERR_DEVICE;
     return (int64_t)nb * prop.multiProcessorCount;
 }
 
+// ... with NLEV from the call: the baked shapes and M = 25's run-time layout (BT = 0) ...
+template <int M, int BT, int NW>
+static int launch_wave_lev(const vaeq_dp_args &a, hipStream_t st)
+{
+    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave<M, decltype(nl)::value, BT, NW, 0, (BT > 0)>(a, st); });
+}
 template <int M, int BT, int NW>
 static int64_t wave_resident_lev(int B, int n_lev)
 {
-    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident<M, decltype(nl)::value, BT, NW>(B); });
+    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident<M, decltype(nl)::value, BT, NW, 0>(B); });
+}
+// ... and run-time B <= BL on the fixed layout of BL (immediate offsets and strides, pipelined tap loops)
+template <int M, int BL, int NW, bool SPEC>
+static int launch_wave_fixl_lev(const vaeq_dp_args &a, hipStream_t st)
+{
+    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave<M, decltype(nl)::value, 0, NW, BL, SPEC>(a, st); });
+}
+template <int M, int BL, int NW>
+static int64_t wave_resident_fixl_lev(int n_lev)
+{
+    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident<M, decltype(nl)::value, 0, NW, BL>(BL); });
 }
 
 // every supported M for a given NW (the per-NW translation units instantiate these): M = 25 on the run-time layout (its fixed-layout and baked forms
 // are dispatched before; this is their A/B counterpart), every other tap count on the fixed layout of the NW class's largest minibatch
-template <int M, int NW>
-static int launch_wave_fixl_lev(const vaeq_dp_args &a, hipStream_t st)
-{
-    return dispatch_nlev(a.n_lev, [&](auto nl) { return launch_wave_fixl<M, decltype(nl)::value, 128 * NW, NW, false>(a, st); });
-}
-template <int M, int NW>
-static int64_t wave_resident_fixl_lev(int n_lev)
-{
-    return dispatch_nlev(n_lev, [&](auto nl) { return wave_resident_fixl<M, decltype(nl)::value, 128 * NW, NW>(); });
-}
-
 template <int NW>
 static int launch_wave_any(const vaeq_dp_args &a, hipStream_t st)
 {
     switch (a.M) {
     case 25: return launch_wave_lev<25, 0, NW>(a, st);
-    case 31: return launch_wave_fixl_lev<31, NW>(a, st);
-    case 21: return launch_wave_fixl_lev<21, NW>(a, st);
-    case 17: return launch_wave_fixl_lev<17, NW>(a, st);
-    case 13: return launch_wave_fixl_lev<13, NW>(a, st);
-    case 9: return launch_wave_fixl_lev<9, NW>(a, st);
+    case 31: return launch_wave_fixl_lev<31, 128 * NW, NW, false>(a, st);
+    case 21: return launch_wave_fixl_lev<21, 128 * NW, NW, false>(a, st);
+    case 17: return launch_wave_fixl_lev<17, 128 * NW, NW, false>(a, st);
+    case 13: return launch_wave_fixl_lev<13, 128 * NW, NW, false>(a, st);
+    case 9: return launch_wave_fixl_lev<9, 128 * NW, NW, false>(a, st);
     }
     return VAEQ_ERR_SHAPE;
 }
@@ -1211,11 +1096,11 @@ static int64_t wave_resident_any(int B, int M, int n_lev)
 {
     switch (M) {
     case 25: return wave_resident_lev<25, 0, NW>(B, n_lev);
-    case 31: return wave_resident_fixl_lev<31, NW>(n_lev);
-    case 21: return wave_resident_fixl_lev<21, NW>(n_lev);
-    case 17: return wave_resident_fixl_lev<17, NW>(n_lev);
-    case 13: return wave_resident_fixl_lev<13, NW>(n_lev);
-    case 9: return wave_resident_fixl_lev<9, NW>(n_lev);
+    case 31: return wave_resident_fixl_lev<31, 128 * NW, NW>(n_lev);
+    case 21: return wave_resident_fixl_lev<21, 128 * NW, NW>(n_lev);
+    case 17: return wave_resident_fixl_lev<17, 128 * NW, NW>(n_lev);
+    case 13: return wave_resident_fixl_lev<13, 128 * NW, NW>(n_lev);
+    case 9: return wave_resident_fixl_lev<9, 128 * NW, NW>(n_lev);
     }
     return VAEQ_ERR_SHAPE;
 }

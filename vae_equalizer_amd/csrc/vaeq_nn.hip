@@ -82,27 +82,6 @@ __global__ __launch_bounds__(NT, (NLEV == 2 && NT <= 512) ? 4 : (NT / 256 > 0 ? 
     const int lane = tid & 63, wv = tid >> 6;
     constexpr int NWV = NT / 64, CQ = C / 4;
 
-    // BK = 1: the next minibatch is fetched while the current step computes (its 1200 samples = three per thread wait in registers: xs is read until
-    // the last gradient phase) -- a step no longer starts with an exposed HBM round trip
-    constexpr int NPRE = BK == 1 ? (1200 + NT - 1) / NT : 1;
-    constexpr bool PREF = BK == 1 && !BN && VAEQ_NN_PREF;
-    float pre[NPRE];
-    auto load_minibatch = [&](int s) {
-#pragma unroll
-        for (int u = 0; u < NPRE; u++) {
-            const int i = tid + u * NT, row = i >= L, c = i - row * L;
-            pre[u] = i < 2 * L ? rxr[(size_t)row * a.S + (size_t)s * L + c] : 0.f;
-        }
-    };
-    auto store_minibatch = [&]() {
-#pragma unroll
-        for (int u = 0; u < NPRE; u++) {
-            const int i = tid + u * NT, row = i >= L, c = i - row * L;
-            if (i < 2 * L) xs[row * Lx + p1 + c] = pre[u];
-        }
-    };
-    if constexpr (PREF) { load_minibatch(0); store_minibatch(); __syncthreads(); }
-
 #ifdef VAEQ_NN_STAMPS
     __shared__ long long tstamp[16];                            // -DVAEQ_NN_STAMPS: wall-clock stamps of run 0's last step (tools/probe_nn_phases.py)
 #define NN_STAMP(i) do { __syncthreads(); if (tid == 0 && run == 0 && s == a.steps - 1) tstamp[i] = wall_clock64(); } while (0)
@@ -112,16 +91,14 @@ __global__ __launch_bounds__(NT, (NLEV == 2 && NT <= 512) ? 4 : (NT / 256 > 0 ? 
     for (int s = 0; s < a.steps; s++) {
         NN_STAMP(0);
         // ---- P0: minibatch -> LDS (:276)
-        if constexpr (!PREF) {
-            for (int i = tid; i < 2 * L; i += NT) {
-                const int row = i / L, c = i - row * L;
-                xs[row * Lx + p1 + c] = rxr[(size_t)row * a.S + (size_t)s * L + c];
-            }
-            __syncthreads();
+        for (int i = tid; i < 2 * L; i += NT) {
+            const int row = i / L, c = i - row * L;
+            xs[row * Lx + p1 + c] = rxr[(size_t)row * a.S + (size_t)s * L + c];
         }
+        __syncthreads();
         NN_STAMP(1);
         // ---- P1/P2: fc1 + ELU, fc2
-        nn_fc1_elu<NT, NLEV, BK == 1 && VAEQ_NN_LEAN>(l, k1, xs, th, w1t, z1, L, 0, L);
+        nn_fc1_elu<NT, NLEV>(l, k1, xs, th, w1t, z1, L, 0, L);
         __syncthreads();
         if (BN) {                                              // BatchNorm1d in training mode (:203): batch statistics over the L samples
             constexpr int NVM = 10;                            // a lane's share of a channel row stays in registers when L <= 640 (the three passes
@@ -169,7 +146,7 @@ __global__ __launch_bounds__(NT, (NLEV == 2 && NT <= 512) ? 4 : (NT / 256 > 0 ? 
             }
             __syncthreads();
         }
-        nn_fc2<NT, NLEV, BK == 1 && VAEQ_NN_LEAN>(l, sps, k2, B, AS, zb, th, w2t, a2);
+        nn_fc2<NT, NLEV>(l, sps, k2, B, AS, zb, th, w2t, a2);
         __syncthreads();
         NN_STAMP(2);
         // ---- P3: per-axis softmax -> q (in place), moments, entropy term; item = (axis, n)
@@ -356,7 +333,6 @@ __global__ __launch_bounds__(NT, (NLEV == 2 && NT <= 512) ? 4 : (NT / 256 > 0 ? 
             }
         }
         __syncthreads();
-        if constexpr (PREF) { if (s + 1 < a.steps) load_minibatch(s + 1); }
         NN_STAMP(6);
         // ---- P7a: fc2 weight / bias gradients: one wave per (input channel, group of 4 taps); pseudo group at the end: the biases
         if constexpr (MF) {
@@ -495,7 +471,6 @@ __global__ __launch_bounds__(NT, (NLEV == 2 && NT <= 512) ? 4 : (NT / 256 > 0 ? 
         step += 1;
         b1t *= 0.9;
         b2t *= 0.999;
-        if constexpr (PREF) { if (s + 1 < a.steps) store_minibatch(); }
         if (!a.no_update) {
             // (hardware reciprocal / square root, 1 ulp each: the step changes by ~2e-7 relative -- as in the DP wave kernel)
             const float rbc2s = (float)(1.0 / sqrt(1.0 - b2t)), ss = (float)(lr / (1.0 - b1t));

@@ -12,13 +12,6 @@
 #include "vaeq_validate.h"
 #include "vaeq_wave.h"
 
-#ifndef VAEQ_NN_PREF
-#define VAEQ_NN_PREF 0                                 // 1: baked 64-QAM `Net` kernel fetches the next minibatch into registers during the step (measured: no gain, 16 spilled registers)
-#endif
-#ifndef VAEQ_NN_LEAN
-#define VAEQ_NN_LEAN 0                                 // 1: ... its forward convolutions with the k-step loop kept a loop (measured: -4 %)
-#endif
-
 #ifndef VAEQ_NN_MFMA8
 #define VAEQ_NN_MFMA8 1                                // 16-QAM (8 channels) on the 16-row MFMA path of 64-QAM, rows 8..15 zero (0: the vector-ALU path)
 #endif
@@ -207,9 +200,9 @@ __device__ __forceinline__ void nn_transpose_weights(const NNLayout &l, int k1, 
 // D[m = 4 (lane >> 4) + reg][n = lane & 15].  M is always the 16 channels.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Sum over the 64 lanes on the vector ALU (DPP row operations + four v_readlane; the form of vaeq_wave.h's wave_sum_dpp): vaeq_common.h's wave_sum is
+// Sum over the 64 lanes on the vector ALU (DPP row operations + four v_readlane; the row sums as in vaeq_wave.h's wave_sum_dpp): vaeq_common.h's wave_sum is
 // a butterfly of six ds_bpermute, i.e. six DEPENDENT LDS round trips -- the BatchNorm statistics take four such sums per channel.  Fixed order.
-// (not folded into wave_sum_dpp: with VAEQ_SUM_BCAST = 1 that one ends on two DPP broadcasts + one v_readlane, other instructions than these)
+// (not folded into wave_sum_dpp: that one ends on two DPP broadcasts + one v_readlane, other instructions than these)
 __device__ __forceinline__ float wave_sum_fast(float v)
 {
     v += dpp_f<0xB1>(v);                                       // quad_perm:[1,0,3,2]
@@ -244,48 +237,10 @@ __device__ __forceinline__ void nn_block_reduce3(float a, float b, float c, floa
 // read from a CLAMPED (always valid) address feeds a select: an ordinary load is sunk into a branch of its own behind its own s_waitcnt lgkmcnt(0)
 // (the backend will not speculate it), i.e. one exposed LDS round trip per operand -- the pattern round 3 found in the epilogue kernel and, with the ISA
 // in hand, here: 35 such branches per tile group of the transposed convolution.
-// lds1 = ldsv under -DVAEQ_NN_PIN=1: the MFMA loops below fetch the operands of the NEXT k-steps before the matrix instructions of the current ones, and
-// the backend's occupancy-driven scheduler undoes that (each operand read lands directly in front of its v_mfma).  Pinning reads + scheduling fences
-// restores the source order (ISA: twelve reads in flight behind ten back-to-back v_mfma) -- and MEASURES 3.7 % SLOWER (212.6 vs 205.0 us per 2048-run
-// step): with two waves per SIMD the load-use order of one wave interleaves with the other's matrix passes well enough.  Off by default.
-#ifndef VAEQ_NN_PIN
-#define VAEQ_NN_PIN 0                                  // measured: the pinned pipeline is 3.7 % SLOWER than the backend's load-use order (see lds1 below)
-#endif
-__device__ __forceinline__ float lds1(const float *p)
-{
-#if VAEQ_NN_PIN
-    return *(lds_cvf *)p;
-#else
-    return *p;
-#endif
-}
-// ... and the matrix instructions must not be hoisted up to "their" loads either (pure operations: the scheduler places each directly behind the
-// read that feeds it, which is the same exposed round trip again): nothing crosses this fence
-__device__ __forceinline__ void sched_fence()
-{
-#if VAEQ_NN_PIN
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
-#ifndef VAEQ_NN_PIN_WG
-#define VAEQ_NN_PIN_WG 0                               // the same for the weight-gradient loops alone (A/B)
-#endif
-__device__ __forceinline__ float lds1w(const float *p)
-{
-#if VAEQ_NN_PIN_WG
-    return *(lds_cvf *)p;
-#else
-    return lds1(p);
-#endif
-}
-__device__ __forceinline__ void sched_fence_w()
-{
-#if VAEQ_NN_PIN_WG
-    __builtin_amdgcn_sched_barrier(0);
-#else
-    sched_fence();
-#endif
-}
+// lds1: the operand reads of the MFMA loops below, an ORDINARY load -- the backend places each read in front of the v_mfma it feeds, and with two waves
+// per SIMD that order beats reads pinned ahead of the matrix instructions.  It stays a function: the same loads written in place
+// compile to other instruction streams in 34 kernels (tools/compare_isa.py).
+__device__ __forceinline__ float lds1(const float *p) { return *p; }
 
 // Conv1d with 16 output channels:  D[c][col] = bias[c] + sum over the (input row, tap) pairs of  w * in[row rstride + tap + col cstep].
 // The 4 k-rows of a v_mfma_f32_16x16x4_f32 (lane group lg = lane >> 4) do NOT take four consecutive (row, tap) pairs: each group WALKS ITS OWN
@@ -297,7 +252,7 @@ __device__ __forceinline__ void sched_fence_w()
 //   wt[(4 t + lg) 16 + c] = weight of channel c for the pair group lg reaches at step t (0 where it has none): nn_transpose_weights
 // T k-steps (even: a trip = two k-steps; the operands of the next trip are fetched while the current 2 TB MFMAs run).  Columns past ncols (the last
 // tile, and tiles past the last one) are READ -- from padded or neighbouring, always finite LDS cells -- and dropped: no clamps.
-// out(c0, col, acc): the lane's channels c0 .. c0 + 3 of column col.
+// out(c0, col, acc): the lane's channels c0 .. c0 + 3 of column col.  LEAN: the k-step loop stays a loop (the half-minibatch kernel of vaeq_nn.hip).
 template <int NT, int TB, bool LEAN = false, typename OutF>
 __device__ __forceinline__ void mfma_conv16(const float *wt, int T, int lbase, int kdw, int rstride, const float *in, int cstep, int ncols,
                                             const float *bias, OutF out, int creal = 16)
@@ -332,12 +287,10 @@ __device__ __forceinline__ void mfma_conv16(const float *wt, int T, int lbase, i
                                                                         // behind wt (another LDS array) are fetched; neither is used
             ld(tn, a0, b0);
             ld(tn + 1, a1, b1);
-            sched_fence();
 #pragma unroll
             for (int u = 0; u < TB; u++) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(x0, y0[u], acc[u], 0, 0, 0);
 #pragma unroll
             for (int u = 0; u < TB; u++) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1, y1[u], acc[u], 0, 0, 0);
-            sched_fence();
         };
         if constexpr (LEAN) {
 #pragma unroll 1
@@ -399,7 +352,7 @@ __device__ __forceinline__ void mfma_wgrad16(const float *g, int gstride, int nr
             const int sa = 4, sb = 4 * rstep;
             float an[4], bn[4];
 #pragma unroll
-            for (int q = 0; q < 4; q++) { an[q] = lds1w(pa + q * sa); bn[q] = lds1w(pb + q * sb); }       // (in range even when nmain == 0: rows < 4 t0 + 16 <= padded arrays)
+            for (int q = 0; q < 4; q++) { an[q] = lds1(pa + q * sa); bn[q] = lds1(pb + q * sb); }       // (in range even when nmain == 0: rows < 4 t0 + 16 <= padded arrays)
             if constexpr (ROW1) {
                 // two operand sets alternate (no register copies): trip m + 1 is fetched before trip m's matrix instructions, trip m + 2 before those of m + 1
                 float a1[4], b1[4];
@@ -411,16 +364,12 @@ __device__ __forceinline__ void mfma_wgrad16(const float *g, int gstride, int nr
                 for (; m + 2 <= nmain; m += 2) {
                     pa += 4 * sa; pb += 4 * sb;
 #pragma unroll
-                    for (int q = 0; q < 4; q++) { a1[q] = lds1w(pa + q * sa); b1[q] = lds1w(pb + q * sb); }
-                    sched_fence_w();
+                    for (int q = 0; q < 4; q++) { a1[q] = lds1(pa + q * sa); b1[q] = lds1(pb + q * sb); }
                     mma(an, bn);
-                    sched_fence_w();
                     pa += 4 * sa; pb += 4 * sb;
 #pragma unroll
-                    for (int q = 0; q < 4; q++) { an[q] = lds1w(pa + q * sa); bn[q] = lds1w(pb + q * sb); }   // (past the last trip: read, never used)
-                    sched_fence_w();
+                    for (int q = 0; q < 4; q++) { an[q] = lds1(pa + q * sa); bn[q] = lds1(pb + q * sb); }   // (past the last trip: read, never used)
                     mma(a1, b1);
-                    sched_fence_w();
                 }
                 if (m < nmain) mma(an, bn);
             } else
@@ -430,11 +379,9 @@ __device__ __forceinline__ void mfma_wgrad16(const float *g, int gstride, int nr
                 for (int q = 0; q < 4; q++) { av[q] = an[q]; bv[q] = ones ? 1.0f : bn[q]; }
                 if (m + 1 < nmain) { pa += 4 * sa; pb += 4 * sb; }
 #pragma unroll
-                for (int q = 0; q < 4; q++) { an[q] = lds1w(pa + q * sa); bn[q] = lds1w(pb + q * sb); }
-                sched_fence_w();
+                for (int q = 0; q < 4; q++) { an[q] = lds1(pa + q * sa); bn[q] = lds1(pb + q * sb); }
 #pragma unroll
                 for (int q = 0; q < 4; q++) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc[q], 0, 0, 0);
-                sched_fence_w();
             }
             for (int t = t0 + 4 * nmain; t < t1; t += 4) {
                 float av[4], bv[4];
@@ -468,7 +415,7 @@ __device__ __forceinline__ void mfma_wgrad16(const float *g, int gstride, int nr
 
 // Backward through the strided Conv1d fc2 (16 -> 16 channels):  gz[cc][s] = sum_{c, k : (s + p2 - k) % sps == 0} w2u[(k 16 + c) 16 + cc] * g2[c GS + (s + p2 - k) / sps],
 // one polyphase component of s at a time (for each only every sps-th tap contributes).  g2 = dL/dlogits in the ZERO-GUARDED layout of nn_layout (row
-// stride GS, columns -A0 .. 16 ceil(B / 16) + A0 - 1 readable, zeros outside [0, B)): every operand read is unconditional and pinned, the operands of
+// stride GS, columns -A0 .. 16 ceil(B / 16) + A0 - 1 readable, zeros outside [0, B)): every operand read is unconditional, the operands of
 // the next tap are in flight while the current tap's 4 TB matrix instructions run, and the epilogue reads what it needs of the old buffer (pre) for
 // all its outputs before it writes any (post) -- round 2's form had each of these reads in a branch of its own behind its own s_waitcnt lgkmcnt(0)
 // (35 exposed LDS round trips per tile group: 4.1 us for 0.8 us of matrix passes).
@@ -505,14 +452,10 @@ __device__ __forceinline__ void mfma_convT16(const float *w2u, int k2, int p2, i
             if (nk > 0) ld(0, av[0], bv[0]);
             for (int kj = 0; kj < nk; kj += 2) {                                     // two register sets alternate (no copies)
                 if (kj + 1 < nk) ld(kj + 1, av[1], bv[1]);
-                sched_fence();
                 mm(av[0], bv[0]);
-                sched_fence();
                 if (kj + 1 < nk) {
                     if (kj + 2 < nk) ld(kj + 2, av[0], bv[0]);
-                    sched_fence();
                     mm(av[1], bv[1]);
-                    sched_fence();
                 }
             }
             float old[TB][4];
@@ -522,7 +465,6 @@ __device__ __forceinline__ void mfma_convT16(const float *w2u, int k2, int p2, i
 #pragma unroll
                 for (int t = 0; t < 4; t++) old[u][t] = pre(4 * lg + t, sps * mc + ph);
             }
-            sched_fence();
 #pragma unroll
             for (int u = 0; u < TB; u++) {
                 const int m = (tg + u) * 16 + lc;
