@@ -256,6 +256,23 @@ int vaeq_dp_epilogue_compact(int32_t R, int64_t N, int32_t n_lev, int32_t batch_
                              const void *tx_f16, const float *amp, const float *var, const float *nu_sc, float *ser, int32_t *shift,
                              int32_t *r_flag, void *stream);
 
+/* Information-rate figures of one DP frame, per run and polarisation, over exactly the symbols the soft-demapper SER of vaeq_dp_epilogue keeps
+ * (shift[R][2] / rflag[R] = that call's path-0 alignment: the same roll, polarisation exchange, per-minibatch cut and frame-edge slice).
+ * Exactly one of q[R][2][2*n_lev][N] (posteriors as stored) and y[R][2][2][N] (equalised samples; the posteriors are recomputed by the soft
+ * demapper's formula with var[R][2] / nu_sc[R], in the log domain -- the form for the compact pipeline, which never materialises q) is given;
+ * var and nu_sc may be NULL with q.  tx_f16[R][2][2][N] IEEE half, amp[n_lev], P[R][n_lev] the runs' per-axis pmf.
+ * Level i carries the binary-reflected Gray label g(i) = i ^ (i >> 1), b = log2 n_lev bits per axis; H = -sum P log2 P.  Of the eight
+ * hypotheses h = 4 flip + rot (rot: 0, pi, pi/2, 3 pi/2; shared_funcs.py:188-222) the one with the fewest symbol errors of argmax(q) wins, ties
+ * to the smallest h, so sym_err / kept IS the soft-demapper SER.  Under it, with l(x) = log2 max(x, FLT_MIN) (y-mode: an exact log-softmax):
+ *   AIR = 2 H + mean[l(q_I[t_I]) + l(q_Q[t_Q])]                                   (symbol-wise mismatched decoding, bit per 2-D symbol)
+ *   GMI = 2 H + mean sum_axis sum_k l(sum of q_axis[i] over the i whose label bit k equals that of the transmitted level)
+ *   BER = bit_err / (2 b kept), bit_err = differing label bits between decided and transmitted level, both axes
+ * (NGMI = 1 - (2 H - GMI) / (2 b) is the host's).  info[R][2][3] = AIR, GMI, BER; counts[R][2][4] = kept, sym_err, bit_err, hyp.  An empty
+ * window gives NaN figures and zero counts.  q is read once; sums run in a fixed order without float atomics: two calls give identical bits. */
+int vaeq_dp_epilogue_info(int32_t R, int64_t N, int32_t n_lev, int32_t batch_len, const float *q, const float *y, const void *tx_f16,
+                          const float *amp, const float *P, const float *var, const float *nu_sc, const int32_t *shift,
+                          const int32_t *rflag, float *info, int32_t *counts, void *stream);
+
 /* The two-stage epilogue of the constant-modulus baselines in one launch (optical_DP_channel/func_CMA_DP_MQAM_shaping.py:39-52 after the phase
  * estimation; the CMAbatch / CMAflex modules are identical there): the constellation stage FIRST (find_shift_symb_full on y, roll / cut,
  * SER_constell_shaping), whose mean-radius normalisation stays in the kept window of the aligned output (the reference normalises a slice view in place,

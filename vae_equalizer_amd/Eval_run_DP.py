@@ -40,7 +40,11 @@ N_frame_max = 10000
 
 savePATH = ""
 base_seed = None    # int -> reproducible runs (run i of the flattened sweep uses base_seed + 1000*i); None = like the reference
+info_metrics = False  # True (VAE / VAEflex): the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), shaped like SER with a leading axis of 2
 generator = None    # None: "hip" (on-device channel simulator) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set; or force "numpy" / "hip" / "torch"
+
+
+INFO_KEYS = ("GMI", "NGMI", "AIR", "BER")
 
 
 def sweep_points():
@@ -72,7 +76,8 @@ def main():
     # one batch per problem shape (M, batch_len, flex_step) and symbol rate (the device generators simulate one rate per call)
     key = lambda i: (points[i][1]["M"], points[i][1]["batch_len"], points[i][1]["flex_step"], points[i][1]["symb_rate"])
     shapes = sorted({key(i) for i in mine})
-    local = torch.zeros(len(mine), 8, num_frames, dtype=torch.float32)
+    n_col = 16 if info_metrics else 8                      # with info_metrics: + GMI[2] | NGMI[2] | AIR[2] | BER[2]
+    local = torch.zeros(len(mine), n_col, num_frames, dtype=torch.float32)
     for (M, batch_len, fs, rate) in shapes:
         sel = [k for k, i in enumerate(mine) if key(i) == (M, batch_len, fs, rate)]
         runs = [DPRun(points[mine[k]][1]["SNR"], points[mine[k]][1]["nu"], points[mine[k]][1]["theta_diff"], points[mine[k]][1]["theta"],
@@ -84,12 +89,18 @@ def main():
                               device=device, generator=generator if generator in (None, "numpy", "hip") else "hip", verbose=False)
         elif loss_type in ('VAE', 'VAEflex'):
             r = run_dp_batch(runs, mod, sps, M, batch_len, N_frame_max, num_frames, fs, channel, tau_cd, tau_pmd, phiIQ, N_lrhalf,
-                             flex=(loss_type == 'VAEflex'), device=device, generator=generator, verbose=False)
+                             flex=(loss_type == 'VAEflex'), device=device, generator=generator, verbose=False,
+                             want_info=info_metrics)
         else:
             raise NameError(f"loss_type {loss_type!r}: the reference leaves `process` undefined (:56-65)")
         local[sel, 0:4] = r["SER"]
         local[sel, 4:6] = r["Var_est"]
         local[sel, 6:8] = r["var"].unsqueeze(-1).expand(-1, -1, num_frames)
+        if info_metrics:
+            if "info" not in r:
+                raise ValueError(f"info_metrics is defined for loss_type 'VAE' and 'VAEflex', not {loss_type!r}")
+            for j, k in enumerate(INFO_KEYS):
+                local[sel, 8 + 2 * j:10 + 2 * j] = r["info"][k]
     rows = sweep.gather_rows(local, len(points), rank, world)
     if rank != 0:
         return None
@@ -101,6 +112,12 @@ def main():
     save_dict = {'SER': SER.numpy(), 'Var_est': Var_est.numpy(), 'var_real': var_real.numpy(), 'SNR': SNR_vec, 'nu': nu_vec,
                  'theta_diff': theta_diff_vec, 'theta': theta_vec, 'M': M_vec, 'lr': lr_optim_vec, 'batch_len': batch_len_vec,
                  'symb_rate': symb_rate_vec, 'symb_step': flex_step_vec}
+    if info_metrics:
+        for j, name_k in enumerate(INFO_KEYS):
+            arr = torch.empty(2, *shape_tail, num_frames, dtype=torch.float32)
+            for k, (idx, _) in enumerate(points):
+                arr[(slice(None),) + idx] = rows[k, 8 + 2 * j:10 + 2 * j]
+            save_dict[name_k] = arr.numpy()
     io.savemat(name, {'dict': save_dict})
     return name, save_dict
 

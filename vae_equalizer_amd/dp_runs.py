@@ -15,7 +15,7 @@ import torch
 
 from . import channel as ch
 from . import shared_funcs as sfun
-from .engine import DPEngine, dp_epilogue, dp_epilogue_compact  # noqa: F401
+from .engine import DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info  # noqa: F401
 
 
 @dataclass
@@ -84,6 +84,7 @@ def check_one_symb_rate(runs, generator):
 
 
 _SIDE = {}
+INFO_FLOAT, INFO_INT = ("AIR", "GMI", "NGMI", "BER"), ("kept", "sym_err", "bit_err", "hyp")
 
 
 def _side_streams(device):
@@ -108,13 +109,16 @@ def default_device():
 
 
 def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex_step, channel, tau_cd, tau_pmd, phiIQ,
-                 N_lrhalf, flex=False, device=None, generator=None, verbose=False, threads=0, keep_last=False):
+                 N_lrhalf, flex=False, device=None, generator=None, verbose=False, threads=0, keep_last=False, want_info=False):
     """Train + evaluate R runs.  Returns dict(SER[R,4,num_frames], Var_est[R,2,num_frames], var[R,2]) on the CPU.
 
     generator: None    = "hip" when no run carries a seed, "numpy" otherwise (resolve_generator);
                "numpy" = reference-faithful host simulator per run (seeded per run when DPRun.seed is set);
                "hip"   = on-device simulator, HIP kernels + hipFFT, Philox streams keyed by the first run's seed (row f1);
                "torch" = batched on-device simulator (channel.generate_batch_gpu), seeded from the first run's seed.
+    want_info: also dict(AIR, GMI, NGMI, BER [R,2,num_frames] f32; kept, sym_err, bit_err, hyp [R,2,num_frames] int64) under "info":
+               engine.dp_epilogue_info after every frame's epilogue, on its soft-demapper alignment -- from y on the compact path, from q in
+               a frame whose q is materialised (keep_last).  Every other output is the same with and without it.
     """
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
@@ -156,6 +160,11 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
     # per-frame results stay on the device until the end: no host synchronisation inside the frame loop (unless verbose)
     SER = torch.empty(R, 4, num_frames, dtype=torch.float32, device=device)
     Var_est = torch.empty(R, 2, num_frames, dtype=torch.float32, device=device)
+    INFO = None
+    if want_info:
+        P_t = torch.tensor(P, dtype=torch.float32, device=device)
+        INFO = {k: torch.empty(R, 2, num_frames, dtype=torch.float32 if k in INFO_FLOAT else torch.int64, device=device)
+                for k in INFO_FLOAT + INFO_INT}
     last = None
     SNRs = np.array([r.SNR for r in runs], dtype=np.float32)
     hip_seed = (int(runs[0].seed) if runs[0].seed is not None else fresh_seed()) if generator == "hip" else None
@@ -201,6 +210,15 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
         Var_est[:, :, frame] = ve.mean(dim=2)                                   # :69
         res = dp_epilogue_compact(out["eq"][:, 0], out["dec"][:, 0], out["y"][:, 0], data, amp, nu_sc_t, var, None if flex else batch_len)
         SER[:, :, frame] = res["SER"]
+        if want_info:
+            bl = None if flex else batch_len
+            if out.get("q") is not None:
+                fig = dp_epilogue_info(q=out["q"][:, 0], data=data, amp_levels=amp, P=P_t, shift=res["shift_q"], r=res["r_q"], batch_len=bl)
+            else:
+                fig = dp_epilogue_info(y=out["y"][:, 0], data=data, amp_levels=amp, P=P_t, nu_sc=nu_sc_t, var=var, shift=res["shift_q"],
+                                       r=res["r_q"], batch_len=bl)
+            for k in INFO:
+                INFO[k][:, :, frame] = fig[k]
         return res, ve
 
     # Small batches (fewer runs than the device keeps resident: the script-faithful sweeps, 15 ... 300 runs) leave most of the chip idle
@@ -259,6 +277,8 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
             if keep_last and frame == num_frames - 1:
                 last = dict(q=out["q"][:, 0] if need_q else None, y=out["y"][:, 0], data=data, rx=rx, **res)
     ret = dict(SER=SER.cpu(), Var_est=Var_est.cpu(), var=torch.tensor(var_np), engine=eng)
+    if INFO is not None:
+        ret["info"] = {k: v.cpu() for k, v in INFO.items()}
     if last is not None:
         ret["last"] = last
     return ret

@@ -6,6 +6,7 @@ This is the host side of the C ABI (include/vaeq.h).  It mirrors what one call o
 once, because on an MI355X the sweep (Eval_run_DP.py:68-86), not the single run, is the unit of parallelism.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -427,6 +428,40 @@ def dp_epilogue_compact(eq, dec, y, data, amp_levels, nu_sc, var, batch_len=None
                                                      nat.ptr(shift, torch.int32), nat.ptr(rflag, torch.int32), nat.current_stream(dev)),
                   "vaeq_dp_epilogue_compact")
     return dict(SER=ser, shift_q=shift[:, 0].long(), r_q=rflag[:, 0].long(), shift_c=shift[:, 1].long(), r_c=rflag[:, 1].long())
+
+
+def dp_epilogue_info(q=None, y=None, data=None, amp_levels=None, P=None, nu_sc=None, var=None, shift=None, r=None, batch_len=None):
+    """Information-rate figures of one frame on the device (vaeq_dp_epilogue_info), over exactly the symbols dp_epilogue's soft-demapper SER keeps:
+    exactly one of q[R,2,2n,N] and y[R,2,2,N] (y: the posteriors are recomputed by the soft demapper from var / nu_sc, in the log domain),
+    data[R,2,2,N] fp16, P[R,n] (or [n]) the per-axis pmf, shift[R,2] / r[R] = dp_epilogue's shift_q / r_q ->
+    dict(AIR[R,2], GMI[R,2], NGMI[R,2], BER[R,2] f32 (NaN where nothing is kept); kept, sym_err, bit_err, hyp [R,2] int64).
+    AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
+    if (q is None) == (y is None):
+        raise ValueError("dp_epilogue_info takes exactly one of q and y")
+    src = q if y is None else y
+    dev, R, N = src.device, src.shape[0], src.shape[-1]
+    amp = _f32(amp_levels, dev).reshape(-1)
+    n = amp.numel()
+    P = _f32(P, dev).reshape(-1, n).expand(R, n).contiguous()
+    var_t = nu_t = None
+    if y is not None:
+        var_t = _f32(var, dev).expand(R, 2).contiguous()
+        nu_t = _f32(nu_sc, dev).expand(R).contiguous()
+    src = src.contiguous()
+    data = data.to(torch.float16).contiguous()
+    shift = torch.as_tensor(shift, device=dev).to(torch.int32).reshape(R, 2).contiguous()
+    r = torch.as_tensor(r, device=dev).to(torch.int32).reshape(R).contiguous()
+    info = torch.empty(R, 2, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(R, 2, 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_dp_epilogue_info(R, N, n, int(batch_len or 0), nat.ptr(src if y is None else None), nat.ptr(src if y is not None else None),
+                                                  nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(P), nat.ptr(var_t), nat.ptr(nu_t),
+                                                  nat.ptr(shift, torch.int32), nat.ptr(r, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32),
+                                                  nat.current_stream(dev)), "vaeq_dp_epilogue_info")
+    H = -(P * torch.where(P > 0, torch.log2(P.clamp_min(torch.finfo(torch.float32).tiny)), torch.zeros_like(P))).sum(1, keepdim=True)
+    gmi = info[:, :, 1]
+    return dict(AIR=info[:, :, 0], GMI=gmi, NGMI=1.0 - (2.0 * H - gmi) / (2.0 * math.log2(n)), BER=info[:, :, 2],
+                kept=counts[:, :, 0].long(), sym_err=counts[:, :, 1].long(), bit_err=counts[:, :, 2].long(), hyp=counts[:, :, 3].long())
 
 
 def cma_epilogue(y, data, amp_levels, nu_sc, var):
