@@ -314,8 +314,8 @@ int vaeq_gen_dp_finish(int32_t R, int32_t N, int32_t sps, int32_t Ls, int32_t Lr
  *   staged  any other shape (or env VAEQ_GEN_STAGED=1): the three stage kernels around in-place hipFFT transforms, plans cached per (Lrow, R).
  * power_ws: [R][vaeq_gen_dp_power_parts(Lrow)] floats -- for sps == 2 the first pass leaves partial sums of |sig|^2 there and the noise level
  * (:83) is derived from them: the fibre's transfer matrix is unitary at every frequency (:38-54), the dispersed signal has the power of the
- * undispersed one, so no pass over the dispersed signal is spent on it (other sps: the first R floats, filled by a power pass as in
- * vaeq_gen_dp_finish). */
+ * undispersed one, so no pass over the dispersed signal is spent on it (other sps: the first R floats, filled by a power pass over the
+ * first Ls samples of every row, likewise BEFORE the fibre: on a padded row the dispersed signal leaves some energy in the pad). */
 int32_t vaeq_gen_dp_power_parts(int32_t Lrow);               /* max(8, 2 * ceil(Lrow / 2048)) */
 int vaeq_gen_dp_frame(int32_t R, int32_t N, int32_t N_conv, int32_t sps, int32_t n_lev, int32_t Lg, int32_t Ls, int32_t Lrow,
                       int32_t ref_offset, const float *amp, const float *cdf, const float *g_complex, const float *snr_db,

@@ -6,23 +6,12 @@ import numpy as np
 import pytest
 import torch
 
+from _ref_generator import philox4x32_10, u01
 from vae_equalizer_amd import channel as ch
 from vae_equalizer_amd import shared_funcs as sfun
 
 pytestmark = pytest.mark.gpu
 DP = dict(symb_rate=90e9, tau_cd=-26e-24, tau_pmd=0.1e-12 * np.sqrt(1000), phiIQ=np.array([0.0314, 0.0314], dtype=np.complex64))
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """numpy Philox4x32-10 (Salmon et al.), vectorised over uint64 arrays holding 32-bit words."""
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & M32 for c in np.broadcast_arrays(c0, c1, c2, c3))
-    k0, k1 = np.uint64(k0) & M32, np.uint64(k1) & M32
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & M32, p1 & M32, ((p0 >> np.uint64(32)) ^ c3 ^ k1) & M32, p0 & M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
 
 
 def host_symbols(seed, frame, run, pol, n_idx, cdf):
@@ -30,7 +19,7 @@ def host_symbols(seed, frame, run, pol, n_idx, cdf):
     key = ch._mix_seed(seed, 0)
     x, y, z, w = philox4x32_10(n_idx >> 1, run, frame, pol, key & 0xFFFFFFFF, key >> 32)
     odd = (n_idx & 1).astype(bool)
-    u = lambda v: ((v >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+    u = u01
     lev = lambda uu: (uu[:, None] >= cdf[None, :-1].astype(np.float32)).sum(1)
     return lev(u(np.where(odd, z, x))), lev(u(np.where(odd, w, y)))
 

@@ -488,9 +488,9 @@ def generate_data_rc(N, amps, SNR, h_channel, nu, sps=1, rng=None, noise=None):
     return rx, ref, P.astype(np.float32)
 
 
-def generate_dfe_batch_hip(R, N, amps, P, SNR, h_channel, device, seed, frame, sigma_fixed=None):
+def generate_dfe_batch_hip(R, N, amps, P, SNR, h_channel, device, seed, frame, sigma_fixed=None, return_sigma=False):
     """generate_data_rc for R frames on the device (vaeq_gen_awgn at sps = 1 with the raised-cosine geometry): deterministic in
-    (seed, frame, run).  SNR scalar or [R].  Returns (rx[R,2,N] f32, data[R,2,N] f16)."""
+    (seed, frame, run).  SNR scalar or [R].  Returns (rx[R,2,N] f32, data[R,2,N] f16[, sigma_n[R]])."""
     import ctypes as C
 
     from . import _native as nat
@@ -513,4 +513,4 @@ def generate_dfe_batch_hip(R, N, amps, P, SNR, h_channel, device, seed, frame, s
                                           None if sigma_fixed is None else
                                           nat.ptr(_dev_const(np.broadcast_to(np.asarray(sigma_fixed, np.float32), (R,)), torch.float32, dev)),
                                           nat.current_stream(dev)), "vaeq_gen_awgn")
-    return rx, data
+    return (rx, data, sigma) if return_sigma else (rx, data)

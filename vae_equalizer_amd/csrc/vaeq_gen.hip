@@ -416,10 +416,11 @@ static void launch_tx(int R, int npol, int N, int N_conv, int sps, int n_lev, in
 
 static void launch_finish(int R, int npol, int N, int sps, int Ls, int Lrow, const float *snr_db, uint64_t seed, uint32_t frame,
                           const float2 *sig, float *power_ws, float *rx, float *sigma_out, hipStream_t st, const float *sigma_fixed = nullptr,
-                          int n_parts = 0)
+                          int n_parts = 0, bool power_done = false)
 {
     const int Lout = sps * N, nj = (Lout + 1) / 2;
-    if (!sigma_fixed && n_parts == 0) hipLaunchKernelGGL(gen_power_kernel, dim3(R), dim3(256), 0, st, Ls, Lrow, npol, sig, power_ws);
+    // power_done: power_ws[run] already holds the mean power (taken by the caller before the fibre)
+    if (!sigma_fixed && n_parts == 0 && !power_done) hipLaunchKernelGGL(gen_power_kernel, dim3(R), dim3(256), 0, st, Ls, Lrow, npol, sig, power_ws);
     if (!sigma_fixed && n_parts > 0) hipLaunchKernelGGL(gen_sigma_kernel, dim3((R + 255) / 256), dim3(256), 0, st, R, n_parts, npol, Ls, sps, snr_db, power_ws);
     hipLaunchKernelGGL(gen_finish_kernel, dim3((nj + 255) / 256 > 64 ? 64 : (nj + 255) / 256, npol, R), dim3(256), 0, st, Lrow, Lout, sps, snr_db,
                        power_ws, seed, frame, npol, sig, rx, sigma_out, sigma_fixed, n_parts, Ls);
@@ -650,12 +651,15 @@ extern "C" int vaeq_gen_dp_frame(int32_t R, int32_t N, int32_t N_conv, int32_t s
     const int n_parts = sps == 2 ? 2 * ((Lrow + vaeq::TX_TILE - 1) / vaeq::TX_TILE) : 0;
     vaeq::launch_tx(R, 2, N, N_conv, sps, n_lev, Lg, Ls, Lrow, ref_offset, amp, cdf, reinterpret_cast<const float2 *>(g_complex), seed, frame, sig,
                     reinterpret_cast<__half *>(data_f16), st, n_parts ? power_ws : nullptr);
+    // other sps: the mean power of the first Ls samples, likewise BEFORE the fibre -- on a zero-padded row (Lrow > Ls) the dispersed signal leaks a
+    // little of its energy into the pad, so the power of its first Ls samples is not the power the noise level is defined by
+    if (!n_parts) hipLaunchKernelGGL(vaeq::gen_power_kernel, dim3(R), dim3(256), 0, st, Ls, Lrow, 2, sig, power_ws);
     if (hipfftExecC2C(plan, reinterpret_cast<hipfftComplex *>(sig), reinterpret_cast<hipfftComplex *>(sig), HIPFFT_FORWARD) != HIPFFT_SUCCESS)
         return VAEQ_ERR_LAUNCH;
     hipLaunchKernelGGL(vaeq::gen_disperse_kernel, dim3((Lrow + 255) / 256, R), dim3(256), 0, st, Lrow, fs / (double)Lrow, tau_cd, tau_pmd,
                        make_float2(e0_re, e0_im), make_float2(e1_re, e1_im), 1.0f / (float)Lrow, theta, sig);
     if (hipfftExecC2C(plan, reinterpret_cast<hipfftComplex *>(sig), reinterpret_cast<hipfftComplex *>(sig), HIPFFT_BACKWARD) != HIPFFT_SUCCESS)
         return VAEQ_ERR_LAUNCH;
-    vaeq::launch_finish(R, 2, N, sps, Ls, Lrow, snr_db, seed, frame, sig, power_ws, rx, sigma_out, st, nullptr, n_parts);
+    vaeq::launch_finish(R, 2, N, sps, Ls, Lrow, snr_db, seed, frame, sig, power_ws, rx, sigma_out, st, nullptr, n_parts, true);
     return hipGetLastError() == hipSuccess ? VAEQ_OK : VAEQ_ERR_LAUNCH;
 }
