@@ -255,6 +255,7 @@ extern "C" int vaeq_awgn_cma(int32_t R, int64_t N, int32_t sps, int32_t M, int32
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!rx || !h || !lr || !loss) return VAEQ_ERR_NULL;
     auto k = M <= 31 ? vaeq::awgn_cma_kernel<true> : vaeq::awgn_cma_kernel<false>;
+    vaeq::note_kernel("vaeq::awgn_cma_kernel<%s>", M <= 31 ? "true" : "false");
     return vaeq::launch(k, dim3(R), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), (int)N, sps, M, update ? 1 : 0, rx, R_mod, h, lr, loss, out, e);
 }
 
@@ -283,6 +284,7 @@ extern "C" int vaeq_awgn_cma_validate(int32_t R, int64_t N, int32_t sps, int32_t
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *d = reinterpret_cast<const __half *>(data_f16);
     float2 *w = reinterpret_cast<float2 *>(ws);
+    vaeq::note_kernel("vaeq::awgn_cma_validate_kernel<%s>", lds ? "true" : "false");
     if (lds)
         return vaeq::launch(vaeq::awgn_cma_validate_kernel<true>, dim3(R), dim3(vaeq::AV_NT), (size_t)K * sizeof(float2), st, (int)N, sps, M, n_lev, n_shift,
                             rx, h, amp, d, w, ser, shift, cpe_out);

@@ -342,6 +342,7 @@ static void launch_dfe_recursion(hipStream_t st, int R, int N, int K2, int C, in
 {
     hipLaunchKernelGGL((dfe_spec_kernel<NL, K2M>), dim3((R * C + 255) / 256), dim3(256), 0, st, R, N, K2, C, CH, W, ff, fb, amp, init, dec, spec);
     hipLaunchKernelGGL((dfe_repair_kernel<NL, K2M>), dim3(R), dim3(64), 0, st, N, K2, C, CH, ff, fb, amp, dec, spec, repairs);
+    note_kernel("vaeq::dfe_repair_kernel<%d, %d>", NL, K2M);   // the spec kernel carries the same template arguments
 }
 
 }  // namespace vaeq
