@@ -273,6 +273,39 @@ int vaeq_dp_epilogue_info(int32_t R, int64_t N, int32_t n_lev, int32_t batch_len
                           const float *amp, const float *P, const float *var, const float *nu_sc, const int32_t *shift,
                           const int32_t *rflag, float *info, int32_t *counts, void *stream);
 
+/* vaeq_awgn_validate for rows under its 64 symbols: the same arguments, results and kernel for 23 + n_shift / 2 <= N < 64 (every shift the
+ * search can return, at most n_shift / 2, still keeps a symbol); any other N is VAEQ_ERR_SHAPE, every other refusal is vaeq_awgn_validate's.
+ * The reference has no lower limit on the validation frame; vaeq_awgn_validate keeps its own. */
+int vaeq_awgn_validate_short(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t n_shift, const float *x, const float *W,
+                             const float *amp, const float *amp_mean, const float *var, const void *data_f16, float *y_ws, float *ser,
+                             int32_t *shift, void *stream);
+
+/* Information-rate figures of one AWGN validation frame, per run, over exactly the symbols the SER_q of vaeq_awgn_validate / vaeq_nn_validate
+ * keeps: for shift[r] = sh the kept symbol j in [0, len), len = N - 22 - sh, pairs the posterior (or sample) 11 + sh + j with the TX symbol
+ * 11 + j (q[:, 11+sh : -11] against data[:, 11 : -11-sh], func_VAELE_MQAM_shaping.py:318).  The window is empty when 11 + sh <= 0 or len <= 0;
+ * no int32 shift takes an index out of [0, N).  One polarisation, four rotation hypotheses, no IQ flip (SER_q, :97-123).
+ * Exactly one of q[R][2*n_lev][N] (posteriors as stored: the output of vaeq_nn_forward) and y[R][2][N] (the un-normalised equaliser output the
+ * fused validation leaves in y_ws; amp_mean and var are required with it and may be NULL with q) is given.  data_f16[R][2][N] IEEE half,
+ * amp[n_lev], P[R][n_lev] the runs' per-axis pmf.
+ * Level i carries the binary-reflected Gray label g(i) = i ^ (i >> 1), S = n_lev - 1, b = log2 n_lev bits per axis; H = -sum P log2 P (a zero
+ * entry contributes 0).  TX level t = clamp(rint(S/2 tx + S/2), 0, S) per axis; the decision d_c is the first maximum of the posterior of axis c.
+ * Hypothesis h in {0, 1, 2, 3} = rotation by 0, pi, pi/2, 3 pi/2 maps (d_I, d_Q) to (d_I, d_Q), (S - d_I, S - d_Q), (S - d_Q, d_I),
+ * (d_Q, S - d_I), the posterior vectors likewise; the one with the fewest symbol errors wins, ties to the smallest h.  Under it, with
+ * l(x) = log2 max(x, FLT_MIN) in q-mode and an exact log-softmax in y-mode:
+ *   AIR = 2 H + mean[l(q_I'[t_I]) + l(q_Q'[t_Q])]                                 (symbol-wise mismatched decoding, bit per 2-D symbol)
+ *   GMI = 2 H + mean sum_axis sum_k l(sum of q_axis'[i] over the i whose label bit k equals that of the transmitted level)
+ *   BER = bit_err / (2 b kept), bit_err = sum popcount(g(d') ^ g(t)) over both axes
+ * (NGMI = 1 - (2 H - GMI) / (2 b) is the host's).  y-mode posteriors (:228-229): m_c = (sum_{n < N} |y_c[n]|) / N over the WHOLE row,
+ * yhat_c = y_c (amp_mean / m_c), z_i = -(yhat_c - a_i)^2 / var, posteriors = log-softmax of z; every bit-wise sum is a log-sum-exp around its own
+ * maximum, so nothing underflows.  A component with m_c == 0 has no normalisation: that run reports the empty-window result.  y-mode decides
+ * with its own sum for m_c, so sym_err / kept is the validation's SER except where a symbol lies within float32 rounding of a threshold.
+ * info[R][3] = AIR, GMI, BER; counts[R][4] = kept, sym_err, bit_err, hyp.  An empty window gives NaN figures and zero counts.  One workgroup
+ * per run; sums run in a fixed order without atomics: two calls give identical bits.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); both or neither of q and y is VAEQ_ERR_NULL, before any shape rule; R < 0, N < 1,
+ * N > 0x3fffffff or n_lev not in {2, 4, 8} is VAEQ_ERR_SHAPE. */
+int vaeq_awgn_info(int32_t R, int64_t N, int32_t n_lev, const float *q, const float *y, const void *data_f16, const float *amp, const float *P,
+                   const float *amp_mean, const float *var, const int32_t *shift, float *info, int32_t *counts, void *stream);
+
 /* The two-stage epilogue of the constant-modulus baselines in one launch (optical_DP_channel/func_CMA_DP_MQAM_shaping.py:39-52 after the phase
  * estimation; the CMAbatch / CMAflex modules are identical there): the constellation stage FIRST (find_shift_symb_full on y, roll / cut,
  * SER_constell_shaping), whose mean-radius normalisation stays in the kept window of the aligned output (the reference normalises a slice view in place,

@@ -22,7 +22,9 @@ epe = 2                 # epochs per evaluation
 
 savePATH = ""
 base_seed = None        # int -> reproducible runs; None = like the reference
+info_metrics = False    # True: the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), each shaped like SER
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
+INFO_KEYS = ("GMI", "NGMI", "AIR", "BER")
 
 
 def sweep_points():
@@ -42,22 +44,33 @@ def main():
         print('Run code on: ', device, f'({world} rank(s))')
     points = list(sweep_points())
     mine = sweep.my_slice(len(points), rank, world)
-    local = torch.zeros(len(mine), num_epochs // epe, dtype=torch.float32)
+    n_eval = num_epochs // epe
+    local = torch.zeros(len(mine), 1 + len(INFO_KEYS), n_eval, dtype=torch.float32) if info_metrics else torch.zeros(len(mine), n_eval, dtype=torch.float32)
     for b, (M, N_train) in enumerate(sorted({(points[i][1]["M"], points[i][1]["N_train"]) for i in mine})):   # one batch per problem shape
         sel = [k for k, i in enumerate(mine) if (points[i][1]["M"], points[i][1]["N_train"]) == (M, N_train)]
         runs = [dict(SNR=points[mine[k]][1]["SNR"], nu=points[mine[k]][1]["nu"], lr_optim=points[mine[k]][1]["lr"],
                      seed=None if base_seed is None else base_seed + 1000 * mine[k]) for k in sel]
-        local[sel] = run_awgn_batch(runs, mod, sps, M, N_train, N_valid, train_len, num_epochs, epe, channel, device=device,
-                                    generator=generator, seed=sweep.stream_seed(base_seed, rank, b))
+        r = run_awgn_batch(runs, mod, sps, M, N_train, N_valid, train_len, num_epochs, epe, channel, device=device,
+                           generator=generator, seed=sweep.stream_seed(base_seed, rank, b), want_info=info_metrics)
+        if info_metrics:                                       # per run: SER | GMI | NGMI | AIR | BER
+            local[sel] = torch.stack([r[0]] + [r[1][k] for k in INFO_KEYS], dim=1)
+        else:
+            local[sel] = r
     rows = sweep.gather_rows(local, len(points), rank, world)
     if rank != 0:
         return None
     SER = torch.empty(len(SNR_vec), 1, 1, len(M_vec), len(lr_optim_vec), len(N_train_vec), iter, num_epochs // epe, dtype=torch.float32)
     for k, (idx, _) in enumerate(points):
-        SER[idx] = rows[k]
+        SER[idx] = rows[k, 0] if info_metrics else rows[k]
     nu = nu_vec[-1]
     name = f"{savePATH}SERvsSNR_VAELE_shaping_{nu}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
     save_dict = {'SER': SER.numpy(), 'SNR': SNR_vec, 'M': M_vec, 'lr': lr_optim_vec, 'N_train': N_train_vec, 'nu': nu_vec}
+    if info_metrics:
+        for j, name_k in enumerate(INFO_KEYS):
+            arr = torch.empty_like(SER)
+            for k, (idx, _) in enumerate(points):
+                arr[idx] = rows[k, 1 + j]
+            save_dict[name_k] = arr.numpy()
     io.savemat(name, {'dict': save_dict})
     return name, save_dict
 

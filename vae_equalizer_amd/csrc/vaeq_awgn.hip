@@ -577,6 +577,22 @@ extern "C" int vaeq_awgn_validate(int32_t R, int64_t N, int32_t sps, int32_t M, 
     return vaeq::launch_validate<false>(n_lev, R, (int)N, sps, M, n_shift, x, W, amp, amp_mean, var, d, y_ws, ser, shift, st);
 }
 
+// vaeq_awgn_validate for the rows under its 64 symbols: the same kernel, launched for 23 + n_shift / 2 <= N < 64, where every shift the search
+// can return (at most n_shift / 2) still keeps a symbol of q[:, 11+sh : -11].  The kernel bounds every access by N (staging, y stores,
+// decisions, NE = min(N, 1000) of the shift search), so nothing but the entry check of vaeq_awgn_validate stood in the way.
+extern "C" int vaeq_awgn_validate_short(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t n_shift, const float *x, const float *W,
+                                        const float *amp, const float *amp_mean, const float *var, const void *data_f16, float *y_ws, float *ser,
+                                        int32_t *shift, void *stream)
+{
+    if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
+    if (!x || !W || !amp || !amp_mean || !var || !data_f16 || !y_ws || !ser) return VAEQ_ERR_NULL;
+    if (R < 0 || !vaeq::fir_shape_ok(sps, M) || n_shift <= 0 || n_shift > vaeq::VAL_MAXSHIFT) return VAEQ_ERR_SHAPE;
+    if (N < 23 + n_shift / 2 || N >= 64) return VAEQ_ERR_SHAPE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const __half *d = reinterpret_cast<const __half *>(data_f16);
+    return vaeq::launch_validate<false>(n_lev, R, (int)N, sps, M, n_shift, x, W, amp, amp_mean, var, d, y_ws, ser, shift, st);
+}
+
 // vaeq_awgn_validate on x = clean frame + noise made while staging (include/vaeq.h)
 extern "C" int vaeq_awgn_validate_gen(int32_t R, int64_t N, int32_t sps, int32_t M, int32_t n_lev, int32_t n_shift, const float *sig, int32_t Ls,
                                       const float *power_ws, const float *snr_db, const float *sigma_fixed, uint64_t seed, uint32_t frame,

@@ -20,6 +20,7 @@
 #include "vaeq.h"
 #include "vaeq_common.h"
 #include "vaeq_epilogue_keep.h"
+#include "vaeq_info.h"
 #include "vaeq_launch.h"
 #include "vaeq_wave.h"
 
@@ -31,23 +32,6 @@ struct InfoShared {
     float f[INFO_WAVES][16];                  // [wave][2 h + (0: AIR terms, 1: GMI terms)]
     int c[INFO_WAVES][17];                    // [wave][h: symbol errors | 8 + h: bit errors | 16: kept]
 };
-
-__device__ __forceinline__ int info_gray(int i) { return i ^ (i >> 1); }
-__device__ __forceinline__ float info_log2(float x) { return __log2f(fmaxf(x, FLT_MIN)); }       // l(x) of q-mode: an exact 0 costs 126 bit, not infinity
-__device__ __forceinline__ int info_wave_sum(int v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-template <int NL>
-__device__ __forceinline__ float info_pick(const float (&v)[NL], int l)     // v[l] without a register array indexed at run time
-{
-    float r = v[0];
-#pragma unroll
-    for (int i = 1; i < NL; i++) r = l == i ? v[i] : r;
-    return r;
-}
 
 template <int NL, bool YMODE>
 __global__ __launch_bounds__(EPI_NT) void dp_epilogue_info_kernel(int N, int batch_len, const float *__restrict__ q, const float *__restrict__ y,

@@ -252,7 +252,8 @@ class AWGNEngine:
 
     def validate(self, x, data, n_shift=21):
         """Fused validation pass (:308-318) -> (SER[R] f32, shift[R] i32, y[R,2,N]): forward, find_shift and SER_q in one
-        kernel (vaeq_awgn_validate); x[R,2,N*sps] f32, data[R,2,N] f16."""
+        kernel (vaeq_awgn_validate; rows of 23 + n_shift // 2 <= N < 64 symbols: vaeq_awgn_validate_short, the same kernel);
+        x[R,2,N*sps] f32, data[R,2,N] f16."""
         R, N = x.shape[0], x.shape[-1] // self.sps
         if tuple(data.shape) != (R, 2, N):
             raise ValueError(f"data must be [R={R}, 2, N={N}], got {tuple(data.shape)}")
@@ -260,11 +261,12 @@ class AWGNEngine:
         ser = torch.empty(R, dtype=torch.float32, device=self.device)
         shift = torch.empty(R, dtype=torch.int32, device=self.device)
         y = torch.empty(R, 2, N, dtype=torch.float32, device=self.device)
+        short = 23 + int(n_shift) // 2 <= N < 64
+        fn, what = (nat.lib().vaeq_awgn_validate_short, "vaeq_awgn_validate_short") if short else (nat.lib().vaeq_awgn_validate, "vaeq_awgn_validate")
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().vaeq_awgn_validate(R, N, self.sps, self.M, self.n_lev, int(n_shift), nat.ptr(x), nat.ptr(self.W),
-                                                   nat.ptr(self.amp), nat.ptr(self.amp_mean), nat.ptr(self.var),
-                                                   nat.ptr(data, torch.float16), nat.ptr(y), nat.ptr(ser), nat.ptr(shift, torch.int32),
-                                                   nat.current_stream(self.device)), "vaeq_awgn_validate")
+            nat.check(fn(R, N, self.sps, self.M, self.n_lev, int(n_shift), nat.ptr(x), nat.ptr(self.W), nat.ptr(self.amp), nat.ptr(self.amp_mean),
+                         nat.ptr(self.var), nat.ptr(data, torch.float16), nat.ptr(y), nat.ptr(ser), nat.ptr(shift, torch.int32),
+                         nat.current_stream(self.device)), what)
         return ser, shift, y
 
     def validate_clean(self, frame, n_shift=21, return_sigma=False):
@@ -287,6 +289,11 @@ class AWGNEngine:
                                                        nat.ptr(ser), nat.ptr(shift, torch.int32), None if sigma is None else nat.ptr(sigma),
                                                        nat.current_stream(self.device)), "vaeq_awgn_validate_gen")
         return (ser, shift, y, sigma) if return_sigma else (ser, shift, y)
+
+    def info(self, y, data, shift):
+        """GMI, NGMI, achievable rate and pre-FEC BER of a validation frame (awgn_info, y-mode) from what validate / validate_clean return:
+        y[R,2,N], data[R,2,N] f16 and shift[R], demapped with the engine's P, amp_mean and var."""
+        return awgn_info(y=y, data=data, amp_levels=self.amp, P=self.P, amp_mean=self.amp_mean, var=self.var, shift=shift)
 
 
 class NNEngine:
@@ -387,6 +394,29 @@ class NNEngine:
                                                  nat.ptr(shift, torch.int32), nat.current_stream(self.device)), "vaeq_nn_validate")
         return ser, shift
 
+    def info(self, x, data, shift, P=None):
+        """GMI, NGMI, achievable rate and pre-FEC BER of a validation frame (awgn_info, q-mode on the eval forward's posteriors): x[R,2,N*sps],
+        data[R,2,N] f16, shift[R] = validate's; P[R,n] / [n] the per-axis pmf (default uniform: the VAE-NN script's model).  The posteriors are
+        formed and consumed in chunks of runs of at most 1 GiB each."""
+        R, N = x.shape[0], x.shape[-1] // self.sps
+        if R != self.R or tuple(data.shape) != (R, 2, N):
+            raise ValueError(f"x must be [R={self.R}, 2, N*sps] and data [R, 2, N={N}], got {tuple(x.shape)}, {tuple(data.shape)}")
+        n = self.n_lev
+        P = _f32([1.0 / n] * n if P is None else P, self.device).reshape(-1, n).expand(R, n).contiguous()
+        x, data = x.contiguous(), data.to(torch.float16).contiguous()
+        shift = torch.as_tensor(shift, device=self.device).to(torch.int32).reshape(R).contiguous()
+        chunk = max(1, (1 << 30) // (2 * n * N * 4))
+        parts = []
+        for s in range(0, R, chunk):
+            e = min(R, s + chunk)
+            q = torch.empty(e - s, 2 * n, N, dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                nat.check(nat.lib().vaeq_nn_forward(e - s, N, self.sps, self.M, n, self.k1, self.k2, nat.ptr(x[s:e]), nat.ptr(self.theta[s:e]),
+                                                    None if self.bn is None else nat.ptr(self.bn[s:e]), nat.ptr(q),
+                                                    nat.current_stream(self.device)), "vaeq_nn_forward")
+            parts.append(awgn_info(q=q, data=data[s:e], amp_levels=self.amp, P=P[s:e], shift=shift[s:e]))
+        return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
 
 def dp_epilogue(q, y, data, amp_levels, nu_sc, var, batch_len=None):
     """Per-frame epilogue on the device (vaeq_dp_epilogue): q[R,2,2n,N], y[R,2,2,N], data[R,2,2,N] fp16 ->
@@ -462,6 +492,42 @@ def dp_epilogue_info(q=None, y=None, data=None, amp_levels=None, P=None, nu_sc=N
     gmi = info[:, :, 1]
     return dict(AIR=info[:, :, 0], GMI=gmi, NGMI=1.0 - (2.0 * H - gmi) / (2.0 * math.log2(n)), BER=info[:, :, 2],
                 kept=counts[:, :, 0].long(), sym_err=counts[:, :, 1].long(), bit_err=counts[:, :, 2].long(), hyp=counts[:, :, 3].long())
+
+
+def awgn_info(q=None, y=None, data=None, amp_levels=None, P=None, amp_mean=None, var=None, shift=None):
+    """Information-rate figures of an AWGN validation frame on the device (vaeq_awgn_info), over exactly the symbols the validation's SER_q keeps
+    (q[:, 11+sh : -11] against data[:, 11 : -11-sh], sh = shift[r]): exactly one of q[R,2n,N] (stored posteriors) and y[R,2,N] (the validation's
+    un-normalised output; the VAE-LE demapper's posteriors are recomputed from amp_mean[R] / var[R] in the log domain), data[R,2,N] fp16,
+    P[R,n] (or [n]) the per-axis pmf, shift[R] ->
+    dict(AIR[R], GMI[R], NGMI[R], BER[R] f32 (NaN where nothing is kept); kept, sym_err, bit_err, hyp [R] int64).
+    AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
+    if (q is None) == (y is None):
+        raise ValueError("awgn_info takes exactly one of q and y")
+    src = q if y is None else y
+    dev, R, N = src.device, src.shape[0], src.shape[-1]
+    amp = _f32(amp_levels, dev).reshape(-1)
+    n = amp.numel()
+    if tuple(src.shape) != (R, 2 * n if y is None else 2, N) or tuple(data.shape) != (R, 2, N):
+        raise ValueError(f"expected q[R,{2 * n},N] or y[R,2,N] and data[R,2,N], got {tuple(src.shape)}, {tuple(data.shape)}")
+    P = _f32(P, dev).reshape(-1, n).expand(R, n).contiguous()
+    am_t = var_t = None
+    if y is not None:
+        am_t = _f32(amp_mean, dev).expand(R).contiguous()
+        var_t = _f32(var, dev).expand(R).contiguous()
+    src = src.contiguous()
+    data = data.to(torch.float16).contiguous()
+    shift = torch.as_tensor(shift, device=dev).to(torch.int32).reshape(R).contiguous()
+    info = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(R, 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_awgn_info(R, N, n, nat.ptr(src if y is None else None), nat.ptr(src if y is not None else None),
+                                           nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(P), nat.ptr(am_t), nat.ptr(var_t),
+                                           nat.ptr(shift, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32), nat.current_stream(dev)),
+                  "vaeq_awgn_info")
+    H = -(P * torch.where(P > 0, torch.log2(P.clamp_min(torch.finfo(torch.float32).tiny)), torch.zeros_like(P))).sum(1)
+    gmi = info[:, 1]
+    return dict(AIR=info[:, 0], GMI=gmi, NGMI=1.0 - (2.0 * H - gmi) / (2.0 * math.log2(n)), BER=info[:, 2],
+                kept=counts[:, 0].long(), sym_err=counts[:, 1].long(), bit_err=counts[:, 2].long(), hyp=counts[:, 3].long())
 
 
 def cma_epilogue(y, data, amp_levels, nu_sc, var):

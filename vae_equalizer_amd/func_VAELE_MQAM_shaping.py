@@ -25,6 +25,8 @@ def awgn_tables(mod, nu, SNR, channel, sps):
     return dict(amps=t["amps"], P=t["P"], amp_mean=amp_mean, var=10 ** (-SNR / 10), h_channel=h_channel, M_channel=len(ir), n=n)
 
 
+INFO_FIGURES, INFO_COUNTS = ("AIR", "GMI", "NGMI", "BER"), ("kept", "sym_err", "bit_err", "hyp")   # the keys of engine.awgn_info
+
 generate_data = ch.generate_data                       # (:39-61) host restatement, reference signature + optional rng / noise streams
 
 
@@ -104,14 +106,15 @@ def SER_symb(rx, tx, sps, amp_levels, num_lev, device=None):
 
 
 def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epochs, epe, channel, device=None, verbose=False,
-                   generator=None, seed=None):
+                   generator=None, seed=None, want_info=False):
     """R AWGN VAE-LE runs at once: ``runs`` = list of dict(SNR, nu, lr_optim, seed).  Per epoch ONE training launch and, on evaluated
     epochs, ONE fused validation launch (forward + find_shift + SER_q, vaeq_awgn_validate) for all runs (:291-322).
 
     generator: None    = "hip" when no run carries a seed (the reference seeds nothing), else "numpy" (dp_runs.resolve_generator);
                "numpy" = the bit-faithful host channel model per run (seeded like tools/capture_golden.py when the run has a seed);
                "hip"   = the on-device generator (vaeq_gen_awgn), Philox streams keyed by ``seed``, the draw counter and the run index.
-    Returns SER_valid[R, num_epochs // epe] (CPU float32)."""
+    Returns SER_valid[R, num_epochs // epe] (CPU float32); with want_info (SER_valid, info), info = dict(AIR, GMI, NGMI, BER f32; kept, sym_err,
+    bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: engine.awgn_info in y-mode on the y and the shift of every validation launch."""
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
     generator = resolve_generator(generator, any(r.get("seed") is not None for r in runs))
@@ -129,6 +132,8 @@ def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epoch
     steps = N_train // batch_len                                                 # :297 (the remainder is dropped)
     n_eval = num_epochs // epe
     SER_dev = torch.empty(R, max(n_eval, 1), dtype=torch.float32, device=device)
+    info_dev = {k: torch.empty(R, max(n_eval, 1), dtype=torch.float32 if k in INFO_FIGURES else torch.int64, device=device)
+                for k in INFO_FIGURES + INFO_COUNTS} if want_info else None
     P_all = np.stack([t["P"] for t in tabs])
     snr_all = np.array([r["SNR"] for r in runs], dtype=np.float32)
     draws = [0]
@@ -153,28 +158,35 @@ def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epoch
         if epoch % epe == 0 and epoch // epe < n_eval:                           # :308-318
             if generator == "hip" and ch.awgn_clean_supported(sps, M_est):       # the validation frame is read once: its noise goes on while it is read
                 draws[0] += 1
-                ser, sh, _ = eng.validate_clean(ch.generate_awgn_clean_batch_hip(R, N_valid, t0["amps"], P_all, snr_all, t0["h_channel"], sps,
-                                                                                 device, seed, draws[0] - 1), 21)
+                frame = ch.generate_awgn_clean_batch_hip(R, N_valid, t0["amps"], P_all, snr_all, t0["h_channel"], sps, device, seed, draws[0] - 1)
+                ser, sh, yv = eng.validate_clean(frame, 21)
+                datav = frame.data
             else:
                 rxv, datav = draw(N_valid)
-                ser, sh, _ = eng.validate(rxv, datav, 21)
+                ser, sh, yv = eng.validate(rxv, datav, 21)
             SER_dev[:, epoch // epe] = ser
+            if want_info:
+                for k, v in eng.info(yv, datav, sh).items():
+                    info_dev[k][:, epoch // epe] = v
             if verbose:
                 loss, ser_h, sh_h = out["loss"][:, -1].cpu(), ser.cpu(), sh.cpu()
                 for i in range(R):
                     tag = f"[run {i}] " if R > 1 else ""
                     print(f"{tag}{epoch}", loss[i].item(), int(sh_h[i]), '\t\t\t\t\t\tSER = ', ser_h[i].item())
+    if want_info:
+        return SER_dev[:, :n_eval].cpu(), {k: v[:, :n_eval].cpu() for k, v in info_dev.items()}
     return SER_dev[:, :n_eval].cpu()
 
 
 def processing(mod, sps, SNR, nu, M_est, lr_optim, batch_len, N_valid, N_train, num_epochs, epe, channel, *, seed=None,
-               device=None, verbose=True, generator=None):
-    """One AWGN VAE-LE run -> SER_valid[num_epochs//epe] (CPU float32).
+               device=None, verbose=True, generator=None, want_info=False):
+    """One AWGN VAE-LE run -> SER_valid[num_epochs//epe] (CPU float32); with want_info (SER_valid, info), info as run_awgn_batch's per run.
 
     NB the sweep script passes its ``N_train`` (350) as ``batch_len`` and ``train_len`` (1200) as ``N_train``
     (Eval_run_shaping_vaele.py:53)."""
     device = default_device() if device is None else torch.device(device)
     if verbose:
         print("We are using the following device for learning:", device)
-    return run_awgn_batch([dict(SNR=SNR, nu=nu, lr_optim=lr_optim, seed=seed)], mod, sps, M_est, batch_len, N_valid, N_train,
-                          num_epochs, epe, channel, device=device, verbose=verbose, generator=generator)[0]
+    out = run_awgn_batch([dict(SNR=SNR, nu=nu, lr_optim=lr_optim, seed=seed)], mod, sps, M_est, batch_len, N_valid, N_train,
+                         num_epochs, epe, channel, device=device, verbose=verbose, generator=generator, want_info=want_info)
+    return (out[0][0], {k: v[0] for k, v in out[1].items()}) if want_info else out[0]

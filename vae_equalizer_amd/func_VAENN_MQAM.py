@@ -138,14 +138,16 @@ def theta_to_net(theta, net, bn=None):
 
 
 def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_valid, N_train, num_epochs, epe, channel, device=None,
-                    verbose=False, generator="hip", seed=0, theta0=None, net_type="Net"):
+                    verbose=False, generator="hip", seed=0, theta0=None, net_type="Net", want_info=False):
     """R VAE-NN runs at once: ``runs`` = list of dict(SNR, lr_optim, seed).  Per epoch one generator call, ONE training launch
     (N_train // batch_len minibatches) and, on evaluated epochs, one fused validation launch for all runs (:266-301).
 
     generator: "hip" = on-device channel model (vaeq_gen_awgn with the script's fixed noise level), Philox streams keyed by ``seed``;
                "numpy" = the host restatement per run, seeded per run when the run has a seed.
     theta0: optional [R, NP] initial parameters (default: Xavier / PyTorch-default initialisation drawn on the device).
-    Returns SER_valid[R, num_epochs // epe] (CPU float32)."""
+    Returns SER_valid[R, num_epochs // epe] (CPU float32); with want_info (SER_valid, info), info = dict(AIR, GMI, NGMI, BER f32; kept, sym_err,
+    bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: NNEngine.info (eval forward, then engine.awgn_info in q-mode, uniform pmf) on the
+    frame and the shift of every validation launch."""
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
     t = vaenn_tables(mod, channel, sps)
@@ -167,6 +169,8 @@ def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_vali
     steps = N_train // batch_len
     n_eval = num_epochs // epe
     SER_dev = torch.empty(R, max(n_eval, 1), dtype=torch.float32, device=device)
+    info_dev = {k: torch.empty(R, max(n_eval, 1), dtype=torch.float32 if k in ("AIR", "GMI", "NGMI", "BER") else torch.int64, device=device)
+                for k in ("AIR", "GMI", "NGMI", "BER", "kept", "sym_err", "bit_err", "hyp")} if want_info else None
     draws = [0]
 
     def draw(N):
@@ -187,20 +191,27 @@ def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_vali
             rxv, datav = draw(N_valid)
             ser, sh = eng.validate(rxv, datav, 21)
             SER_dev[:, epoch // epe] = ser
+            if want_info:
+                for k, v in eng.info(rxv, datav, sh).items():
+                    info_dev[k][:, epoch // epe] = v
             if verbose:
                 loss, ser_h, sh_h = out["loss"][:, -1].cpu(), ser.cpu(), sh.cpu()
                 for i in range(R):
                     tag = f"[run {i}] " if R > 1 else ""
                     print(f"{tag}{epoch}", loss[i].item(), int(sh_h[i]), '\t\t\t\t\t\tSER = ', ser_h[i].item())
+    if want_info:
+        return SER_dev[:, :n_eval].cpu(), {k: v[:, :n_eval].cpu() for k, v in info_dev.items()}
     return SER_dev[:, :n_eval].cpu()
 
 
 def processing(mod, sps, SNR, M_est, kernel_1, kernel_2, lr_optim, batch_len, N_valid, N_train, num_epochs, epe, channel, net_type, *,
-               seed=None, device=None, verbose=True, generator="numpy", theta0=None):
-    """One VAE-NN run -> SER_valid[num_epochs//epe] (CPU float32), the reference's positional signature (:215)."""
+               seed=None, device=None, verbose=True, generator="numpy", theta0=None, want_info=False):
+    """One VAE-NN run -> SER_valid[num_epochs//epe] (CPU float32), the reference's positional signature (:215); with want_info
+    (SER_valid, info), info as run_vaenn_batch's per run."""
     device = default_device() if device is None else torch.device(device)
     if verbose:
         print("We are using the following device for learning:", device)
-    return run_vaenn_batch([dict(SNR=SNR, lr_optim=lr_optim, seed=seed)], mod, sps, M_est, kernel_1, kernel_2, batch_len, N_valid, N_train,
-                           num_epochs, epe, channel, device=device, verbose=verbose, generator=generator, seed=seed or 0, theta0=theta0,
-                           net_type=net_type)[0]
+    out = run_vaenn_batch([dict(SNR=SNR, lr_optim=lr_optim, seed=seed)], mod, sps, M_est, kernel_1, kernel_2, batch_len, N_valid, N_train,
+                          num_epochs, epe, channel, device=device, verbose=verbose, generator=generator, seed=seed or 0, theta0=theta0,
+                          net_type=net_type, want_info=want_info)
+    return (out[0][0], {k: v[0] for k, v in out[1].items()}) if want_info else out[0]
