@@ -316,6 +316,27 @@ int vaeq_awgn_info(int32_t R, int64_t N, int32_t n_lev, const float *q, const fl
 int vaeq_cma_epilogue(int32_t R, int64_t N, int32_t n_lev, const float *y, const void *tx_f16, const float *amp, const float *var,
                       const float *nu_sc, float *ser, int32_t *shift, int32_t *rflag, void *workspace, void *stream);
 
+/* Information-rate figures of one frame of the constant-modulus baselines, per run and polarisation, over exactly the symbols the soft-demapper SER
+ * of vaeq_cma_epilogue keeps; the figures, hypotheses, tie-break, Gray labels and output layout are vaeq_dp_epilogue_info's y-mode (info[R][2][3] =
+ * AIR, GMI, BER; counts[R][2][4] = kept, sym_err, bit_err, hyp; NGMI is the host's).  y[R][2][2][N], tx_f16[R][2][2][N], var[R][2], nu_sc[R]: what
+ * vaeq_cma_epilogue got; amp[n_lev], P[R][n_lev] the runs' per-axis pmf; shift_c[R][2], r_c[R], shift_q[R][2], r_q[R]: that call's constellation-stage
+ * and soft-demapper-stage alignment (shift[:, 1], rflag[:, 1], shift[:, 0], rflag[:, 0]); shifts are clamped to +-10.  The epilogue leaves neither
+ * the sequence it demapped nor q in memory, so the kernel redoes both stages' addressing from y:
+ *   ya[p'][c][m] = y[(p' - r_c) & 1][c][(m + shift_c[p']) mod N]                      (the roll wraps around the frame)
+ *   W_c = [11, N - 11 - max|shift_c|),  fac = sum_{p', m in W_c} |tx[p'][:, m]| / sum_{p', m in W_c} |ya[p'][:, m]|   (one factor per run)
+ *   yn = ya fac inside W_c, ya outside it          (the reference normalises a slice view in place, shared_funcs.py:242)
+ *   posteriors per axis = softmax_i(-(yn - a_i)^2 / (2 var[p']) - nu_sc a_i^2), in the log domain, every bit-wise sum a log-sum-exp around its own maximum
+ *   kept symbol n in [11, N - 11 - max|shift_q|) of output polarisation p reads yn[(p - r_q) & 1][:, n + shift_q[p]]
+ * fac is this kernel's own sum, not the epilogue's bit for bit, so sym_err / kept is the epilogue's soft-demapper SER except where a sample lies
+ * within float32 rounding of a decision threshold.  A run whose sum of |ya| over W_c is zero has no normalisation: NaN figures, zero counts.
+ * One launch, one workgroup per run, y and tx read twice, no workspace; sums run in a fixed order without atomics: two calls give identical bits, R runs in one call
+ * the bits of R single calls.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); any NULL pointer is VAEQ_ERR_NULL, before any shape rule; R < 0, N < 43, N > 0x3fffffff or n_lev
+ * not in {2, 4, 8} is VAEQ_ERR_SHAPE. */
+int vaeq_cma_epilogue_info(int32_t R, int64_t N, int32_t n_lev, const float *y, const void *tx_f16, const float *amp, const float *P,
+                           const float *var, const float *nu_sc, const int32_t *shift_c, const int32_t *r_c, const int32_t *shift_q,
+                           const int32_t *r_q, float *info, int32_t *counts, void *stream);
+
 /* ------------------------------------------------------------------------
  * Seeded on-device DP channel simulator (input producer): optical_DP_channel/shared_funcs.py:65-90 in three stages with
  * the FFT / inverse FFT over Ls done by the caller (hipFFT through torch.fft) between them.  Counter-based RNG (Philox4x32-10):

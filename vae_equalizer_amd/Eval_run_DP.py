@@ -40,7 +40,7 @@ N_frame_max = 10000
 
 savePATH = ""
 base_seed = None    # int -> reproducible runs (run i of the flattened sweep uses base_seed + 1000*i); None = like the reference
-info_metrics = False  # True (VAE / VAEflex): the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), shaped like SER with a leading axis of 2
+info_metrics = False  # True (every loss_type): the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), shaped like SER with a leading axis of 2
 generator = None    # None: "hip" (on-device channel simulator) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set; or force "numpy" / "hip" / "torch"
 
 
@@ -86,7 +86,8 @@ def main():
         if loss_type in ('CMA', 'CMAbatch', 'CMAflex'):         # the constant-modulus baselines (:58-65)
             from .cma_runs import run_cma_batch
             r = run_cma_batch(runs, loss_type, mod, sps, M, batch_len, N_frame_max, num_frames, fs, channel, tau_cd, tau_pmd, phiIQ, N_lrhalf,
-                              device=device, generator=generator if generator in (None, "numpy", "hip") else "hip", verbose=False)
+                              device=device, generator=generator if generator in (None, "numpy", "hip") else "hip", verbose=False,
+                              want_info=info_metrics)
         elif loss_type in ('VAE', 'VAEflex'):
             r = run_dp_batch(runs, mod, sps, M, batch_len, N_frame_max, num_frames, fs, channel, tau_cd, tau_pmd, phiIQ, N_lrhalf,
                              flex=(loss_type == 'VAEflex'), device=device, generator=generator, verbose=False,
@@ -98,7 +99,7 @@ def main():
         local[sel, 6:8] = r["var"].unsqueeze(-1).expand(-1, -1, num_frames)
         if info_metrics:
             if "info" not in r:
-                raise ValueError(f"info_metrics is defined for loss_type 'VAE' and 'VAEflex', not {loss_type!r}")
+                raise ValueError(f"the result of loss_type {loss_type!r} carries no 'info'")
             for j, k in enumerate(INFO_KEYS):
                 local[sel, 8 + 2 * j:10 + 2 * j] = r["info"][k]
     rows = sweep.gather_rows(local, len(points), rank, world)

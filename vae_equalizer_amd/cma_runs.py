@@ -14,18 +14,23 @@ import torch
 from . import channel as ch
 from . import epilogue as epi
 from . import shared_funcs as sfun
-from .dp_runs import DPRun, _host_pool, check_one_symb_rate, default_device, fresh_seed, resolve_generator  # noqa: F401
+from .dp_runs import INFO_FLOAT, INFO_INT, DPRun, _host_pool, check_one_symb_rate, default_device, fresh_seed, resolve_generator  # noqa: F401
 from .engine import cma, cpe, soft_demap
 
 N_CUT = 10   # symbols cut at both frame ends before the phase estimation (func_CMA_DP_MQAM_shaping.py:26,39)
 
 
-def cma_frame_epilogue(out_const, data, amp, nu_sc, var):
+def cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=None):
     """out_const[R,2,2,K] (CMA output of one frame), data[R,2,2,K] fp16 -> dict(SER[R,4], shift_c, r_c, shift_q, r_q): phase estimation
-    (vaeq_cpe) + the two-stage epilogue in one HIP launch (vaeq_cma_epilogue; q is never materialised)."""
-    from .engine import cma_epilogue
+    (vaeq_cpe) + the two-stage epilogue in one HIP launch (vaeq_cma_epilogue; q is never materialised).  P[R,n] (the runs' per-axis pmf): also
+    "info" = engine.cma_epilogue_info on the same y and the alignment just found (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp, each [R,2])."""
+    from .engine import cma_epilogue, cma_epilogue_info
     y = cpe(out_const[..., N_CUT:-N_CUT].contiguous())                          # :39
-    return cma_epilogue(y, data[..., N_CUT:-N_CUT], amp, nu_sc, var)            # :40-52
+    d = data[..., N_CUT:-N_CUT]
+    res = cma_epilogue(y, d, amp, nu_sc, var)                                   # :40-52
+    if P is not None:
+        res["info"] = cma_epilogue_info(y, d, amp, P, nu_sc, var, res["shift_c"], res["r_c"], res["shift_q"], res["r_q"])
+    return res
 
 
 def cma_frame_epilogue_torch(out_const, data, amp, nu_sc, var):
@@ -52,9 +57,11 @@ def cma_frame_epilogue_torch(out_const, data, amp, nu_sc, var):
 
 
 def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frames, flex_step, channel, tau_cd, tau_pmd, phiIQ, N_lrhalf,
-                  device=None, generator=None, verbose=False):
+                  device=None, generator=None, verbose=False, want_info=False):
     """R baseline runs (list of dp_runs.DPRun; lr_optim = the CMA step size) -> dict(SER[R,4,num_frames], Var_est[R,2,num_frames] (zeros,
-    like the reference), var[R,2], h).  mode: "CMA" | "CMAbatch" | "CMAflex"."""
+    like the reference), var[R,2], h).  mode: "CMA" | "CMAbatch" | "CMAflex".
+    want_info: also dict(AIR, GMI, NGMI, BER [R,2,num_frames] f32; kept, sym_err, bit_err, hyp [R,2,num_frames] int64) under "info", on the CPU
+               like run_dp_batch's: engine.cma_epilogue_info after every frame's epilogue, on the runs' PCS pmf rows."""
     if mode not in ("CMA", "CMAbatch", "CMAflex"):
         raise ValueError(f"unknown CMA variant {mode!r}")
     device = default_device() if device is None else torch.device(device)
@@ -76,6 +83,11 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
     streams = [ch.SeededStreams(r.seed) if r.seed is not None else None for r in runs]
     SER = torch.empty(R, 4, num_frames, dtype=torch.float32, device=device)
     P = np.stack([t["P"] for t in tabs])
+    P_t = INFO = None
+    if want_info:
+        P_t = torch.tensor(P, dtype=torch.float32, device=device)
+        INFO = {k: torch.empty(R, 2, num_frames, dtype=torch.float32 if k in INFO_FLOAT else torch.int64, device=device)
+                for k in INFO_FLOAT + INFO_INT}
     check_one_symb_rate(runs, generator)
     hip_seed = int(runs[0].seed) if R and runs[0].seed is not None else fresh_seed()   # unseeded: fresh entropy per call and rank
     for frame in range(num_frames):
@@ -97,8 +109,11 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
             raise ValueError(f"unknown generator {generator!r}")
         theta = theta + theta_diff
         out_const, e = cma(rx, h, lr.astype(np.float32), sps, mode, batch_len, flex_step, 1.0, want_e=verbose)
-        res = cma_frame_epilogue(out_const, data, amp, nu_sc, var)
+        res = cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=P_t)
         SER[:, :, frame] = res["SER"]
+        if want_info:
+            for k in INFO:
+                INFO[k][:, :, frame] = res["info"][k]
         if verbose:
             es, ser_h = e.sum(dim=(1, 2)).cpu(), res["SER"].cpu()
             for i in range(R):
@@ -107,7 +122,10 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
                       res["shift_c"][i, 1].item(), "\tr = ", int(res["r_c"][i]))
                 print("\t\t\t\t\t\t\tSER_x = ", ser_h[i, 0].item(), "\tSER_y = ", ser_h[i, 1].item(), "\t(constell. with shaping)")
                 print("\t\t\t\t\t\t\tSER_x = ", ser_h[i, 2].item(), "\tSER_y = ", ser_h[i, 3].item(), "\t(soft demapper)")
-    return dict(SER=SER.cpu(), Var_est=torch.zeros(R, 2, num_frames), var=torch.tensor(var_np), h=h)
+    ret = dict(SER=SER.cpu(), Var_est=torch.zeros(R, 2, num_frames), var=torch.tensor(var_np), h=h)
+    if INFO is not None:
+        ret["info"] = {k: v.cpu() for k, v in INFO.items()}
+    return ret
 
 
 def _processing(mode, mod, sps, SNR, nu, M_est, theta_diff, theta, lr_optim, batch_len, N_train_max, num_frames, flex_step, channel, symb_rate,

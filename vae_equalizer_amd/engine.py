@@ -551,6 +551,38 @@ def cma_epilogue(y, data, amp_levels, nu_sc, var):
     return dict(SER=ser, shift_q=shift[:, 0].long(), r_q=rflag[:, 0].long(), shift_c=shift[:, 1].long(), r_c=rflag[:, 1].long())
 
 
+def cma_epilogue_info(y, data, amp_levels, P, nu_sc, var, shift_c, r_c, shift_q, r_q):
+    """Information-rate figures of one frame of the constant-modulus baselines on the device (vaeq_cma_epilogue_info), over exactly the symbols
+    cma_epilogue's soft-demapper SER keeps: y[R,2,2,N], data[R,2,2,N] fp16, nu_sc, var as cma_epilogue got them, P[R,n] (or [n]) the per-axis pmf,
+    shift_c[R,2] / r_c[R] / shift_q[R,2] / r_q[R] = that call's alignment.  The posteriors are the soft demapper's on the stage-c aligned output
+    whose kept window carries the mean-radius normalisation, recomputed in the log domain (neither that sequence nor q exists in memory) ->
+    dict(AIR[R,2], GMI[R,2], NGMI[R,2], BER[R,2] f32 (NaN for a run without a normalisation); kept, sym_err, bit_err, hyp [R,2] int64).
+    AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
+    dev, R, N = y.device, y.shape[0], y.shape[-1]
+    amp = _f32(amp_levels, dev).reshape(-1)
+    n = amp.numel()
+    if tuple(y.shape) != (R, 2, 2, N) or tuple(data.shape) != (R, 2, 2, N):
+        raise ValueError(f"expected y[R,2,2,N] and data[R,2,2,N], got {tuple(y.shape)}, {tuple(data.shape)}")
+    P = _f32(P, dev).reshape(-1, n).expand(R, n).contiguous()
+    var_t = _f32(var, dev).expand(R, 2).contiguous()
+    nu_t = _f32(nu_sc, dev).expand(R).contiguous()
+    y = y.contiguous()
+    data = data.to(torch.float16).contiguous()
+    i32 = lambda t, shape: torch.as_tensor(t, device=dev).to(torch.int32).reshape(shape).contiguous()
+    sc, rc, sq, rq = i32(shift_c, (R, 2)), i32(r_c, (R,)), i32(shift_q, (R, 2)), i32(r_q, (R,))
+    info = torch.empty(R, 2, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(R, 2, 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_cma_epilogue_info(R, N, n, nat.ptr(y), nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(P), nat.ptr(var_t),
+                                                   nat.ptr(nu_t), nat.ptr(sc, torch.int32), nat.ptr(rc, torch.int32), nat.ptr(sq, torch.int32),
+                                                   nat.ptr(rq, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32), nat.current_stream(dev)),
+                  "vaeq_cma_epilogue_info")
+    H = -(P * torch.where(P > 0, torch.log2(P.clamp_min(torch.finfo(torch.float32).tiny)), torch.zeros_like(P))).sum(1, keepdim=True)
+    gmi = info[:, :, 1]
+    return dict(AIR=info[:, :, 0], GMI=gmi, NGMI=1.0 - (2.0 * H - gmi) / (2.0 * math.log2(n)), BER=info[:, :, 2],
+                kept=counts[:, :, 0].long(), sym_err=counts[:, :, 1].long(), bit_err=counts[:, :, 2].long(), hyp=counts[:, :, 3].long())
+
+
 def awgn_loss(q, x, h, amp_levels, P=None):
     """ELBO of the single-polarisation variants for a given q (vaeq_awgn_loss): q[R,2n,B] (or [2n,B]), x[R,2,B*sps], h[R,2,M];
     P[R,n] / [n] -> the VAE-LE form (KL to the prior), P None -> the VAE-NN form (entropy).  Returns loss[R] (or a 0-dim tensor)."""
