@@ -191,8 +191,10 @@ __global__ __launch_bounds__(64 * NW, 2) void awgn_wave_kernel(const vaeq_awgn_a
     const float c2 = LOG2E / var, ivar2 = 2.0f / var;          // z_i = -(yhat - a_i)^2 / var: no 1/2, no PCS term (:229)
     const float lr = a.lr[run];
 
-    for (int i = gl; i < (lay.W - lay.X) / 8; i += NT) Xs[i] = make_float2(0.f, 0.f);     // X, E, U, PSv
-    for (int i = gl; i < (lay.PSh - lay.H) / 8; i += NT) Ht[i] = make_float2(0.f, 0.f);   // incl. the pad tap
+    // All of it, the padding between the arrays and XP included: the blocked tap-gradient loops below run uniform trip counts and read their U / x
+    // operands past a part's range (up to PH / PW pairs beyond U, which at B < 128 is past PSv, into the pads of W, PSh, VS and into XP); the
+    // terms are masked by a zero e / gy factor, and 0 * (NaN left in LDS by an earlier kernel) is NaN.
+    for (int i = gl; i < lay.total / 8; i += NT) Xs[i] = make_float2(0.f, 0.f);           // X, E, U, PSv, W, H (incl. the pad tap), PSh, VS, XP, RED
     __syncthreads();
     const int tk = lane & 31, half = lane >> 5;
     const bool worker = tk < M, owner = worker && wv == 0, wown = owner && half == 0, hown = owner && half == 1;
