@@ -12,6 +12,8 @@
 // once and every hypothesis is a selection among (axis, level in {t_I, n-1-t_I, t_Q, n-1-t_Q}).
 // Integer counts are exact; float sums run per thread in symbol order, then over the wave's lanes (DPP, fixed order), then over the four waves in
 // order: no atomics, two calls give identical bits.
+// This file holds the window, the pre-pass for the two means, the early-out and the VAE-LE demapper's exponent; the per-symbol body and the tail
+// are vaeq_info.h's (info_symbol<NL, YMODE, 4>: no IQ flip; info_finish with K = len given, not counted), shared with the two DP kernels.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -27,12 +29,6 @@ namespace vaeq {
 
 constexpr int AINFO_NT = 256, AINFO_WAVES = AINFO_NT / 64, AINFO_EDGE = 11;
 
-struct AwgnInfoShared {
-    float red[AINFO_WAVES];                   // eval_block_sum's scratch (y-mode: the two sums of |y_c|)
-    float f[AINFO_WAVES][8];                  // [wave][2 h + (0: AIR terms, 1: GMI terms)]
-    int c[AINFO_WAVES][8];                    // [wave][h: symbol errors | 4 + h: bit errors]
-};
-
 template <int NL, bool YMODE>
 __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float *__restrict__ q, const float *__restrict__ y,
                                                              const __half *__restrict__ txg, const float *__restrict__ amp_g,
@@ -40,9 +36,9 @@ __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float 
                                                              const float *__restrict__ var, const int32_t *__restrict__ shift,
                                                              float *__restrict__ info, int32_t *__restrict__ counts)
 {
-    constexpr int S = NL - 1, NB = NL == 2 ? 1 : (NL == 4 ? 2 : 3);
     constexpr float LOG2E = 1.4426950408889634f;
-    __shared__ AwgnInfoShared sh;
+    __shared__ float red[AINFO_WAVES];                         // eval_block_sum's scratch (y-mode: the two sums of |y_c|)
+    __shared__ InfoShared<4, AINFO_WAVES> sh;
     const int run = blockIdx.x, tid = threadIdx.x;
     float *o = info + (size_t)run * 3;
     int32_t *cn = counts + (size_t)run * 4;
@@ -62,8 +58,8 @@ __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float 
 #pragma unroll 4
             for (int n = tid; n < N; n += AINFO_NT) { sa0 += fabsf(src[n]); sa1 += fabsf(src[(size_t)N + n]); }
         }
-        sa0 = eval_block_sum<AINFO_NT>(sa0, sh.red, tid);
-        sa1 = eval_block_sum<AINFO_NT>(sa1, sh.red, tid);
+        sa0 = eval_block_sum<AINFO_NT>(sa0, red, tid);
+        sa1 = eval_block_sum<AINFO_NT>(sa1, red, tid);
         const float m0 = sa0 / (float)N, m1 = sa1 / (float)N, A = amp_mean[run];
         if (m0 == 0.f || m1 == 0.f) empty = true;              // a component that is zero throughout has no normalisation: no measurement
         sc[0] = A / m0; sc[1] = A / m1;
@@ -80,7 +76,6 @@ __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float 
     }
 
     const __half *txI = txg + (size_t)run * 2 * N, *txQ = txI + N;
-    const float scale = 0.5f * S;
     float fs[8];
     int se[4], be[4];
 #pragma unroll
@@ -90,11 +85,8 @@ __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float 
 
     for (int j = tid; j < len; j += AINFO_NT) {
         const int m = AINFO_EDGE + sft + j, n = AINFO_EDGE + j;
-        const int tI = min(max((int)rintf(scale * __half2float(txI[n]) + scale), 0), S);
-        const int tQ = min(max((int)rintf(scale * __half2float(txQ[n]) + scale), 0), S);
-        // v[c][i]: q-mode the posterior q, y-mode its unnormalised log2
+        const __half txi = txI[n], txq = txQ[n];
         float v[2][NL];
-        int d[2];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if constexpr (YMODE) {
@@ -108,101 +100,10 @@ __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float 
 #pragma unroll
                 for (int i = 0; i < NL; i++) v[c][i] = src[(size_t)(c * NL + i) * N + m];
             }
-            float best = v[c][0];
-            int bi = 0;
-#pragma unroll
-            for (int i = 1; i < NL; i++)
-                if (v[c][i] > best) { best = v[c][i]; bi = i; }                                  // first maximum, as argmax
-            d[c] = bi;
         }
-        // L[c][k][b]: log2 of the posterior mass of the levels whose label bit k is b; lse[c]: y-mode's log2 of the normaliser
-        float L[2][NB][2], lse[2] = {0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int k = 0; k < NB; k++) {
-                if constexpr (YMODE) {                         // log-sum-exp around each set's OWN maximum: no set underflows
-                    float mx[2] = {-INFINITY, -INFINITY}, sm[2] = {0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < NL; i++) { const int b = (info_gray(i) >> k) & 1; mx[b] = fmaxf(mx[b], v[c][i]); }
-#pragma unroll
-                    for (int i = 0; i < NL; i++) { const int b = (info_gray(i) >> k) & 1; sm[b] += __builtin_amdgcn_exp2f(v[c][i] - mx[b]); }
-                    L[c][k][0] = mx[0] + __log2f(sm[0]);
-                    L[c][k][1] = mx[1] + __log2f(sm[1]);
-                    if (k == 0) {
-                        const float hi = fmaxf(L[c][0][0], L[c][0][1]), lo = fminf(L[c][0][0], L[c][0][1]);
-                        lse[c] = hi + __log2f(1.0f + __builtin_amdgcn_exp2f(lo - hi));
-                    }
-                } else {
-                    float sm[2] = {0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < NL; i++) sm[(info_gray(i) >> k) & 1] += v[c][i];
-                    L[c][k][0] = info_log2(sm[0]);
-                    L[c][k][1] = info_log2(sm[1]);
-                }
-            }
-        // the two terms of every hypothesis are (axis c, level lv[j]) pairs
-        const int lv[4] = {tI, S - tI, tQ, S - tQ};
-        float A[2][4], G[2][4];
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int jj = 0; jj < 4; jj++) {
-                const float pv = info_pick<NL>(v[c], lv[jj]);
-                A[c][jj] = YMODE ? pv - lse[c] : info_log2(pv);
-                const int g = info_gray(lv[jj]);
-                float gs = 0.f;
-#pragma unroll
-                for (int k = 0; k < NB; k++) gs += ((g >> k) & 1) ? L[c][k][1] : L[c][k][0];
-                G[c][jj] = YMODE ? gs - (float)NB * lse[c] : gs;
-            }
-        // decisions under rotation by 0, pi, pi/2, 3 pi/2 (SER_q, :97-123), and where the I' and the Q' term of each come from:
-        // q'_I = q_I, rev q_I, rev q_Q, q_Q; q'_Q = q_Q, rev q_Q, q_I, rev q_I
-        const int hI[4] = {d[0], S - d[0], S - d[1], d[1]}, hQ[4] = {d[1], S - d[1], d[0], S - d[0]};
-        const int cI[4] = {0, 0, 1, 1}, jI[4] = {0, 1, 1, 0}, cQ[4] = {1, 1, 0, 0}, jQ[4] = {2, 3, 2, 3};
-#pragma unroll
-        for (int h = 0; h < 4; h++) {
-            fs[2 * h + 0] += A[cI[h]][jI[h]] + A[cQ[h]][jQ[h]];
-            fs[2 * h + 1] += G[cI[h]][jI[h]] + G[cQ[h]][jQ[h]];
-            const int xI = info_gray(hI[h]) ^ info_gray(tI), xQ = info_gray(hQ[h]) ^ info_gray(tQ);
-            se[h] += (xI | xQ) != 0;
-            be[h] += __popc(xI) + __popc(xQ);
-        }
+        info_symbol<NL, YMODE, 4>(v, txi, txq, fs, se, be);
     }
-
-    const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const float t = wave_sum_dpp(fs[i]);
-        if (lane == 0) sh.f[w][i] = t;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int a = info_wave_sum(se[i]), b = info_wave_sum(be[i]);
-        if (lane == 0) { sh.c[w][i] = a; sh.c[w][4 + i] = b; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int tot[8];
-        for (int i = 0; i < 8; i++) {
-            tot[i] = 0;
-            for (int k = 0; k < AINFO_WAVES; k++) tot[i] += sh.c[k][i];
-        }
-        int h = 0;
-        for (int k = 1; k < 4; k++)
-            if (tot[k] < tot[h]) h = k;                        // fewest symbol errors, ties to the smallest h
-        float sa = 0.f, sg = 0.f;
-        for (int k = 0; k < AINFO_WAVES; k++) { sa += sh.f[k][2 * h]; sg += sh.f[k][2 * h + 1]; }
-        float H = 0.f;                                         // per-axis entropy of the run's pmf; a zero entry contributes 0
-        for (int i = 0; i < NL; i++) {
-            const float pi = Pg[run * NL + i];
-            if (pi > 0.f) H -= pi * log2f(pi);
-        }
-        o[0] = 2.0f * H + sa / (float)len;
-        o[1] = 2.0f * H + sg / (float)len;
-        o[2] = (float)tot[4 + h] / ((float)(2 * NB) * (float)len);
-        cn[0] = len; cn[1] = tot[h]; cn[2] = tot[4 + h]; cn[3] = h;
-    }
+    info_finish<NL, 4, AINFO_WAVES, false>(sh, tid, fs, se, be, len, Pg + run * NL, o, cn);
 }
 
 }  // namespace vaeq

@@ -6,7 +6,8 @@
 //   stage c:  ya[p'][c][m] = y[(p' - r_c) & 1][c][(m + shift_c[p']) mod N],   W_c = [11, N - 11 - max|shift_c|)
 //             fac = sum_{p', m in W_c} |tx[p'][:, m]| / sum_{p', m in W_c} |ya[p'][:, m]|,   yn = ya fac inside W_c, ya outside it
 //   stage q:  kept symbol n in [11, N - 11 - max|shift_q|) of output polarisation p reads yn[p' = (p - r_q) & 1][:, m = n + shift_q[p]]
-// and demaps it with var[p'] in the log domain (info_symbol_y, vaeq_info.h).
+// and demaps it with var[p'] in the log domain.  What is this kernel's own is that addressing, the radius walk and the two calls of the tail; the
+// per-symbol body, the tail and the demapper's exponent are vaeq_info.h's (info_symbol, info_finish, info_demap_log2), shared with the siblings.
 //
 // One workgroup per run, three walks: the first forms fac, the second and third the figures of output polarisation 0 and 1.
 // y and tx are read, nothing but the 56 bytes of results per run is written.  Integer counts are exact; float sums run per thread in index order,
@@ -28,14 +29,6 @@ namespace vaeq {
 
 constexpr int CMA_INFO_WAVES = EPI_NT / 64;
 
-struct CmaInfoShared {
-    float rad[CMA_INFO_WAVES][2];             // [wave][0: sum |tx|, 1: sum |ya|] over W_c
-    float f[CMA_INFO_WAVES][16];              // [wave][2 h + (0: AIR terms, 1: GMI terms)]
-    int c[CMA_INFO_WAVES][17];                // [wave][h: symbol errors | 8 + h: bit errors | 16: kept]
-};
-
-__device__ __forceinline__ int cma_info_clamp_shift(int s) { return min(max(s, -HALF_SHIFT), HALF_SHIFT); }
-
 template <int NL>
 __global__ __launch_bounds__(EPI_NT) void cma_epilogue_info_kernel(int N, const float *__restrict__ y, const __half *__restrict__ txg,
                                                                    const float *__restrict__ amp_g, const float *__restrict__ Pg,
@@ -44,13 +37,13 @@ __global__ __launch_bounds__(EPI_NT) void cma_epilogue_info_kernel(int N, const 
                                                                    const int32_t *__restrict__ shift_q, const int32_t *__restrict__ r_q,
                                                                    float *__restrict__ info, int32_t *__restrict__ counts)
 {
-    constexpr int S = NL - 1, NB = NL == 2 ? 1 : (NL == 4 ? 2 : 3);
-    __shared__ CmaInfoShared sh;
+    __shared__ float rad[CMA_INFO_WAVES][2];                   // [wave][0: sum |tx|, 1: sum |ya|] over W_c
+    __shared__ InfoShared<8, CMA_INFO_WAVES> sh;
     const int run = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     // both alignments clamped to what the epilogue can find: with 11 <= n and a window that ends 11 + max|shift| before the row does, n + shift
     // stays inside [1, N - 1) in either stage; only the stage-c roll of a sample outside W_c can wrap around the frame
-    const int c0 = cma_info_clamp_shift(shift_c[run * 2 + 0]), c1 = cma_info_clamp_shift(shift_c[run * 2 + 1]);
-    const int q0 = cma_info_clamp_shift(shift_q[run * 2 + 0]), q1 = cma_info_clamp_shift(shift_q[run * 2 + 1]);
+    const int c0 = info_clamp_shift(shift_c[run * 2 + 0]), c1 = info_clamp_shift(shift_c[run * 2 + 1]);
+    const int q0 = info_clamp_shift(shift_q[run * 2 + 0]), q1 = info_clamp_shift(shift_q[run * 2 + 1]);
     const int rc = r_c[run] & 1, rq = r_q[run] & 1;
     const int endc = N - EDGE - max(abs(c0), abs(c1)), endq = N - EDGE - max(abs(q0), abs(q1));   // W_c = [EDGE, endc), kept = [EDGE, endq)
     const float *yr = y + (size_t)run * 4 * N;
@@ -71,10 +64,10 @@ __global__ __launch_bounds__(EPI_NT) void cma_epilogue_info_kernel(int N, const 
     }
     st = wave_sum_dpp(st);
     sy = wave_sum_dpp(sy);
-    if (lane == 0) { sh.rad[w][0] = st; sh.rad[w][1] = sy; }
+    if (lane == 0) { rad[w][0] = st; rad[w][1] = sy; }
     __syncthreads();
     st = sy = 0.f;
-    for (int k = 0; k < CMA_INFO_WAVES; k++) { st += sh.rad[k][0]; sy += sh.rad[k][1]; }
+    for (int k = 0; k < CMA_INFO_WAVES; k++) { st += rad[k][0]; sy += rad[k][1]; }
     const bool degenerate = sy == 0.f;                         // no radius, no normalisation: the run reports the empty-window result
     const float fac = st / sy;
 
@@ -85,7 +78,7 @@ __global__ __launch_bounds__(EPI_NT) void cma_epilogue_info_kernel(int N, const 
         const int sp = (pp - rc) & 1, sfc = pp ? c1 : c0;          // stage c: aligned row p' comes from row p' - r_c of y, rolled by shift_c[p'] (wrapping)
         const float *yI = yr + (size_t)(sp * 2) * N, *yQ = yI + N;
         const __half *txI = txr + (size_t)(p * 2) * N, *txQ = txI + N;
-        const float scale = 0.5f * S, nusc = nu_sc[run];
+        const float nusc = nu_sc[run];
         const float i2v = 0.5f / var[run * 2 + pp];                // the demapper of the stage-c aligned polarisation, as in the epilogue
         float amp[NL], pen[NL];
 #pragma unroll
@@ -106,55 +99,16 @@ __global__ __launch_bounds__(EPI_NT) void cma_epilogue_info_kernel(int N, const 
             if (ms < 0) ms += N;
             const float g = (m >= EDGE && m < endc) ? fac : 1.0f;  // scaled exactly where the aligned index lies in W_c
             kept++;
-            const int tI = min(max((int)rintf(scale * __half2float(txI[n]) + scale), 0), S);         // shared_funcs.py:198
-            const int tQ = min(max((int)rintf(scale * __half2float(txQ[n]) + scale), 0), S);
-            const float yv[2] = {yI[ms] * g, yQ[ms] * g};
-            info_symbol_y<NL>(yv, tI, tQ, amp, pen, i2v, fs, se, be);
+            const __half txi = txI[n], txq = txQ[n];
+            float v[2][NL];
+            info_demap_log2<NL>(yI[ms] * g, amp, pen, i2v, v[0]);
+            info_demap_log2<NL>(yQ[ms] * g, amp, pen, i2v, v[1]);
+            info_symbol<NL, true, 8>(v, txi, txq, fs, se, be);
         }
-
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const float t = wave_sum_dpp(fs[i]);
-            if (lane == 0) sh.f[w][i] = t;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int a = info_wave_sum(se[i]), b = info_wave_sum(be[i]);
-            if (lane == 0) { sh.c[w][i] = a; sh.c[w][8 + i] = b; }
-        }
-        kept = info_wave_sum(kept);
-        if (lane == 0) sh.c[w][16] = kept;
-        __syncthreads();
-        if (tid == 0) {
-            int tot[17];
-            for (int i = 0; i < 17; i++) {
-                tot[i] = 0;
-                for (int k = 0; k < CMA_INFO_WAVES; k++) tot[i] += sh.c[k][i];
-            }
-            int h = 0;
-            for (int k = 1; k < 8; k++)
-                if (tot[k] < tot[h]) h = k;                        // fewest symbol errors, ties to the smallest h
-            float sa = 0.f, sg = 0.f;
-            for (int k = 0; k < CMA_INFO_WAVES; k++) { sa += sh.f[k][2 * h]; sg += sh.f[k][2 * h + 1]; }
-            float H = 0.f;                                         // per-axis entropy of the run's pmf; a zero entry contributes 0
-            for (int i = 0; i < NL; i++) {
-                const float pi = Pg[run * NL + i];
-                if (pi > 0.f) H -= pi * log2f(pi);
-            }
-            float *o = info + ((size_t)run * 2 + p) * 3;
-            int32_t *c = counts + ((size_t)run * 2 + p) * 4;
-            const int K = tot[16];
-            if (K == 0) {                                          // nothing kept, or no normalisation: no measurement
-                o[0] = o[1] = o[2] = NAN;
-                c[0] = c[1] = c[2] = c[3] = 0;
-            } else {
-                o[0] = 2.0f * H + sa / (float)K;
-                o[1] = 2.0f * H + sg / (float)K;
-                o[2] = (float)tot[8 + h] / ((float)(2 * NB) * (float)K);
-                c[0] = K; c[1] = tot[h]; c[2] = tot[8 + h]; c[3] = h;
-            }
-        }
-        __syncthreads();                                       // sh.f / sh.c are reused by the next polarisation
+        // (a degenerate run kept nothing: no normalisation is no measurement)
+        info_finish<NL, 8, CMA_INFO_WAVES, true>(sh, tid, fs, se, be, kept, Pg + run * NL, info + ((size_t)run * 2 + p) * 3,
+                                                 counts + ((size_t)run * 2 + p) * 4);
+        __syncthreads();                                       // sh is reused by the next polarisation
     }
 }
 
