@@ -4,7 +4,6 @@ from datetime import datetime
 from itertools import product
 
 import scipy.io as io
-import torch
 
 mod = '64-QAM'          # Modulation Format: {4,16,64}-QAM
 sps = 2                 # samples per symbol
@@ -34,31 +33,19 @@ def main():
     from . import sweep
     from .func_CMA_MQAM_shaping import run_awgn_cma_batch
 
-    rank, world, local_rank = sweep.init_distributed()
-    device = sweep.device_for_rank(local_rank, world)
-    if rank == 0:
-        print('Run code on: ', device, f'({world} rank(s))')
-    points = list(sweep_points())
-    mine = sweep.my_slice(len(points), rank, world)
-    local = torch.zeros(len(mine), num_epochs // epe, dtype=torch.float32)
-    for b, M in enumerate(sorted({points[i][1]["M"] for i in mine})):            # one batch per problem shape
-        sel = [k for k, i in enumerate(mine) if points[i][1]["M"] == M]
-        runs = [dict(SNR=points[mine[k]][1]["SNR"], nu=points[mine[k]][1]["nu"], lr_optim=points[mine[k]][1]["lr"],
-                     seed=None if base_seed is None else base_seed + 1000 * mine[k]) for k in sel]
-        local[sel] = run_awgn_cma_batch(runs, mod, sps, M, N_valid, train_len, num_epochs, epe, channel, device=device, generator=generator,
-                                        seed=sweep.stream_seed(base_seed, rank, b))
-    rows = sweep.gather_rows(local, len(points), rank, world)
-    if rank != 0:
+    def run_batch(M, pts, seeds, device, seed):
+        runs = [dict(SNR=p["SNR"], nu=p["nu"], lr_optim=p["lr"], seed=s) for p, s in zip(pts, seeds)]
+        return run_awgn_cma_batch(runs, mod, sps, M, N_valid, train_len, num_epochs, epe, channel, device=device, generator=generator, seed=seed)
+
+    out = sweep.run_sharded(list(sweep_points()), lambda p: p["M"], run_batch, base_seed,
+                            (len(SNR_vec), 1, 1, len(M_vec), len(lr_optim_vec), 1, iter), (num_epochs // epe,))
+    if out is None:
         return None
-    SER = torch.empty(len(SNR_vec), 1, 1, len(M_vec), len(lr_optim_vec), 1, iter, num_epochs // epe, dtype=torch.float32)
-    for k, (idx, _) in enumerate(points):
-        SER[idx] = rows[k]
     nu = nu_vec[-1]
     name = f"{savePATH}SERvsSNR_CMA_shaping_{nu}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
-    save_dict = {'SER': SER.numpy(), 'SNR': SNR_vec, 'M': M_vec, 'lr': lr_optim_vec, 'nu': nu_vec}
+    save_dict = {'SER': out[0].numpy(), 'SNR': SNR_vec, 'M': M_vec, 'lr': lr_optim_vec, 'nu': nu_vec}
     io.savemat(name, {'dict': save_dict})
     return name, save_dict
-
 
 if __name__ == "__main__":
     main()

@@ -4,7 +4,6 @@ from datetime import datetime
 from itertools import product
 
 import scipy.io as io
-import torch
 
 mod = '64-QAM'          # Modulation Format: {4,16,64}-QAM
 sps = 2                 # samples per symbol
@@ -38,42 +37,25 @@ def main():
     from . import sweep
     from .func_VAELE_MQAM_shaping import run_awgn_batch
 
-    rank, world, local_rank = sweep.init_distributed()
-    device = sweep.device_for_rank(local_rank, world)
-    if rank == 0:
-        print('Run code on: ', device, f'({world} rank(s))')
-    points = list(sweep_points())
-    mine = sweep.my_slice(len(points), rank, world)
+    def run_batch(shape, pts, seeds, device, seed):
+        M, N_train = shape
+        runs = [dict(SNR=p["SNR"], nu=p["nu"], lr_optim=p["lr"], seed=s) for p, s in zip(pts, seeds)]
+        r = run_awgn_batch(runs, mod, sps, M, N_train, N_valid, train_len, num_epochs, epe, channel, device=device, generator=generator, seed=seed,
+                           want_info=info_metrics)
+        return sweep.info_rows(r, INFO_KEYS) if info_metrics else r               # per run: SER | GMI | NGMI | AIR | BER
+
     n_eval = num_epochs // epe
-    local = torch.zeros(len(mine), 1 + len(INFO_KEYS), n_eval, dtype=torch.float32) if info_metrics else torch.zeros(len(mine), n_eval, dtype=torch.float32)
-    for b, (M, N_train) in enumerate(sorted({(points[i][1]["M"], points[i][1]["N_train"]) for i in mine})):   # one batch per problem shape
-        sel = [k for k, i in enumerate(mine) if (points[i][1]["M"], points[i][1]["N_train"]) == (M, N_train)]
-        runs = [dict(SNR=points[mine[k]][1]["SNR"], nu=points[mine[k]][1]["nu"], lr_optim=points[mine[k]][1]["lr"],
-                     seed=None if base_seed is None else base_seed + 1000 * mine[k]) for k in sel]
-        r = run_awgn_batch(runs, mod, sps, M, N_train, N_valid, train_len, num_epochs, epe, channel, device=device,
-                           generator=generator, seed=sweep.stream_seed(base_seed, rank, b), want_info=info_metrics)
-        if info_metrics:                                       # per run: SER | GMI | NGMI | AIR | BER
-            local[sel] = torch.stack([r[0]] + [r[1][k] for k in INFO_KEYS], dim=1)
-        else:
-            local[sel] = r
-    rows = sweep.gather_rows(local, len(points), rank, world)
-    if rank != 0:
+    out = sweep.run_sharded(list(sweep_points()), lambda p: (p["M"], p["N_train"]), run_batch, base_seed,
+                            (len(SNR_vec), 1, 1, len(M_vec), len(lr_optim_vec), len(N_train_vec), iter),
+                            (1 + len(INFO_KEYS), n_eval) if info_metrics else (n_eval,))
+    if out is None:
         return None
-    SER = torch.empty(len(SNR_vec), 1, 1, len(M_vec), len(lr_optim_vec), len(N_train_vec), iter, num_epochs // epe, dtype=torch.float32)
-    for k, (idx, _) in enumerate(points):
-        SER[idx] = rows[k, 0] if info_metrics else rows[k]
     nu = nu_vec[-1]
     name = f"{savePATH}SERvsSNR_VAELE_shaping_{nu}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
-    save_dict = {'SER': SER.numpy(), 'SNR': SNR_vec, 'M': M_vec, 'lr': lr_optim_vec, 'N_train': N_train_vec, 'nu': nu_vec}
-    if info_metrics:
-        for j, name_k in enumerate(INFO_KEYS):
-            arr = torch.empty_like(SER)
-            for k, (idx, _) in enumerate(points):
-                arr[idx] = rows[k, 1 + j]
-            save_dict[name_k] = arr.numpy()
+    save_dict = {'SER': out[0].numpy(), 'SNR': SNR_vec, 'M': M_vec, 'lr': lr_optim_vec, 'N_train': N_train_vec, 'nu': nu_vec}
+    save_dict.update({k: arr.numpy() for k, arr in zip(INFO_KEYS, out[1:])})
     io.savemat(name, {'dict': save_dict})
     return name, save_dict
-
 
 if __name__ == "__main__":
     main()

@@ -4,7 +4,6 @@ from datetime import datetime
 from itertools import product
 
 import scipy.io as io
-import torch
 
 mod = '64-QAM'          # Modulation Format: {4,16,64}-QAM
 sps = 2                 # samples per symbol
@@ -40,47 +39,27 @@ def main():
     from . import sweep
     from .func_VAENN_MQAM import run_vaenn_batch
 
-    rank, world, local_rank = sweep.init_distributed()
-    device = sweep.device_for_rank(local_rank, world)
-    if rank == 0:
-        print('Run code on: ', device, f'({world} rank(s))')
     name = save_dict = None
-    for net_type in net_type_vec:
-        points = list(sweep_points())
-        mine = sweep.my_slice(len(points), rank, world)
-        n_eval = num_epochs // epe
-        local = torch.zeros(len(mine), 1 + len(INFO_KEYS), n_eval, dtype=torch.float32) if info_metrics else torch.zeros(len(mine), n_eval, dtype=torch.float32)
-        key = lambda p: (p["M"], p["k1"], p["k2"], p["batch_len"])
-        for b, shape in enumerate(sorted({key(points[i][1]) for i in mine})):       # one batch per problem shape
-            sel = [k for k, i in enumerate(mine) if key(points[i][1]) == shape]
-            runs = [dict(SNR=points[mine[k]][1]["SNR"], lr_optim=points[mine[k]][1]["lr"],
-                         seed=None if base_seed is None else base_seed + 1000 * mine[k]) for k in sel]
+    for j, net_type in enumerate(net_type_vec):
+        def run_batch(shape, pts, seeds, device, seed):
             M, k1, k2, batch_len = shape
+            runs = [dict(SNR=p["SNR"], lr_optim=p["lr"], seed=s) for p, s in zip(pts, seeds)]
             r = run_vaenn_batch(runs, mod, sps, M, k1, k2, batch_len, N_valid, train_len, num_epochs, epe, channel, device=device,
-                                generator=generator, seed=sweep.stream_seed(base_seed, rank, b + 1000 * net_type_vec.index(net_type)), net_type=net_type,
-                                want_info=info_metrics)
-            if info_metrics:                                   # per run: SER | GMI | NGMI | AIR | BER
-                local[sel] = torch.stack([r[0]] + [r[1][k] for k in INFO_KEYS], dim=1)
-            else:
-                local[sel] = r
-        rows = sweep.gather_rows(local, len(points), rank, world)
-        if rank != 0:
-            continue
-        SER = torch.empty(len(SNR_vec), len(k2_vec), len(k1_vec), len(M_vec), len(lr_optim_vec), len(batch_len_vec), iter, num_epochs // epe,
-                          dtype=torch.float32)
-        for k, (idx, _) in enumerate(points):
-            SER[idx] = rows[k, 0] if info_metrics else rows[k]
-        name = f"{savePATH}SERvsSNR_{net_type}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
-        save_dict = {'SER': SER.numpy(), 'SNR': SNR_vec, 'k2': k2_vec, 'k1': k1_vec, 'M': M_vec, 'lr': lr_optim_vec, 'N_train': batch_len_vec}
-        if info_metrics:
-            for j, name_k in enumerate(INFO_KEYS):
-                arr = torch.empty_like(SER)
-                for k, (idx, _) in enumerate(points):
-                    arr[idx] = rows[k, 1 + j]
-                save_dict[name_k] = arr.numpy()
-        io.savemat(name, {'dict': save_dict})
-    return (name, save_dict) if rank == 0 else None
+                                generator=generator, seed=seed, net_type=net_type, want_info=info_metrics)
+            return sweep.info_rows(r, INFO_KEYS) if info_metrics else r           # per run: SER | GMI | NGMI | AIR | BER
 
+        n_eval = num_epochs // epe
+        out = sweep.run_sharded(list(sweep_points()), lambda p: (p["M"], p["k1"], p["k2"], p["batch_len"]), run_batch, base_seed,
+                                (len(SNR_vec), len(k2_vec), len(k1_vec), len(M_vec), len(lr_optim_vec), len(batch_len_vec), iter),
+                                (1 + len(INFO_KEYS), n_eval) if info_metrics else (n_eval,),
+                                batch_offset=1000 * net_type_vec.index(net_type), announce=j == 0)
+        if out is None:
+            continue
+        name = f"{savePATH}SERvsSNR_{net_type}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
+        save_dict = {'SER': out[0].numpy(), 'SNR': SNR_vec, 'k2': k2_vec, 'k1': k1_vec, 'M': M_vec, 'lr': lr_optim_vec, 'N_train': batch_len_vec}
+        save_dict.update({k: arr.numpy() for k, arr in zip(INFO_KEYS, out[1:])})
+        io.savemat(name, {'dict': save_dict})
+    return (name, save_dict) if sweep.dist_info()[0] == 0 else None
 
 if __name__ == "__main__":
     main()

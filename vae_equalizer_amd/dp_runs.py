@@ -15,7 +15,7 @@ import torch
 
 from . import channel as ch
 from . import shared_funcs as sfun
-from .engine import DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info  # noqa: F401
+from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info  # noqa: F401
 
 
 @dataclass
@@ -84,7 +84,6 @@ def check_one_symb_rate(runs, generator):
 
 
 _SIDE = {}
-INFO_FLOAT, INFO_INT = ("AIR", "GMI", "NGMI", "BER"), ("kept", "sym_err", "bit_err", "hyp")
 
 
 def _side_streams(device):

@@ -13,8 +13,60 @@ import torch
 from . import _native as nat
 
 
+INFO_FLOAT, INFO_INT = ("AIR", "GMI", "NGMI", "BER"), ("kept", "sym_err", "bit_err", "hyp")   # the keys of the info dicts: float32 figures, int64 counts
+
+
 def _f32(x, device):
     return torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
+
+
+def _per_run(x, R, shape, device):
+    """One value per run: x of ``shape`` (shared by the R runs) or [R, *shape] -> contiguous float32 [R, *shape]."""
+    t = _f32(x, device)
+    if t.dim() == len(shape):
+        t = t.expand(R, *shape)
+    if tuple(t.shape) != (R, *shape):
+        raise ValueError(f"expected shape {(R, *shape)} or {shape}, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _amp(amp_levels, dev):
+    return _f32(amp_levels, dev).reshape(-1)
+
+
+def _pmf(P, R, n, dev):                                  # the per-axis pmf [n] or [R,n] -> [R,n]
+    return _f32(P, dev).reshape(-1, n).expand(R, n).contiguous()
+
+
+def _var_nu(var, nu_sc, R, dev):                         # the soft demapper's constants: var [2] or [R,2] -> [R,2], nu_sc scalar or [R] -> [R]
+    return _f32(var, dev).expand(R, 2).contiguous(), _f32(nu_sc, dev).expand(R).contiguous()
+
+
+def _i32(t, shape, dev):
+    return torch.as_tensor(t, device=dev).to(torch.int32).reshape(shape).contiguous()
+
+
+def _f16(data):
+    return data.to(torch.float16).contiguous()
+
+
+def _alignment_out(R, dev):
+    """What an epilogue launch writes: SER[R,4] f32, shift[R,2,2] i32 and the exchange flags [R,2] i32 (stage q, then stage c)."""
+    e = lambda *s, dtype=torch.int32: torch.empty(R, *s, dtype=dtype, device=dev)
+    return e(4, dtype=torch.float32), e(2, 2), e(2)
+
+
+def _alignment_dict(ser, shift, rflag):
+    return dict(SER=ser, shift_q=shift[:, 0].long(), r_q=rflag[:, 0].long(), shift_c=shift[:, 1].long(), r_c=rflag[:, 1].long())
+
+
+def _info_dict(info, counts, P):
+    """An info kernel's info[..., 3] = (AIR, GMI, BER) and counts[..., 4] -> the dict of INFO_FLOAT + INFO_INT, with NGMI = 1 - (2 H - GMI) / (2 log2 n)
+    formed here in float32 from the entropy H of P[R,n]."""
+    H = -(P * torch.where(P > 0, torch.log2(P.clamp_min(torch.finfo(torch.float32).tiny)), torch.zeros_like(P))).sum(1, keepdim=info.dim() == 3)
+    gmi = info[..., 1]
+    return dict(AIR=info[..., 0], GMI=gmi, NGMI=1.0 - (2.0 * H - gmi) / (2.0 * math.log2(P.shape[1])), BER=info[..., 2],
+                kept=counts[..., 0].long(), sym_err=counts[..., 1].long(), bit_err=counts[..., 2].long(), hyp=counts[..., 3].long())
 
 
 class DPEngine:
@@ -26,24 +78,16 @@ class DPEngine:
             raise ValueError("M_est must be odd")
         self.device = torch.device(device)
         self.R, self.M, self.sps, self.threads = int(R), int(M_est), int(sps), int(threads)
-        self.amp = _f32(amp_levels, self.device).reshape(-1)
+        self.amp = _amp(amp_levels, self.device)
         self.n_lev = self.amp.numel()
-        self.P = self._per_run(P, (self.n_lev,))
-        self.var = self._per_run(var, (2,))
-        self.nu_sc = self._per_run(nu_sc, ())
+        self.P = _per_run(P, self.R, (self.n_lev,), self.device)
+        self.var = _per_run(var, self.R, (2,), self.device)
+        self.nu_sc = _per_run(nu_sc, self.R, (), self.device)
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)
         self.W, self.h = z(R, 2, 4, self.M), z(R, 2, 2, 2, self.M)
         self.mW, self.vW, self.mh, self.vh = z(R, 2, 4, self.M), z(R, 2, 4, self.M), z(R, 2, 2, 2, self.M), z(R, 2, 2, 2, self.M)
         self.step = torch.zeros(R, dtype=torch.int32, device=self.device)
         self.reset()
-
-    def _per_run(self, x, shape):
-        t = _f32(x, self.device)
-        if t.dim() == len(shape):
-            t = t.expand(self.R, *shape)
-        if tuple(t.shape) != (self.R, *shape):
-            raise ValueError(f"expected shape {(self.R, *shape)} or {shape}, got {tuple(t.shape)}")
-        return t.contiguous()
 
     def reset(self):
         """Dirac initialisation of W (shared_funcs.py:495) and h_est (:585); Adam state zeroed."""
@@ -93,7 +137,7 @@ class DPEngine:
         stride = B if stride is None else stride
         keep_len = B if keep_len is None else keep_len
         lr_h = lr_W if lr_h is None else lr_h
-        lrW, lrH = self._per_run(lr_W, ()), self._per_run(lr_h, ())
+        lrW, lrH = _per_run(lr_W, R, (), self.device), _per_run(lr_h, R, (), self.device)
         No = steps * keep_len
         dev = self.device
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -134,10 +178,9 @@ def soft_demap(y, amp_levels, var, nu_sc):
     if squeeze:
         y = y.unsqueeze(0)
     dev, R, N = y.device, y.shape[0], y.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
+    amp = _amp(amp_levels, dev)
     n = amp.numel()
-    var = _f32(var, dev).expand(R, 2).contiguous()
-    nu = _f32(nu_sc, dev).expand(R).contiguous()
+    var, nu = _var_nu(var, nu_sc, R, dev)
     y = y.contiguous()
     q = torch.empty(R, 2, 2 * n, N, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -154,10 +197,9 @@ def dp_forward(x, W, amp_levels, var, nu_sc, sps=2, want_q=True):
     x = pad_to_symbols(x, sps)
     dev, R = x.device, x.shape[0]
     N, M = x.shape[-1] // sps, W.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
+    amp = _amp(amp_levels, dev)
     n = amp.numel()
-    var = _f32(var, dev).expand(R, 2).contiguous()
-    nu = _f32(nu_sc, dev).expand(R).contiguous()
+    var, nu = _var_nu(var, nu_sc, R, dev)
     x, W = x.contiguous(), W.contiguous()
     q = torch.empty(R, 2, 2 * n, N, dtype=torch.float32, device=dev) if want_q else None
     y = torch.empty(R, 2, 2, N, dtype=torch.float32, device=dev)
@@ -176,7 +218,7 @@ def dp_loss(q, rx, h, amp_levels, P):
         q, rx, h = q.unsqueeze(0), rx.unsqueeze(0), h.unsqueeze(0)
     dev, R, B = q.device, q.shape[0], q.shape[-1]
     sps, M = rx.shape[-1] // B, h.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
+    amp = _amp(amp_levels, dev)
     n = amp.numel()
     Pt = _f32(P, dev)
     Pt = (Pt.expand(R, n) if Pt.dim() == 1 else Pt).contiguous()
@@ -198,9 +240,9 @@ class AWGNEngine:
             raise ValueError("M_est must be odd")
         self.device = torch.device(device)
         self.R, self.M, self.sps, self.threads = int(R), int(M_est), int(sps), int(threads)
-        self.amp = _f32(amp_levels, self.device).reshape(-1)
+        self.amp = _amp(amp_levels, self.device)
         self.n_lev = self.amp.numel()
-        pr = lambda x, shape: DPEngine._per_run(self, x, shape)
+        pr = lambda x, shape: _per_run(x, self.R, shape, self.device)
         self.P, self.amp_mean, self.var = pr(P, (self.n_lev,)), pr(amp_mean, ()), pr(var, ())
         z = lambda: torch.zeros(R, 2, self.M, dtype=torch.float32, device=self.device)
         self.W, self.h = z(), z()
@@ -220,7 +262,7 @@ class AWGNEngine:
         R, S = rx.shape[0], rx.shape[-1]
         if R != self.R or rx.shape[1] != 2:
             raise ValueError(f"rx must be [R={self.R}, 2, S], got {tuple(rx.shape)}")
-        lr_t = DPEngine._per_run(self, lr, ())
+        lr_t = _per_run(lr, R, (), self.device)
         dev = self.device
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         out = {"loss": e(R, steps), "q": e(R, 2 * self.n_lev, steps * B) if want_q else None,
@@ -272,7 +314,6 @@ class AWGNEngine:
     def validate_clean(self, frame, n_shift=21, return_sigma=False):
         """validate() on a channel.CleanAwgnFrame: the noise of the frame's (seed, frame index) is added while the samples are staged
         (vaeq_awgn_validate_gen) -- bit for bit validate(*generate_awgn_batch_hip(...)) without the noisy frame's round trip through HBM."""
-        import ctypes as C
         R, N = frame.R, frame.N
         if R != self.R or frame.sps != self.sps:
             raise ValueError(f"frame of {R} runs at {frame.sps} sps for an engine of {self.R} runs at {self.sps} sps")
@@ -402,9 +443,9 @@ class NNEngine:
         if R != self.R or tuple(data.shape) != (R, 2, N):
             raise ValueError(f"x must be [R={self.R}, 2, N*sps] and data [R, 2, N={N}], got {tuple(x.shape)}, {tuple(data.shape)}")
         n = self.n_lev
-        P = _f32([1.0 / n] * n if P is None else P, self.device).reshape(-1, n).expand(R, n).contiguous()
-        x, data = x.contiguous(), data.to(torch.float16).contiguous()
-        shift = torch.as_tensor(shift, device=self.device).to(torch.int32).reshape(R).contiguous()
+        P = _pmf([1.0 / n] * n if P is None else P, R, n, self.device)
+        x, data = x.contiguous(), _f16(data)
+        shift = _i32(shift, R, self.device)
         chunk = max(1, (1 << 30) // (2 * n * N * 4))
         parts = []
         for s in range(0, R, chunk):
@@ -422,42 +463,36 @@ def dp_epilogue(q, y, data, amp_levels, nu_sc, var, batch_len=None):
     """Per-frame epilogue on the device (vaeq_dp_epilogue): q[R,2,2n,N], y[R,2,2,N], data[R,2,2,N] fp16 ->
     dict(SER[R,4], shift_q[R,2], r_q[R], shift_c[R,2], r_c[R]).  batch_len None = VAEflex (no per-minibatch cut)."""
     dev, R, N = q.device, q.shape[0], q.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
+    amp = _amp(amp_levels, dev)
     n = amp.numel()
-    var = _f32(var, dev).expand(R, 2).contiguous()
-    nu = _f32(nu_sc, dev).expand(R).contiguous()
+    var, nu = _var_nu(var, nu_sc, R, dev)
     q, y = q.contiguous(), y.contiguous()
-    data = data.to(torch.float16).contiguous()
-    ser = torch.empty(R, 4, dtype=torch.float32, device=dev)
-    shift = torch.empty(R, 2, 2, dtype=torch.int32, device=dev)
-    rflag = torch.empty(R, 2, dtype=torch.int32, device=dev)
+    data = _f16(data)
+    ser, shift, rflag = _alignment_out(R, dev)
     ws = torch.empty(int(nat.lib().vaeq_dp_epilogue_ws_bytes(R, N)), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         nat.check(nat.lib().vaeq_dp_epilogue(R, N, n, int(batch_len or 0), nat.ptr(q), nat.ptr(y), nat.ptr(data, torch.float16),
                                              nat.ptr(amp), nat.ptr(var), nat.ptr(nu), nat.ptr(ser), nat.ptr(shift, torch.int32),
                                              nat.ptr(rflag, torch.int32), nat.ptr(ws, torch.uint8), nat.current_stream(dev)),
                   "vaeq_dp_epilogue")
-    return dict(SER=ser, shift_q=shift[:, 0].long(), r_q=rflag[:, 0].long(), shift_c=shift[:, 1].long(), r_c=rflag[:, 1].long())
+    return _alignment_dict(ser, shift, rflag)
 
 
 def dp_epilogue_compact(eq, dec, y, data, amp_levels, nu_sc, var, batch_len=None):
     """dp_epilogue fed by the training kernel's compact outputs of one frame (vaeq_dp_epilogue_compact): eq[R,2,N] f32,
     dec[R,2,2,N] int8, y[R,2,2,N], data[R,2,2,N] fp16 -> the same dict; bit-identical to dp_epilogue on that call's q."""
     dev, R, N = y.device, y.shape[0], y.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
-    var = _f32(var, dev).expand(R, 2).contiguous()
-    nu = _f32(nu_sc, dev).expand(R).contiguous()
+    amp = _amp(amp_levels, dev)
+    var, nu = _var_nu(var, nu_sc, R, dev)
     eq, dec, y = eq.contiguous(), dec.contiguous(), y.contiguous()
-    data = data.to(torch.float16).contiguous()
-    ser = torch.empty(R, 4, dtype=torch.float32, device=dev)
-    shift = torch.empty(R, 2, 2, dtype=torch.int32, device=dev)
-    rflag = torch.empty(R, 2, dtype=torch.int32, device=dev)
+    data = _f16(data)
+    ser, shift, rflag = _alignment_out(R, dev)
     with torch.cuda.device(dev):
         nat.check(nat.lib().vaeq_dp_epilogue_compact(R, N, amp.numel(), int(batch_len or 0), nat.ptr(eq), nat.ptr(dec, torch.int8), nat.ptr(y),
                                                      nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(var), nat.ptr(nu), nat.ptr(ser),
                                                      nat.ptr(shift, torch.int32), nat.ptr(rflag, torch.int32), nat.current_stream(dev)),
                   "vaeq_dp_epilogue_compact")
-    return dict(SER=ser, shift_q=shift[:, 0].long(), r_q=rflag[:, 0].long(), shift_c=shift[:, 1].long(), r_c=rflag[:, 1].long())
+    return _alignment_dict(ser, shift, rflag)
 
 
 def dp_epilogue_info(q=None, y=None, data=None, amp_levels=None, P=None, nu_sc=None, var=None, shift=None, r=None, batch_len=None):
@@ -470,17 +505,15 @@ def dp_epilogue_info(q=None, y=None, data=None, amp_levels=None, P=None, nu_sc=N
         raise ValueError("dp_epilogue_info takes exactly one of q and y")
     src = q if y is None else y
     dev, R, N = src.device, src.shape[0], src.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
+    amp = _amp(amp_levels, dev)
     n = amp.numel()
-    P = _f32(P, dev).reshape(-1, n).expand(R, n).contiguous()
+    P = _pmf(P, R, n, dev)
     var_t = nu_t = None
     if y is not None:
-        var_t = _f32(var, dev).expand(R, 2).contiguous()
-        nu_t = _f32(nu_sc, dev).expand(R).contiguous()
+        var_t, nu_t = _var_nu(var, nu_sc, R, dev)
     src = src.contiguous()
-    data = data.to(torch.float16).contiguous()
-    shift = torch.as_tensor(shift, device=dev).to(torch.int32).reshape(R, 2).contiguous()
-    r = torch.as_tensor(r, device=dev).to(torch.int32).reshape(R).contiguous()
+    data = _f16(data)
+    shift, r = _i32(shift, (R, 2), dev), _i32(r, R, dev)
     info = torch.empty(R, 2, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(R, 2, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -488,10 +521,7 @@ def dp_epilogue_info(q=None, y=None, data=None, amp_levels=None, P=None, nu_sc=N
                                                   nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(P), nat.ptr(var_t), nat.ptr(nu_t),
                                                   nat.ptr(shift, torch.int32), nat.ptr(r, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32),
                                                   nat.current_stream(dev)), "vaeq_dp_epilogue_info")
-    H = -(P * torch.where(P > 0, torch.log2(P.clamp_min(torch.finfo(torch.float32).tiny)), torch.zeros_like(P))).sum(1, keepdim=True)
-    gmi = info[:, :, 1]
-    return dict(AIR=info[:, :, 0], GMI=gmi, NGMI=1.0 - (2.0 * H - gmi) / (2.0 * math.log2(n)), BER=info[:, :, 2],
-                kept=counts[:, :, 0].long(), sym_err=counts[:, :, 1].long(), bit_err=counts[:, :, 2].long(), hyp=counts[:, :, 3].long())
+    return _info_dict(info, counts, P)
 
 
 def awgn_info(q=None, y=None, data=None, amp_levels=None, P=None, amp_mean=None, var=None, shift=None):
@@ -505,18 +535,18 @@ def awgn_info(q=None, y=None, data=None, amp_levels=None, P=None, amp_mean=None,
         raise ValueError("awgn_info takes exactly one of q and y")
     src = q if y is None else y
     dev, R, N = src.device, src.shape[0], src.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
+    amp = _amp(amp_levels, dev)
     n = amp.numel()
     if tuple(src.shape) != (R, 2 * n if y is None else 2, N) or tuple(data.shape) != (R, 2, N):
         raise ValueError(f"expected q[R,{2 * n},N] or y[R,2,N] and data[R,2,N], got {tuple(src.shape)}, {tuple(data.shape)}")
-    P = _f32(P, dev).reshape(-1, n).expand(R, n).contiguous()
+    P = _pmf(P, R, n, dev)
     am_t = var_t = None
     if y is not None:
         am_t = _f32(amp_mean, dev).expand(R).contiguous()
         var_t = _f32(var, dev).expand(R).contiguous()
     src = src.contiguous()
-    data = data.to(torch.float16).contiguous()
-    shift = torch.as_tensor(shift, device=dev).to(torch.int32).reshape(R).contiguous()
+    data = _f16(data)
+    shift = _i32(shift, R, dev)
     info = torch.empty(R, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(R, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -524,31 +554,25 @@ def awgn_info(q=None, y=None, data=None, amp_levels=None, P=None, amp_mean=None,
                                            nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(P), nat.ptr(am_t), nat.ptr(var_t),
                                            nat.ptr(shift, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32), nat.current_stream(dev)),
                   "vaeq_awgn_info")
-    H = -(P * torch.where(P > 0, torch.log2(P.clamp_min(torch.finfo(torch.float32).tiny)), torch.zeros_like(P))).sum(1)
-    gmi = info[:, 1]
-    return dict(AIR=info[:, 0], GMI=gmi, NGMI=1.0 - (2.0 * H - gmi) / (2.0 * math.log2(n)), BER=info[:, 2],
-                kept=counts[:, 0].long(), sym_err=counts[:, 1].long(), bit_err=counts[:, 2].long(), hyp=counts[:, 3].long())
+    return _info_dict(info, counts, P)
 
 
 def cma_epilogue(y, data, amp_levels, nu_sc, var):
     """The constant-modulus baselines' two-stage epilogue of one frame in one launch (vaeq_cma_epilogue): y[R,2,2,N] = phase-corrected output cut
     to [10:-10], data[R,2,2,N] fp16 cut likewise -> dict(SER[R,4] (constellation rows, then soft-demapper rows), shift_c, r_c, shift_q, r_q)."""
     dev, R, N = y.device, y.shape[0], y.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
-    var = _f32(var, dev).expand(R, 2).contiguous()
-    nu = _f32(nu_sc, dev).expand(R).contiguous()
+    amp = _amp(amp_levels, dev)
+    var, nu = _var_nu(var, nu_sc, R, dev)
     y = y.contiguous()
-    data = data.to(torch.float16).contiguous()
-    ser = torch.empty(R, 4, dtype=torch.float32, device=dev)
-    shift = torch.empty(R, 2, 2, dtype=torch.int32, device=dev)
-    rflag = torch.empty(R, 2, dtype=torch.int32, device=dev)
+    data = _f16(data)
+    ser, shift, rflag = _alignment_out(R, dev)
     L = nat.lib()
     ws = torch.empty(int(L.vaeq_dp_epilogue_ws_bytes(R, N)), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         nat.check(L.vaeq_cma_epilogue(R, N, amp.numel(), nat.ptr(y), nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(var), nat.ptr(nu), nat.ptr(ser),
                                       nat.ptr(shift, torch.int32), nat.ptr(rflag, torch.int32), nat.ptr(ws, torch.uint8), nat.current_stream(dev)),
                   "vaeq_cma_epilogue")
-    return dict(SER=ser, shift_q=shift[:, 0].long(), r_q=rflag[:, 0].long(), shift_c=shift[:, 1].long(), r_c=rflag[:, 1].long())
+    return _alignment_dict(ser, shift, rflag)
 
 
 def cma_epilogue_info(y, data, amp_levels, P, nu_sc, var, shift_c, r_c, shift_q, r_q):
@@ -559,17 +583,15 @@ def cma_epilogue_info(y, data, amp_levels, P, nu_sc, var, shift_c, r_c, shift_q,
     dict(AIR[R,2], GMI[R,2], NGMI[R,2], BER[R,2] f32 (NaN for a run without a normalisation); kept, sym_err, bit_err, hyp [R,2] int64).
     AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
     dev, R, N = y.device, y.shape[0], y.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1)
+    amp = _amp(amp_levels, dev)
     n = amp.numel()
     if tuple(y.shape) != (R, 2, 2, N) or tuple(data.shape) != (R, 2, 2, N):
         raise ValueError(f"expected y[R,2,2,N] and data[R,2,2,N], got {tuple(y.shape)}, {tuple(data.shape)}")
-    P = _f32(P, dev).reshape(-1, n).expand(R, n).contiguous()
-    var_t = _f32(var, dev).expand(R, 2).contiguous()
-    nu_t = _f32(nu_sc, dev).expand(R).contiguous()
+    P = _pmf(P, R, n, dev)
+    var_t, nu_t = _var_nu(var, nu_sc, R, dev)
     y = y.contiguous()
-    data = data.to(torch.float16).contiguous()
-    i32 = lambda t, shape: torch.as_tensor(t, device=dev).to(torch.int32).reshape(shape).contiguous()
-    sc, rc, sq, rq = i32(shift_c, (R, 2)), i32(r_c, (R,)), i32(shift_q, (R, 2)), i32(r_q, (R,))
+    data = _f16(data)
+    sc, rc, sq, rq = _i32(shift_c, (R, 2), dev), _i32(r_c, R, dev), _i32(shift_q, (R, 2), dev), _i32(r_q, R, dev)
     info = torch.empty(R, 2, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(R, 2, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -577,10 +599,7 @@ def cma_epilogue_info(y, data, amp_levels, P, nu_sc, var, shift_c, r_c, shift_q,
                                                    nat.ptr(nu_t), nat.ptr(sc, torch.int32), nat.ptr(rc, torch.int32), nat.ptr(sq, torch.int32),
                                                    nat.ptr(rq, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32), nat.current_stream(dev)),
                   "vaeq_cma_epilogue_info")
-    H = -(P * torch.where(P > 0, torch.log2(P.clamp_min(torch.finfo(torch.float32).tiny)), torch.zeros_like(P))).sum(1, keepdim=True)
-    gmi = info[:, :, 1]
-    return dict(AIR=info[:, :, 0], GMI=gmi, NGMI=1.0 - (2.0 * H - gmi) / (2.0 * math.log2(n)), BER=info[:, :, 2],
-                kept=counts[:, :, 0].long(), sym_err=counts[:, :, 1].long(), bit_err=counts[:, :, 2].long(), hyp=counts[:, :, 3].long())
+    return _info_dict(info, counts, P)
 
 
 def awgn_loss(q, x, h, amp_levels, P=None):
@@ -590,7 +609,7 @@ def awgn_loss(q, x, h, amp_levels, P=None):
     if single:
         q, x, h = q.unsqueeze(0), x.unsqueeze(0), h.unsqueeze(0)
     dev, R, B = q.device, q.shape[0], q.shape[-1]
-    amp = _f32(amp_levels, dev).reshape(-1).contiguous()
+    amp = _amp(amp_levels, dev).contiguous()
     n = amp.numel()
     q, x, h = q.contiguous().float(), x.contiguous().float(), h.contiguous().float()
     Pt = None if P is None else _f32(P, dev).expand(R, n).contiguous()
@@ -660,8 +679,8 @@ def awgn_cma_validate(rx, h, data, amp_levels, sps=2, n_shift=21, want_cpe=False
     if tuple(data.shape) != (R, 2, K) or tuple(h.shape[:2]) != (R, 2):
         raise ValueError(f"data must be [R={R}, 2, {K}] and h [R, 2, M], got {tuple(data.shape)}, {tuple(h.shape)}")
     rx, h = rx.contiguous(), h.contiguous()
-    data = data.to(torch.float16).contiguous()
-    amp = _f32(amp_levels, dev).reshape(-1)
+    data = _f16(data)
+    amp = _amp(amp_levels, dev)
     L = nat.lib()
     wsb = int(L.vaeq_awgn_cma_validate_ws_bytes(R, N, int(sps)))
     nat.check(min(wsb, 0), "vaeq_awgn_cma_validate_ws_bytes")
@@ -697,8 +716,8 @@ def awgn_lmmse_eval(rx, taps, data, amp_levels, n_shift=21, n_cut=20, want_out=F
     rx = rx.contiguous()
     h = _taps2(taps, R, dev)
     K = h.shape[-1]
-    data = data.to(torch.float16).contiguous()
-    amp = _f32(amp_levels, dev).reshape(-1)
+    data = _f16(data)
+    amp = _amp(amp_levels, dev)
     L = nat.lib()
     wsb = int(L.vaeq_awgn_lmmse_eval_ws_bytes(R, N, K))
     nat.check(min(wsb, 0), "vaeq_awgn_lmmse_eval_ws_bytes")
@@ -737,7 +756,7 @@ def awgn_dfe(rx, ff_taps, fb_taps, init_dec, amp_levels, data=None, n_shift=24, 
     C = c0 if C is None else int(C)
     W = w0 if W is None else int(W)
     init_dec = init_dec.to(dev, torch.int8).contiguous()
-    amp = _f32(amp_levels, dev).reshape(-1)
+    amp = _amp(amp_levels, dev)
     L = nat.lib()
     wsb = int(L.vaeq_awgn_dfe_ws_bytes(R, N, C))
     nat.check(min(wsb, 0), "vaeq_awgn_dfe_ws_bytes")
@@ -749,7 +768,7 @@ def awgn_dfe(rx, ff_taps, fb_taps, init_dec, amp_levels, data=None, n_shift=24, 
     if data is not None:
         if tuple(data.shape) != (R, 2, N):
             raise ValueError(f"data must be [R={R}, 2, {N}], got {tuple(data.shape)}")
-        data = data.to(torch.float16).contiguous()
+        data = _f16(data)
         ser = torch.empty(R, dtype=torch.float32, device=dev)
         shift = torch.empty(R, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):

@@ -4,13 +4,13 @@ training loop on one HIP wave per run (vaeq_awgn_cma) and each evaluated epoch -
 
 The mirrors CPE / find_shift_symb / SER_CMA / SER_symb keep the reference's call surface as batched torch restatements on the device; they
 are also the cross-check of the fused validation kernel (cma_validate_torch)."""
-import numpy as np
 import torch
 
 from . import channel as ch
-from .dp_runs import _host_pool, default_device, resolve_generator
+from .awgn_runs import check_generator, run_awgn_epochs
+from .dp_runs import default_device, resolve_generator
 from .engine import awgn_cma, awgn_cma_validate
-from .func_VAELE_MQAM_shaping import SER_symb, awgn_tables  # noqa: F401  (SER_symb: identical text in both reference modules)
+from .func_VAELE_MQAM_shaping import SER_symb, awgn_batch_tables, awgn_tables  # noqa: F401  (SER_symb: identical text in both reference modules)
 
 rcfir, rrcfir = ch.rcfir, ch.rrcfir
 generate_data = ch.generate_data                       # (:39-61) host restatement, reference signature + optional rng / noise streams
@@ -99,52 +99,20 @@ def run_awgn_cma_batch(runs, mod, sps, M_est, N_valid, N_train, num_epochs, epe,
     Returns SER_valid[R, num_epochs // epe] (CPU float32)."""
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
-    generator = resolve_generator(generator, any(r.get("seed") is not None for r in runs))
-    if generator not in ("hip", "numpy"):
-        raise ValueError(f"unknown generator {generator!r}")
-    if seed is None:                                                             # Philox key of the device generator: fresh entropy when not given
-        from .dp_runs import fresh_seed
-        seed = fresh_seed()
-    tab_of = {k: awgn_tables(mod, k[0], k[1], channel, sps) for k in {(r["nu"], r["SNR"]) for r in runs}}
-    tabs = [tab_of[(r["nu"], r["SNR"])] for r in runs]
-    t0 = tabs[0]
-    amp = torch.tensor(t0["amps"], dtype=torch.float32, device=device)
+    generator = check_generator(resolve_generator(generator, any(r.get("seed") is not None for r in runs)))
+    _, gen_args, host, seeded = awgn_batch_tables(runs, mod, sps, channel)
+    amp = torch.tensor(gen_args[0], dtype=torch.float32, device=device)
     h = torch.zeros(R, 2, M_est, dtype=torch.float32, device=device)
     h[:, 0, M_est // 2] = 1.0                                                    # :245-246
     lr = torch.tensor([r["lr_optim"] for r in runs], dtype=torch.float32, device=device)
-    streams = [ch.SeededStreams(r["seed"]) if r.get("seed") is not None else None for r in runs]
-    n_eval = num_epochs // epe
-    SER_dev = torch.empty(R, max(n_eval, 1), dtype=torch.float32, device=device)
-    P_all = np.stack([t["P"] for t in tabs])
-    snr_all = np.array([r["SNR"] for r in runs], dtype=np.float32)
-    draws = [0]
 
-    def draw(N):
-        if generator == "hip":
-            draws[0] += 1
-            return ch.generate_awgn_batch_hip(R, N, t0["amps"], P_all, snr_all, t0["h_channel"], sps, device, seed, draws[0] - 1)
+    def validate(draw, N):                                                       # :222-232
+        rxv, datav = draw(N)
+        ser, sh, _ = awgn_cma_validate(rxv, h, datav, amp, sps, N_SHIFT)
+        return ser, sh, None
 
-        def host(i):
-            t, r, st = tabs[i], runs[i], streams[i]
-            return ch.generate_data(N, t["M_channel"], t["amps"], r["SNR"], t["h_channel"], sps, "cpu", t["P"],
-                                    rng=st.next_rng() if st else None, noise=st.noise if st else None)
-        seeded = R > 1 and all(st is not None for st in streams)                   # own random streams: safe to generate concurrently
-        pairs = list(_host_pool().map(host, range(R))) if seeded else [host(i) for i in range(R)]
-        return torch.stack([p[0] for p in pairs]).to(device), torch.stack([p[1] for p in pairs]).to(device)
-
-    for epoch in range(num_epochs):
-        rx, _ = draw(N_train)                                                    # :218
-        loss, _, _ = awgn_cma(rx, h, lr, sps, update=True)                       # :219-220
-        if epoch % epe == 0 and epoch // epe < n_eval:                           # :222-232
-            rxv, datav = draw(N_valid)
-            ser, sh, _ = awgn_cma_validate(rxv, h, datav, amp, sps, N_SHIFT)
-            SER_dev[:, epoch // epe] = ser
-            if verbose:
-                loss_h, ser_h, sh_h = loss.cpu(), ser.cpu(), sh.cpu()
-                for i in range(R):
-                    tag = f"[run {i}] " if R > 1 else ""
-                    print(f"{tag}{epoch}", loss_h[i].item(), int(sh_h[i]), '\t\t\t\t\t\tSER = ', ser_h[i].item())
-    return SER_dev[:, :n_eval].cpu()
+    return run_awgn_epochs(R, device, num_epochs, epe, N_train, N_valid, lambda rx: awgn_cma(rx, h, lr, sps, update=True)[0], validate,   # :218-220
+                           generator, seed, gen_args, host, seeded, verbose)
 
 
 def processing(mod, sps, SNR, nu, M_est, lr_optim, N_valid, N_train, num_epochs, epe, channel, *, seed=None, device=None, verbose=True,

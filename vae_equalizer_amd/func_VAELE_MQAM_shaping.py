@@ -4,8 +4,9 @@ import numpy as np
 import torch
 
 from . import channel as ch
-from .dp_runs import _host_pool, default_device, resolve_generator
-from .engine import AWGNEngine
+from .awgn_runs import check_generator, first_run, run_awgn_epochs
+from .dp_runs import default_device, resolve_generator
+from .engine import INFO_FLOAT as INFO_FIGURES, INFO_INT as INFO_COUNTS, AWGNEngine  # noqa: F401  (the keys of engine.awgn_info, under this module's names)
 from .shared_funcs import _CHANNELS, qam_tables
 
 
@@ -24,8 +25,6 @@ def awgn_tables(mod, nu, SNR, channel, sps):
     amp_mean = np.sum(np.abs(shaped.real) + np.abs(shaped.imag)) / 2             # :271
     return dict(amps=t["amps"], P=t["P"], amp_mean=amp_mean, var=10 ** (-SNR / 10), h_channel=h_channel, M_channel=len(ir), n=n)
 
-
-INFO_FIGURES, INFO_COUNTS = ("AIR", "GMI", "NGMI", "BER"), ("kept", "sym_err", "bit_err", "hyp")   # the keys of engine.awgn_info
 
 generate_data = ch.generate_data                       # (:39-61) host restatement, reference signature + optional rng / noise streams
 
@@ -105,6 +104,22 @@ def SER_symb(rx, tx, sps, amp_levels, num_lev, device=None):
     return torch.stack([((data - d) != 0).any(dim=0).float().mean() for d in (dec, dec_pi, dec_pi4, dec_3pi4)]).min()
 
 
+def awgn_batch_tables(runs, mod, sps, channel):
+    """What run_awgn_batch and run_awgn_cma_batch derive from ``runs``: one table set per sweep point (not per run) -> (tabs[R], gen_args = the
+    device generator's (amps, P[R,n], SNR[R], h_channel, sps), host(N, i) = run i's frame of N symbols from the bit-faithful host channel model,
+    seeded = every run carries a seed and so owns its random streams)."""
+    tab_of = {k: awgn_tables(mod, k[0], k[1], channel, sps) for k in {(r["nu"], r["SNR"]) for r in runs}}
+    tabs = [tab_of[(r["nu"], r["SNR"])] for r in runs]
+    streams = [ch.SeededStreams(r["seed"]) if r.get("seed") is not None else None for r in runs]
+
+    def host(N, i):
+        t, r, st = tabs[i], runs[i], streams[i]
+        return ch.generate_data(N, t["M_channel"], t["amps"], r["SNR"], t["h_channel"], sps, "cpu", t["P"],
+                                rng=st.next_rng() if st else None, noise=st.noise if st else None)
+    gen_args = (tabs[0]["amps"], np.stack([t["P"] for t in tabs]), np.array([r["SNR"] for r in runs], dtype=np.float32), tabs[0]["h_channel"], sps)
+    return tabs, gen_args, host, all(st is not None for st in streams)
+
+
 def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epochs, epe, channel, device=None, verbose=False,
                    generator=None, seed=None, want_info=False):
     """R AWGN VAE-LE runs at once: ``runs`` = list of dict(SNR, nu, lr_optim, seed).  Per epoch ONE training launch and, on evaluated
@@ -117,65 +132,25 @@ def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epoch
     bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: engine.awgn_info in y-mode on the y and the shift of every validation launch."""
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
-    generator = resolve_generator(generator, any(r.get("seed") is not None for r in runs))
-    if seed is None:                                                             # Philox key of the device generator: fresh entropy when not given
-        from .dp_runs import fresh_seed
-        seed = fresh_seed()
-    tab_of = {k: awgn_tables(mod, k[0], k[1], channel, sps) for k in {(r["nu"], r["SNR"]) for r in runs}}   # one table set per sweep point, not per run
-    tabs = [tab_of[(r["nu"], r["SNR"])] for r in runs]
-    t0 = tabs[0]
-    amp = torch.tensor(t0["amps"], dtype=torch.float32, device=device)
-    eng = AWGNEngine(R, M_est, amp, np.stack([t["P"] for t in tabs]), [t["amp_mean"] for t in tabs], [t["var"] for t in tabs],
-                     device, sps)
+    generator = check_generator(resolve_generator(generator, any(r.get("seed") is not None for r in runs)))
+    tabs, gen_args, host, seeded = awgn_batch_tables(runs, mod, sps, channel)
+    amp = torch.tensor(gen_args[0], dtype=torch.float32, device=device)
+    eng = AWGNEngine(R, M_est, amp, gen_args[1], [t["amp_mean"] for t in tabs], [t["var"] for t in tabs], device, sps)
     lr = np.array([r["lr_optim"] for r in runs], dtype=np.float32)
-    streams = [ch.SeededStreams(r["seed"]) if r.get("seed") is not None else None for r in runs]
     steps = N_train // batch_len                                                 # :297 (the remainder is dropped)
-    n_eval = num_epochs // epe
-    SER_dev = torch.empty(R, max(n_eval, 1), dtype=torch.float32, device=device)
-    info_dev = {k: torch.empty(R, max(n_eval, 1), dtype=torch.float32 if k in INFO_FIGURES else torch.int64, device=device)
-                for k in INFO_FIGURES + INFO_COUNTS} if want_info else None
-    P_all = np.stack([t["P"] for t in tabs])
-    snr_all = np.array([r["SNR"] for r in runs], dtype=np.float32)
-    draws = [0]
 
-    def draw(N):
-        if generator == "hip":
-            draws[0] += 1
-            return ch.generate_awgn_batch_hip(R, N, t0["amps"], P_all, snr_all, t0["h_channel"], sps, device, seed, draws[0] - 1)
-        if generator != "numpy":
-            raise ValueError(f"unknown generator {generator!r}")
-        def host(i):
-            t, r, st = tabs[i], runs[i], streams[i]
-            return ch.generate_data(N, t["M_channel"], t["amps"], r["SNR"], t["h_channel"], sps, "cpu", t["P"],
-                                    rng=st.next_rng() if st else None, noise=st.noise if st else None)
-        seeded = R > 1 and all(st is not None for st in streams)                   # own random streams: safe to generate concurrently
-        pairs = list(_host_pool().map(host, range(R))) if seeded else [host(i) for i in range(R)]
-        return torch.stack([p[0] for p in pairs]).to(device), torch.stack([p[1] for p in pairs]).to(device)
+    def validate(draw, N):                                                       # :308-318
+        if generator == "hip" and ch.awgn_clean_supported(sps, M_est):           # the validation frame is read once: its noise goes on while it is read
+            frame = draw(N, clean=True)
+            ser, sh, yv = eng.validate_clean(frame, 21)
+            datav = frame.data
+        else:
+            rxv, datav = draw(N)
+            ser, sh, yv = eng.validate(rxv, datav, 21)
+        return ser, sh, eng.info(yv, datav, sh) if want_info else None
 
-    for epoch in range(num_epochs):
-        rx, _ = draw(N_train)
-        out = eng.train(rx, batch_len, steps, lr)
-        if epoch % epe == 0 and epoch // epe < n_eval:                           # :308-318
-            if generator == "hip" and ch.awgn_clean_supported(sps, M_est):       # the validation frame is read once: its noise goes on while it is read
-                draws[0] += 1
-                frame = ch.generate_awgn_clean_batch_hip(R, N_valid, t0["amps"], P_all, snr_all, t0["h_channel"], sps, device, seed, draws[0] - 1)
-                ser, sh, yv = eng.validate_clean(frame, 21)
-                datav = frame.data
-            else:
-                rxv, datav = draw(N_valid)
-                ser, sh, yv = eng.validate(rxv, datav, 21)
-            SER_dev[:, epoch // epe] = ser
-            if want_info:
-                for k, v in eng.info(yv, datav, sh).items():
-                    info_dev[k][:, epoch // epe] = v
-            if verbose:
-                loss, ser_h, sh_h = out["loss"][:, -1].cpu(), ser.cpu(), sh.cpu()
-                for i in range(R):
-                    tag = f"[run {i}] " if R > 1 else ""
-                    print(f"{tag}{epoch}", loss[i].item(), int(sh_h[i]), '\t\t\t\t\t\tSER = ', ser_h[i].item())
-    if want_info:
-        return SER_dev[:, :n_eval].cpu(), {k: v[:, :n_eval].cpu() for k, v in info_dev.items()}
-    return SER_dev[:, :n_eval].cpu()
+    return run_awgn_epochs(R, device, num_epochs, epe, N_train, N_valid, lambda rx: eng.train(rx, batch_len, steps, lr)["loss"][:, -1], validate,
+                           generator, seed, gen_args, host, seeded, verbose, want_info)
 
 
 def processing(mod, sps, SNR, nu, M_est, lr_optim, batch_len, N_valid, N_train, num_epochs, epe, channel, *, seed=None,
@@ -189,4 +164,4 @@ def processing(mod, sps, SNR, nu, M_est, lr_optim, batch_len, N_valid, N_train, 
         print("We are using the following device for learning:", device)
     out = run_awgn_batch([dict(SNR=SNR, nu=nu, lr_optim=lr_optim, seed=seed)], mod, sps, M_est, batch_len, N_valid, N_train,
                          num_epochs, epe, channel, device=device, verbose=verbose, generator=generator, want_info=want_info)
-    return (out[0][0], {k: v[0] for k, v in out[1].items()}) if want_info else out[0]
+    return first_run(out, want_info)

@@ -12,7 +12,8 @@ import torch
 from torch import nn
 
 from . import channel as ch
-from .dp_runs import _host_pool, default_device
+from .awgn_runs import check_generator, first_run, run_awgn_epochs
+from .dp_runs import default_device
 from .engine import NNEngine
 from .func_VAELE_MQAM_shaping import SER_q, SER_symb, find_shift  # noqa: F401  (identical helpers in both reference files)
 from .shared_funcs import _CHANNELS, _LEVELS
@@ -153,6 +154,7 @@ def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_vali
     t = vaenn_tables(mod, channel, sps)
     if net_type not in ("Net", "Net_BN"):
         raise UnboundLocalError(f"unknown net_type {net_type!r} (the reference leaves `net` unbound, :239-243)")
+    check_generator(generator)
     eng = NNEngine(R, M_est, kernel_1, kernel_2, t["amps"], device, sps, batch_norm=(net_type == "Net_BN"))
     if theta0 is None:
         gen = torch.Generator(device=device)
@@ -163,45 +165,18 @@ def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_vali
         eng.theta.copy_(torch.as_tensor(theta0, dtype=torch.float32, device=device).expand(R, -1))
     lr = np.array([r["lr_optim"] for r in runs], dtype=np.float32)
     snr = np.array([r["SNR"] for r in runs], dtype=np.float32)
-    sigma = np.sqrt(0.5) / 10 ** (snr / 20)
-    P = np.full(t["n"], 1.0 / t["n"])
     rngs = [np.random.RandomState(r["seed"]) if r.get("seed") is not None else None for r in runs]
     steps = N_train // batch_len
-    n_eval = num_epochs // epe
-    SER_dev = torch.empty(R, max(n_eval, 1), dtype=torch.float32, device=device)
-    info_dev = {k: torch.empty(R, max(n_eval, 1), dtype=torch.float32 if k in ("AIR", "GMI", "NGMI", "BER") else torch.int64, device=device)
-                for k in ("AIR", "GMI", "NGMI", "BER", "kept", "sym_err", "bit_err", "hyp")} if want_info else None
-    draws = [0]
 
-    def draw(N):
-        if generator == "hip":
-            draws[0] += 1
-            return ch.generate_awgn_batch_hip(R, N, t["amps"], P, snr, t["h_channel"], sps, device, seed, draws[0] - 1, sigma_fixed=sigma)
-        if generator != "numpy":
-            raise ValueError(f"unknown generator {generator!r}")
-        host = lambda i: generate_data(N, t["M_channel"], t["constellation"], runs[i]["SNR"], t["h_channel"], sps, "cpu", rngs[i])
-        seeded = R > 1 and all(g is not None for g in rngs)                         # own random streams: safe to generate concurrently
-        pairs = list(_host_pool().map(host, range(R))) if seeded else [host(i) for i in range(R)]
-        return torch.stack([p[0] for p in pairs]).to(device), torch.stack([p[1] for p in pairs]).to(device)
+    def validate(draw, N):
+        rxv, datav = draw(N)
+        ser, sh = eng.validate(rxv, datav, 21)
+        return ser, sh, eng.info(rxv, datav, sh) if want_info else None
 
-    for epoch in range(num_epochs):
-        rx, _ = draw(N_train)
-        out = eng.train(rx, batch_len, steps, lr)
-        if epoch % epe == 0 and epoch // epe < n_eval:
-            rxv, datav = draw(N_valid)
-            ser, sh = eng.validate(rxv, datav, 21)
-            SER_dev[:, epoch // epe] = ser
-            if want_info:
-                for k, v in eng.info(rxv, datav, sh).items():
-                    info_dev[k][:, epoch // epe] = v
-            if verbose:
-                loss, ser_h, sh_h = out["loss"][:, -1].cpu(), ser.cpu(), sh.cpu()
-                for i in range(R):
-                    tag = f"[run {i}] " if R > 1 else ""
-                    print(f"{tag}{epoch}", loss[i].item(), int(sh_h[i]), '\t\t\t\t\t\tSER = ', ser_h[i].item())
-    if want_info:
-        return SER_dev[:, :n_eval].cpu(), {k: v[:, :n_eval].cpu() for k, v in info_dev.items()}
-    return SER_dev[:, :n_eval].cpu()
+    return run_awgn_epochs(R, device, num_epochs, epe, N_train, N_valid, lambda rx: eng.train(rx, batch_len, steps, lr)["loss"][:, -1], validate,
+                           generator, seed, (t["amps"], np.full(t["n"], 1.0 / t["n"]), snr, t["h_channel"], sps),
+                           lambda N, i: generate_data(N, t["M_channel"], t["constellation"], runs[i]["SNR"], t["h_channel"], sps, "cpu", rngs[i]),
+                           all(g is not None for g in rngs), verbose, want_info, sigma_fixed=np.sqrt(0.5) / 10 ** (snr / 20))
 
 
 def processing(mod, sps, SNR, M_est, kernel_1, kernel_2, lr_optim, batch_len, N_valid, N_train, num_epochs, epe, channel, net_type, *,
@@ -214,4 +189,4 @@ def processing(mod, sps, SNR, M_est, kernel_1, kernel_2, lr_optim, batch_len, N_
     out = run_vaenn_batch([dict(SNR=SNR, lr_optim=lr_optim, seed=seed)], mod, sps, M_est, kernel_1, kernel_2, batch_len, N_valid, N_train,
                           num_epochs, epe, channel, device=device, verbose=verbose, generator=generator, seed=seed or 0, theta0=theta0,
                           net_type=net_type, want_info=want_info)
-    return (out[0][0], {k: v[0] for k, v in out[1].items()}) if want_info else out[0]
+    return first_run(out, want_info)

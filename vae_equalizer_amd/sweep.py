@@ -82,3 +82,37 @@ def gather_rows(local_rows, n_runs, rank=None, world=None, force_collective=None
     for k in range(world):
         out[k::world] = allbuf[k, :len(range(k, n_runs, world))]                    # run r lives on rank r % world
     return out
+
+
+def run_sharded(points, shape_key, run_batch, base_seed, result_shape, row_shape, batch_offset=0, announce=True):
+    """The sharded sweep of the AWGN scripts: ``points`` = [(index into the result arrays, point)], this rank's share (my_slice) run as one
+    batch per problem shape -- shape_key(point), in sorted order -- and gathered once (gather_rows).
+
+    run_batch(shape, pts, seeds, device, seed) -> rows[len(pts), *row_shape]: ``seeds`` the per-run seeds (base_seed + 1000 * the point's number,
+    None without base_seed), ``seed`` = stream_seed(base_seed, rank, batch number + batch_offset), the key of the batch's device-generator streams.
+    row_shape (n_eval,) gives one result array, (K, n_eval) gives K of them, each of result_shape + (n_eval,).
+    Returns the list of result arrays (float32) on rank 0, None elsewhere.  announce: rank 0 prints the device line."""
+    rank, world, local_rank = init_distributed()
+    device = device_for_rank(local_rank, world)
+    if rank == 0 and announce:
+        print('Run code on: ', device, f'({world} rank(s))')
+    mine = my_slice(len(points), rank, world)
+    local = torch.zeros(len(mine), *row_shape, dtype=torch.float32)
+    for b, shape in enumerate(sorted({shape_key(points[i][1]) for i in mine})):   # one batch per problem shape
+        sel = [k for k, i in enumerate(mine) if shape_key(points[i][1]) == shape]
+        local[sel] = run_batch(shape, [points[mine[k]][1] for k in sel], [None if base_seed is None else base_seed + 1000 * mine[k] for k in sel],
+                               device, stream_seed(base_seed, rank, b + batch_offset))
+    rows = gather_rows(local, len(points), rank, world)
+    if rank != 0:
+        return None
+    rows = rows.reshape(len(points), *row_shape[-2:]) if len(row_shape) > 1 else rows.unsqueeze(1)
+    out = [torch.empty(*result_shape, row_shape[-1], dtype=torch.float32) for _ in range(rows.shape[1])]
+    for j, arr in enumerate(out):
+        for k, (idx, _) in enumerate(points):
+            arr[idx] = rows[k, j]
+    return out
+
+
+def info_rows(r, keys):
+    """A runner's (SER, info) -> rows [R, 1 + len(keys), n_eval]: per run SER, then info[k] for k in keys."""
+    return torch.stack([r[0]] + [r[1][k] for k in keys], dim=1)
