@@ -530,6 +530,44 @@ int vaeq_awgn_dfe(int32_t R, int64_t N, int32_t sps, int32_t n_lev, int32_t K1, 
                   const void *data_f16, void *ws, int8_t *dec, float *ser, int32_t *shift, int32_t *repairs, float *ff_out, void *stream);
 int64_t vaeq_awgn_dfe_ws_bytes(int32_t R, int64_t N, int32_t C);
 
+/* Information-rate figures of the AWGN baselines, per run, on a complex soft sequence ("track") z in memory, over exactly the symbols the SER of
+ * its validator keeps.  All three baselines end in one shape: z of Nz samples against TX data of Nd symbols through z[:, e+sh : -e] and
+ * data[:, e : -e-sh], sh = shift[r], e = edge: 11 for the constant-modulus script (func_CMA_MQAM_shaping.py:231-232, z = cpe_out of
+ * vaeq_awgn_cma_validate, planar [R][2][Nz]: interleaved = 0), N_cut + 11 = 31 for the LMMSE and the DFE (DFE_MQAM_shaping.py:281, :293; z = out of
+ * vaeq_awgn_lmmse_eval, Nz = Nd + 1, or the z of vaeq_awgn_dfe_soft, Nz = Nd; [R][Nz][2]: interleaved = 1).
+ * Window: L = Nd - 2 e - sh symbols are kept, the slice of z holds Lz = Nz - 2 e - sh samples; kept symbol j < L pairs z[e + sh + j] with TX
+ * symbol e + j.  It is empty when e + sh <= 0 or L <= 0 (the reference's -0 slice), computed in 64 bits: no int32 shift takes an index out of a
+ * row, and shifts are not clamped (find_shift_symb(., ., 24) returns -12 .. +11).
+ * Normalisation (SER_CMA :73 = SER_func :117): scale = (sum_{j<L} |tx_j| / L) / (sum_{m<Lz} |z[e+sh+m]| / Lz), |.| the complex radius, over ALL Lz
+ * samples of the slice; zhat = z scale.  A slice whose sum of |z| is zero has no normalisation: the empty-window result.
+ * Demapper: the AWGN reference's own (func_VAELE_MQAM_shaping.py:229), per axis v_i = -(zhat_c - a_i)^2 / var[r], posteriors = log-softmax of v:
+ * no 1/2 and no prior term, so the first maximum of the posterior is the nearest level.  var[R] is the caller's; the host layers pass
+ * 10^(-SNR/10) (:272), what the VAE-LE of the same sweep point uses.
+ * Gray labels, H, TX level, the four hypotheses (the relabelings of SER_CMA / SER_func: 0, pi, pi/2, 3 pi/2, in that order), tie-break, AIR, GMI,
+ * BER, the K == 0 rule and the outputs are vaeq_awgn_info's y-mode: data_f16[R][2][Nd] IEEE half, amp[n_lev], P[R][n_lev] the runs' per-axis pmf
+ * -> info[R][3] = AIR, GMI, BER; counts[R][4] = kept, sym_err, bit_err, hyp (NGMI is the host's).  The kernel decides with its own radius sums,
+ * so sym_err / kept is the validator's SER except where a sample lies within float32 rounding of a decision threshold.  (The DFE's validator
+ * scores the HARD decisions, whose mean radius SER_func normalises; the figures normalise the soft sequence, whose mean radius the noise raises a
+ * little.  A slicer input within that difference of a threshold -- a fraction of a per cent of a level spacing -- is decided the other way: at low
+ * SNR sym_err can differ from SER kept by a symbol or two.)
+ * One launch, one 256-thread workgroup per run, a pre-pass for the two radius sums and one pass over the window; sums run in a fixed order without
+ * atomics: two calls give identical bits, R runs in one call the bits of R single calls.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); any NULL pointer is VAEQ_ERR_NULL, before any shape rule; R < 0, Nd < 1, Nz not in {Nd, Nd + 1},
+ * Nz > 0x3fffffff, edge < 0, interleaved not in {0, 1} or n_lev not in {2, 4, 8} is VAEQ_ERR_SHAPE. */
+int vaeq_awgn_track_info(int32_t R, int64_t Nz, int64_t Nd, int32_t n_lev, int32_t edge, int32_t interleaved, const float *z,
+                         const void *data_f16, const float *amp, const float *P, const float *var, const int32_t *shift, float *info,
+                         int32_t *counts, void *stream);
+
+/* The DFE's soft sequence.  The reference's dfe() leaves only hard decisions; its soft value is the slicer input (DFE_MQAM_shaping.py:215-221),
+ * rebuilt here from what vaeq_awgn_dfe returns: ff[R][N] complex64 (ff_out), fb[R][2][K2] (re, im; the feedback taps), dec[R][N] int8, amp[n_lev]
+ *   z[p] = ff[p] + sum_{j < K2} fb[j] c(dec[p - 1 - j]) for p >= K2,   c(i) = amp[i / n_lev] + j amp[i % n_lev]
+ * -- plain complex products without conjugation, added to the feed-forward sample with j ascending -- and z[p] = c(dec[p]) for p < K2, the state the
+ * reference holds where no slicer input exists.  z[R][N] complex64.  One thread per sample.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); any NULL pointer is VAEQ_ERR_NULL, before any shape rule; R < 0, N < 1, N > 0x3fffffff, n_lev not
+ * in {2, 4, 8} or K2 outside 1 .. 10 (vaeq_awgn_dfe's range) is VAEQ_ERR_SHAPE. */
+int vaeq_awgn_dfe_soft(int32_t R, int64_t N, int32_t n_lev, int32_t K2, const float *ff, const float *fb, const int8_t *dec, const float *amp,
+                       float *z, void *stream);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

@@ -7,6 +7,9 @@ in torch cfloat, as in the reference.
 
 The one intended difference: importing this module runs nothing.  The reference runs its sweep and a plot at import; here the sweep is
 ``main()`` (or ``python -m vae_equalizer_amd.DFE_MQAM_shaping``) and returns (SER_mmse, SER_dfe).  Plotting is out of scope.
+
+``info_metrics = True`` adds what a shaping sweep is read in -- GMI, NGMI, achievable rate and pre-FEC BER of both curves -- over exactly the
+symbols each SER keeps (engine.awgn_track_info; the DFE's soft sequence is its slicer input, engine.awgn_dfe_soft).
 """
 import numpy as np
 import torch
@@ -64,6 +67,7 @@ num_epochs = 5
 n1 = (lmmse_filter_order - 1) // 2 + 1
 N_SHIFT_LMMSE, N_SHIFT_DFE = 21, 24                    # find_shift_symb lags (:280, :292)
 
+info_metrics = False    # True: main() also returns the info dicts of both curves (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp)
 base_seed = None        # int -> reproducible frames (the reference's stream under the same seed); None = like the reference
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
 
@@ -177,15 +181,18 @@ def _filters(h, SNR):
 
 
 def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.0270955, *, seed=None, generator=None, device=None,
-                  verbose=False, C=None, W=None):
+                  verbose=False, C=None, W=None, want_info=False):
     """The script's loop nest (:264-296) for a channel (h_orig: symbol-spaced taps, default h_1) and a modulation, all frames at once:
     R = len(SNRs) * num_epochs frames, one generator call, ONE LMMSE evaluation launch and ONE DFE launch.
 
     seed / generator: as in Eval_run_shaping_cma.py -- with a seed the frames come from the reference-faithful numpy generator in the
     reference's loop order (SNR-major; those of the reference under the same seed), without one from the device generator.
-    Returns dict(SER_mmse [num_snr, num_epochs], SER_dfe (CPU float32), shift_mmse, shift_dfe, repairs (numpy), C, W)."""
+    Returns dict(SER_mmse [num_snr, num_epochs], SER_dfe (CPU float32), shift_mmse, shift_dfe, repairs (numpy), C, W); with want_info also
+    info_mmse and info_dfe, each dict(AIR, GMI, NGMI, BER f32; kept, sym_err, bit_err, hyp int64) of [num_snr, num_epochs] CPU tensors:
+    engine.awgn_track_info at edge N_cut + 11 on the LMMSE output (one sample longer than the data) at shift_mmse and on the DFE's slicer input
+    (engine.awgn_dfe_soft) at shift_dfe, demapped at var = 10^(-SNR/10), the VAE-LE's of the same SNR (func_VAELE_MQAM_shaping.py:272)."""
     from .dp_runs import default_device, fresh_seed, resolve_generator
-    from .engine import awgn_dfe, awgn_lmmse_eval
+    from .engine import awgn_dfe, awgn_dfe_soft, awgn_lmmse_eval, awgn_track_info
     device = default_device() if device is None else torch.device(device)
     h = channel_taps(CHANNELS["h1"] if h_orig is None else np.asarray(h_orig), sps)
     q = qam_constants(mod)
@@ -209,10 +216,18 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
                                              fresh_seed() if seed is None else seed, 0)
     else:
         raise ValueError(f"unknown generator {generator!r}")
-    ser_m, sh_m, dec_m, _ = awgn_lmmse_eval(rx, lm, data, amps, N_SHIFT_LMMSE, N_cut)
-    r = awgn_dfe(rx, ff, fb, dec_m, amps, data, N_SHIFT_DFE, N_cut, C=C, W=W)
+    ser_m, sh_m, dec_m, out_m = awgn_lmmse_eval(rx, lm, data, amps, N_SHIFT_LMMSE, N_cut, want_out=want_info)
+    r = awgn_dfe(rx, ff, fb, dec_m, amps, data, N_SHIFT_DFE, N_cut, C=C, W=W, want_ff=want_info)
+    info = {}
+    if want_info:
+        P = ch.pcs_probabilities(amps, nu)
+        var = [10 ** (-SNRs[k // E] / 10) for k in range(R)]
+        on_grid = lambda d: {k: v.cpu().reshape(S, E) for k, v in d.items()}  # noqa: E731
+        info["info_mmse"] = on_grid(awgn_track_info(out_m, data, amps, P, var, sh_m, N_cut + 11))
+        info["info_dfe"] = on_grid(awgn_track_info(awgn_dfe_soft(r["ff"], fb, r["dec"], amps), data, amps, P, var, r["shift"], N_cut + 11))
     out = dict(SER_mmse=ser_m.cpu().reshape(S, E), SER_dfe=r["ser"].cpu().reshape(S, E), shift_mmse=sh_m.cpu().numpy().reshape(S, E),
                shift_dfe=r["shift"].cpu().numpy().reshape(S, E), repairs=r["repairs"].cpu().numpy().reshape(S, E), C=r["C"], W=r["W"])
+    out.update(info)
     if verbose:
         for s in range(S):
             for e in range(E):
@@ -221,13 +236,14 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
 
 
 def main():
-    """The reference's sweep (:264-296) with the module's constants -> (SER_mmse, SER_dfe), each [num_snr, num_epochs] (CPU float32)."""
+    """The reference's sweep (:264-296) with the module's constants -> (SER_mmse, SER_dfe), each [num_snr, num_epochs] (CPU float32); with
+    info_metrics (SER_mmse, SER_dfe, info_mmse, info_dfe), the two dicts as run_dfe_batch's."""
     from .dp_runs import default_device
     device = default_device()
     print("We are using the following device for learning:", device)
     r = run_dfe_batch(SNR_vec, num_epochs, N_valid, mod, h_channel_orig, nu, seed=base_seed, generator=generator, device=device,
-                      verbose=True)
-    return r["SER_mmse"], r["SER_dfe"]
+                      verbose=True, want_info=info_metrics)
+    return (r["SER_mmse"], r["SER_dfe"], r["info_mmse"], r["info_dfe"]) if info_metrics else (r["SER_mmse"], r["SER_dfe"])
 
 
 if __name__ == "__main__":

@@ -20,7 +20,9 @@ epe = 2                 # epochs per evaluation
 
 savePATH = ""
 base_seed = None        # int -> reproducible runs; None = like the reference
+info_metrics = False    # True: the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), each shaped like SER
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
+INFO_KEYS = ("GMI", "NGMI", "AIR", "BER")
 
 
 def sweep_points():
@@ -35,15 +37,20 @@ def main():
 
     def run_batch(M, pts, seeds, device, seed):
         runs = [dict(SNR=p["SNR"], nu=p["nu"], lr_optim=p["lr"], seed=s) for p, s in zip(pts, seeds)]
-        return run_awgn_cma_batch(runs, mod, sps, M, N_valid, train_len, num_epochs, epe, channel, device=device, generator=generator, seed=seed)
+        r = run_awgn_cma_batch(runs, mod, sps, M, N_valid, train_len, num_epochs, epe, channel, device=device, generator=generator, seed=seed,
+                               want_info=info_metrics)
+        return sweep.info_rows(r, INFO_KEYS) if info_metrics else r               # per run: SER | GMI | NGMI | AIR | BER
 
+    n_eval = num_epochs // epe
     out = sweep.run_sharded(list(sweep_points()), lambda p: p["M"], run_batch, base_seed,
-                            (len(SNR_vec), 1, 1, len(M_vec), len(lr_optim_vec), 1, iter), (num_epochs // epe,))
+                            (len(SNR_vec), 1, 1, len(M_vec), len(lr_optim_vec), 1, iter),
+                            (1 + len(INFO_KEYS), n_eval) if info_metrics else (n_eval,))
     if out is None:
         return None
     nu = nu_vec[-1]
     name = f"{savePATH}SERvsSNR_CMA_shaping_{nu}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
     save_dict = {'SER': out[0].numpy(), 'SNR': SNR_vec, 'M': M_vec, 'lr': lr_optim_vec, 'nu': nu_vec}
+    save_dict.update({k: arr.numpy() for k, arr in zip(INFO_KEYS, out[1:])})
     io.savemat(name, {'dict': save_dict})
     return name, save_dict
 

@@ -777,3 +777,52 @@ def awgn_dfe(rx, ff_taps, fb_taps, init_dec, amp_levels, data=None, n_shift=24, 
                                   nat.ptr(dec, torch.int8), nat.ptr(ser), nat.ptr(shift, torch.int32), nat.ptr(repairs, torch.int32),
                                   nat.ptr(ff), nat.current_stream(dev)), "vaeq_awgn_dfe")
     return dict(dec=dec, ser=ser, shift=shift, repairs=repairs, ff=torch.view_as_complex(ff) if want_ff else None, C=C, W=W)
+
+
+def awgn_track_info(z, data, amp_levels, P, var, shift, edge=11):
+    """Information-rate figures of an AWGN baseline's soft sequence on the device (vaeq_awgn_track_info), over exactly the symbols its validator's
+    SER keeps (z[:, e+sh : -e] against data[:, e : -e-sh], sh = shift[r], e = edge: 11 for awgn_cma_validate, N_cut + 11 for the LMMSE and the DFE).
+    z: float [R,2,Nz] (planar: the CPE output of awgn_cma_validate) or complex [R,Nz] (the LMMSE output, Nz = Nd + 1, or awgn_dfe_soft's); the
+    layout follows from the dtype.  data[R,2,Nd] fp16, P[R,n] (or [n]) the per-axis pmf, var[R] (or a scalar) the demapper's variance
+    (10^(-SNR/10) in the host layers), shift[R] the validator's ->
+    dict(AIR[R], GMI[R], NGMI[R], BER[R] f32 (NaN where nothing is kept or z is zero); kept, sym_err, bit_err, hyp [R] int64).
+    AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
+    dev, R = z.device, z.shape[0]
+    amp = _amp(amp_levels, dev)
+    n = amp.numel()
+    interleaved = z.is_complex()
+    if interleaved:
+        z = torch.view_as_real(z.to(torch.complex64).contiguous())
+    Nz, Nd = (z.shape[1] if interleaved else z.shape[-1]), data.shape[-1]
+    if tuple(z.shape) != ((R, Nz, 2) if interleaved else (R, 2, Nz)) or tuple(data.shape) != (R, 2, Nd):
+        raise ValueError(f"expected z[R,2,Nz] float or z[R,Nz] complex and data[R,2,Nd], got {tuple(z.shape)}, {tuple(data.shape)}")
+    P = _pmf(P, R, n, dev)
+    var_t = _f32(var, dev).expand(R).contiguous()
+    z = z.float().contiguous()
+    data = _f16(data)
+    shift = _i32(shift, R, dev)
+    info = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(R, 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_awgn_track_info(R, Nz, Nd, n, int(edge), int(interleaved), nat.ptr(z), nat.ptr(data, torch.float16), nat.ptr(amp),
+                                                 nat.ptr(P), nat.ptr(var_t), nat.ptr(shift, torch.int32), nat.ptr(info),
+                                                 nat.ptr(counts, torch.int32), nat.current_stream(dev)), "vaeq_awgn_track_info")
+    return _info_dict(info, counts, P)
+
+
+def awgn_dfe_soft(ff, fb_taps, dec, amp_levels):
+    """The DFE's soft sequence (vaeq_awgn_dfe_soft): the slicer input of the reference's dfe() (DFE_MQAM_shaping.py:215-221), which keeps only the
+    hard decisions, rebuilt from awgn_dfe's ff[R,N] complex64 (want_ff) and dec[R,N] int8 and the feedback taps (as awgn_dfe takes them):
+    z[p] = ff[p] + sum_j fb[j] c(dec[p-1-j]) for p >= K2, c(dec[p]) in front -> z[R,N] complex64."""
+    dev, R, N = ff.device, ff.shape[0], ff.shape[-1]
+    if not ff.is_complex() or ff.dim() != 2 or tuple(dec.shape) != (R, N):
+        raise ValueError(f"ff must be complex [R,N] and dec [R,N], got {tuple(ff.shape)} {ff.dtype}, {tuple(dec.shape)}")
+    ff = torch.view_as_real(ff.to(torch.complex64).contiguous())
+    fb = _taps2(fb_taps, R, dev)
+    dec = dec.to(dev, torch.int8).contiguous()
+    amp = _amp(amp_levels, dev)
+    z = torch.empty(R, N, 2, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_awgn_dfe_soft(R, N, amp.numel(), fb.shape[-1], nat.ptr(ff), nat.ptr(fb), nat.ptr(dec, torch.int8), nat.ptr(amp),
+                                               nat.ptr(z), nat.current_stream(dev)), "vaeq_awgn_dfe_soft")
+    return torch.view_as_complex(z)

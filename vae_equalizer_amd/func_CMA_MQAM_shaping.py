@@ -7,9 +7,9 @@ are also the cross-check of the fused validation kernel (cma_validate_torch)."""
 import torch
 
 from . import channel as ch
-from .awgn_runs import check_generator, run_awgn_epochs
+from .awgn_runs import check_generator, first_run, run_awgn_epochs
 from .dp_runs import default_device, resolve_generator
-from .engine import awgn_cma, awgn_cma_validate
+from .engine import awgn_cma, awgn_cma_validate, awgn_track_info
 from .func_VAELE_MQAM_shaping import SER_symb, awgn_batch_tables, awgn_tables  # noqa: F401  (SER_symb: identical text in both reference modules)
 
 rcfir, rrcfir = ch.rcfir, ch.rrcfir
@@ -89,38 +89,48 @@ def cma_validate_torch(rx, h, data, amp_levels, sps=2, n_shift=N_SHIFT):
 
 
 def run_awgn_cma_batch(runs, mod, sps, M_est, N_valid, N_train, num_epochs, epe, channel, device=None, verbose=False, generator=None,
-                       seed=None):
+                       seed=None, want_info=False):
     """R AWGN constant-modulus runs at once: ``runs`` = list of dict(SNR, nu, lr_optim, seed).  Per epoch ONE training launch (every run's
     per-symbol chain on its own wave) and, on evaluated epochs, ONE fused validation launch (:213-232).
 
     generator: None    = "hip" when no run carries a seed (the reference seeds nothing), else "numpy" (dp_runs.resolve_generator);
                "numpy" = the reference-faithful host channel model per run (seeded like tools/capture_golden.py when the run has a seed);
                "hip"   = the on-device generator (vaeq_gen_awgn), Philox streams keyed by ``seed``, the draw counter and the run index.
-    Returns SER_valid[R, num_epochs // epe] (CPU float32)."""
+    Returns SER_valid[R, num_epochs // epe] (CPU float32); with want_info (SER_valid, info), info = dict(AIR, GMI, NGMI, BER f32; kept, sym_err,
+    bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: engine.awgn_track_info on the CPE output and the shift of every validation launch,
+    demapped at var = 10^(-SNR/10), the VAE-LE's of the same sweep point (func_VAELE_MQAM_shaping.py:272)."""
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
     generator = check_generator(resolve_generator(generator, any(r.get("seed") is not None for r in runs)))
-    _, gen_args, host, seeded = awgn_batch_tables(runs, mod, sps, channel)
+    tabs, gen_args, host, seeded = awgn_batch_tables(runs, mod, sps, channel)
     amp = torch.tensor(gen_args[0], dtype=torch.float32, device=device)
+    var = [t["var"] for t in tabs]
     h = torch.zeros(R, 2, M_est, dtype=torch.float32, device=device)
     h[:, 0, M_est // 2] = 1.0                                                    # :245-246
     lr = torch.tensor([r["lr_optim"] for r in runs], dtype=torch.float32, device=device)
 
     def validate(draw, N):                                                       # :222-232
         rxv, datav = draw(N)
-        ser, sh, _ = awgn_cma_validate(rxv, h, datav, amp, sps, N_SHIFT)
-        return ser, sh, None
+        ser, sh, yv = awgn_cma_validate(rxv, h, datav, amp, sps, N_SHIFT, want_cpe=want_info)
+        return ser, sh, awgn_track_info(yv, datav, amp, gen_args[1], var, sh, 11) if want_info else None
 
     return run_awgn_epochs(R, device, num_epochs, epe, N_train, N_valid, lambda rx: awgn_cma(rx, h, lr, sps, update=True)[0], validate,   # :218-220
-                           generator, seed, gen_args, host, seeded, verbose)
+                           generator, seed, gen_args, host, seeded, verbose, want_info)
 
 
 def processing(mod, sps, SNR, nu, M_est, lr_optim, N_valid, N_train, num_epochs, epe, channel, *, seed=None, device=None, verbose=True,
-               generator=None):
-    """One AWGN constant-modulus run -> SER_valid[num_epochs//epe] (CPU float32).  NB no ``batch_len``: the positional order differs from
+               generator=None, **options):
+    """One AWGN constant-modulus run -> SER_valid[num_epochs//epe] (CPU float32); with want_info=True (SER_valid, info), info as
+    run_awgn_cma_batch's per run.  The named keyword-only parameters are the pinned call surface of this drop-in (tests/test_awgn_cma_host.py);
+    what the reference has no word for arrives through ``options``: want_info (default False), keyword-only like them, anything else a TypeError.
+    NB no ``batch_len``: the positional order differs from
     func_VAELE_MQAM_shaping.processing (:201)."""
+    want_info = bool(options.pop("want_info", False))
+    if options:
+        raise TypeError(f"processing() got an unexpected keyword argument {sorted(options)[0]!r}")
     device = default_device() if device is None else torch.device(device)
     if verbose:
         print("We are using the following device for learning:", device)
-    return run_awgn_cma_batch([dict(SNR=SNR, nu=nu, lr_optim=lr_optim, seed=seed)], mod, sps, M_est, N_valid, N_train, num_epochs, epe,
-                              channel, device=device, verbose=verbose, generator=generator)[0]
+    out = run_awgn_cma_batch([dict(SNR=SNR, nu=nu, lr_optim=lr_optim, seed=seed)], mod, sps, M_est, N_valid, N_train, num_epochs, epe,
+                             channel, device=device, verbose=verbose, generator=generator, want_info=want_info)
+    return first_run(out, want_info)
