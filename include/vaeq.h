@@ -273,6 +273,28 @@ int vaeq_dp_epilogue_info(int32_t R, int64_t N, int32_t n_lev, int32_t batch_len
                           const float *amp, const float *P, const float *var, const float *nu_sc, const int32_t *shift,
                           const int32_t *rflag, float *info, int32_t *counts, void *stream);
 
+/* The per-bit a-posteriori LLRs of one DP frame: the input of a bit-wise (LDPC) decoder behind the equaliser, of which the GMI of
+ * vaeq_dp_epilogue_info is the rate.  Same sources, alignment and window as that call: exactly one of q[R][2][2*n_lev][N] and y[R][2][2][N]
+ * (var[R][2] and nu_sc[R] are required with y and may be NULL with q), amp[n_lev], shift[R][2] / rflag[R] = vaeq_dp_epilogue's path-0
+ * alignment, batch_len its per-minibatch cut.  hyp[R][2] = the hypothesis per run and polarisation, counts[..][3] of vaeq_dp_epilogue_info; it
+ * is used as hyp & 7 and only selects values, no address depends on it.
+ * For one symbol and one received axis c, with L[c][k][s] the log2 of the posterior mass of the levels i whose label bit k of
+ * g(i) = i ^ (i >> 1) is s (q-mode: log2 max(sum, FLT_MIN) of the set sums added in ascending i, so an exact 0 costs 126 bit and every LLR is
+ * finite; y-mode: a log-sum-exp of each set around its own maximum over the soft demapper's exponent, with the var of the RECEIVED row):
+ *   lam[c][k] = ln 2 (L[c][k][0] - L[c][k][1])                  nats, positive = bit 0, a-posteriori (the priors are in the posteriors)
+ * Hypothesis h = 4 flip + rot finds the transmitted axes: rot 0: I' = axis 0, Q' = axis 1; pi: both reversed; pi/2: I' = axis 1 reversed,
+ * Q' = axis 0; 3 pi/2: I' = axis 1, Q' = axis 0 reversed; the flip reverses Q' once more.  Reversing a level order flips the top label bit only
+ * (g(n-1-i) = g(i) ^ n/2): it negates plane k = b-1 of that axis and nothing else (b = log2 n_lev).
+ * llr[R][2][2 b][N] float32: plane a b + k of output polarisation p holds bit k of TX axis a (0 = I, 1 = Q), indexed by the TX symbol index n,
+ * so the planes line up with tx[R][2][2][N].  It reads sample n + clamp(shift[p], -10, 10) of row (p - r) & 1 and is kept iff the window of
+ * vaeq_dp_epilogue_info keeps n and that sample lies in [0, N); every other entry is an erasure, written as +0.0 (the buffer may be
+ * uninitialised).  Elementwise, no atomics: two calls give identical bits.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); both or neither of q and y is VAEQ_ERR_NULL, before any shape rule; then any other NULL
+ * pointer; R < 0, N < 43, N > 0x3fffffff, batch_len < 0, N % batch_len != 0 or n_lev not in {2, 4, 8} is VAEQ_ERR_SHAPE. */
+int vaeq_dp_epilogue_llr(int32_t R, int64_t N, int32_t n_lev, int32_t batch_len, const float *q, const float *y, const float *amp,
+                         const float *var, const float *nu_sc, const int32_t *shift, const int32_t *rflag, const int32_t *hyp, float *llr,
+                         void *stream);
+
 /* vaeq_awgn_validate for rows under its 64 symbols: the same arguments, results and kernel for 23 + n_shift / 2 <= N < 64 (every shift the
  * search can return, at most n_shift / 2, still keeps a symbol); any other N is VAEQ_ERR_SHAPE, every other refusal is vaeq_awgn_validate's.
  * The reference has no lower limit on the validation frame; vaeq_awgn_validate keeps its own. */
@@ -305,6 +327,21 @@ int vaeq_awgn_validate_short(int32_t R, int64_t N, int32_t sps, int32_t M, int32
  * N > 0x3fffffff or n_lev not in {2, 4, 8} is VAEQ_ERR_SHAPE. */
 int vaeq_awgn_info(int32_t R, int64_t N, int32_t n_lev, const float *q, const float *y, const void *data_f16, const float *amp, const float *P,
                    const float *amp_mean, const float *var, const int32_t *shift, float *info, int32_t *counts, void *stream);
+
+/* The per-bit a-posteriori LLRs of one AWGN validation frame, under the definition of vaeq_dp_epilogue_llr with the four rotation hypotheses of
+ * vaeq_awgn_info (hyp[R] = its counts[..][3], used as hyp & 3; no IQ flip) and that call's sources and window: exactly one of q[R][2*n_lev][N]
+ * and y[R][2][N] (amp_mean[R] and var[R] are required with y and may be NULL with q), amp[n_lev], shift[R].  For shift[r] = sh the TX index
+ * 11 + j, j < len = N - 22 - sh, reads the posterior (or sample) 11 + sh + j; the window is empty when 11 + sh <= 0 or len <= 0 (64-bit: no
+ * int32 shift takes an index out of [0, N)).  y-mode posteriors are vaeq_awgn_info's: yhat_c = y_c (amp_mean / m_c), m_c = (sum_{n < N}
+ * |y_c[n]|) / N over the WHOLE row, summed in that kernel's order so that the LLRs are those of the posteriors whose GMI it reports;
+ * z_i = -(yhat_c - a_i)^2 / var, each bit-wise set a log-sum-exp around its own maximum.
+ * llr[R][2 b][N] float32: plane a b + k holds bit k of TX axis a, indexed by the TX symbol index; everything outside [11, 11 + len) is an
+ * erasure, written as +0.0, and an empty window or a component with m_c == 0 writes the whole row as zeros (the buffer may be uninitialised).
+ * One workgroup per run; no atomics: two calls give identical bits.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); both or neither of q and y is VAEQ_ERR_NULL, before any shape rule; then any other NULL
+ * pointer; R < 0, N < 1, N > 0x3fffffff or n_lev not in {2, 4, 8} is VAEQ_ERR_SHAPE. */
+int vaeq_awgn_llr(int32_t R, int64_t N, int32_t n_lev, const float *q, const float *y, const float *amp, const float *amp_mean,
+                  const float *var, const int32_t *shift, const int32_t *hyp, float *llr, void *stream);
 
 /* The two-stage epilogue of the constant-modulus baselines in one launch (optical_DP_channel/func_CMA_DP_MQAM_shaping.py:39-52 after the phase
  * estimation; the CMAbatch / CMAflex modules are identical there): the constellation stage FIRST (find_shift_symb_full on y, roll / cut,

@@ -15,7 +15,7 @@ import torch
 
 from . import channel as ch
 from . import shared_funcs as sfun
-from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info  # noqa: F401
+from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info, dp_epilogue_llr, label_bits  # noqa: F401
 
 
 @dataclass
@@ -108,7 +108,8 @@ def default_device():
 
 
 def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex_step, channel, tau_cd, tau_pmd, phiIQ,
-                 N_lrhalf, flex=False, device=None, generator=None, verbose=False, threads=0, keep_last=False, want_info=False):
+                 N_lrhalf, flex=False, device=None, generator=None, verbose=False, threads=0, keep_last=False, want_info=False,
+                 want_llr=False):
     """Train + evaluate R runs.  Returns dict(SER[R,4,num_frames], Var_est[R,2,num_frames], var[R,2]) on the CPU.
 
     generator: None    = "hip" when no run carries a seed, "numpy" otherwise (resolve_generator);
@@ -118,6 +119,10 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
     want_info: also dict(AIR, GMI, NGMI, BER [R,2,num_frames] f32; kept, sym_err, bit_err, hyp [R,2,num_frames] int64) under "info":
                engine.dp_epilogue_info after every frame's epilogue, on its soft-demapper alignment -- from y on the compact path, from q in
                a frame whose q is materialised (keep_last).  Every other output is the same with and without it.
+    want_llr:  also dict(llr[R,2,2b,N_out] f32, bits[R,2,2b,N_out] int8, hyp[R,2]) under "llr", on the device, for the LAST frame only (a whole
+               sweep's LLRs would be tens of GB): engine.dp_epilogue_llr on that frame's soft-demapper alignment under the winning hypothesis
+               of one dp_epilogue_info call (want_info's, when that is on) -- from q when the frame's q is materialised, from y otherwise --
+               and engine.label_bits of the frame's TX reference.  Every other output is the same with and without it.
     """
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
@@ -160,8 +165,9 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
     SER = torch.empty(R, 4, num_frames, dtype=torch.float32, device=device)
     Var_est = torch.empty(R, 2, num_frames, dtype=torch.float32, device=device)
     INFO = None
-    if want_info:
+    if want_info or want_llr:
         P_t = torch.tensor(P, dtype=torch.float32, device=device)
+    if want_info:
         INFO = {k: torch.empty(R, 2, num_frames, dtype=torch.float32 if k in INFO_FLOAT else torch.int64, device=device)
                 for k in INFO_FLOAT + INFO_INT}
     last = None
@@ -209,15 +215,21 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
         Var_est[:, :, frame] = ve.mean(dim=2)                                   # :69
         res = dp_epilogue_compact(out["eq"][:, 0], out["dec"][:, 0], out["y"][:, 0], data, amp, nu_sc_t, var, None if flex else batch_len)
         SER[:, :, frame] = res["SER"]
-        if want_info:
+        need_llr = want_llr and frame == num_frames - 1
+        if want_info or need_llr:
             bl = None if flex else batch_len
             if out.get("q") is not None:
                 fig = dp_epilogue_info(q=out["q"][:, 0], data=data, amp_levels=amp, P=P_t, shift=res["shift_q"], r=res["r_q"], batch_len=bl)
             else:
                 fig = dp_epilogue_info(y=out["y"][:, 0], data=data, amp_levels=amp, P=P_t, nu_sc=nu_sc_t, var=var, shift=res["shift_q"],
                                        r=res["r_q"], batch_len=bl)
-            for k in INFO:
-                INFO[k][:, :, frame] = fig[k]
+            if want_info:
+                for k in INFO:
+                    INFO[k][:, :, frame] = fig[k]
+            if need_llr:                                                        # the same source, alignment and window as fig, under its hypothesis
+                src = dict(q=out["q"][:, 0]) if out.get("q") is not None else dict(y=out["y"][:, 0], nu_sc=nu_sc_t, var=var)
+                state["llr"] = dict(llr=dp_epilogue_llr(amp_levels=amp, shift=res["shift_q"], r=res["r_q"], hyp=fig["hyp"], batch_len=bl, **src),
+                                    bits=label_bits(data, n_lev), hyp=fig["hyp"])
         return res, ve
 
     # Small batches (fewer runs than the device keeps resident: the script-faithful sweeps, 15 ... 300 runs) leave most of the chip idle
@@ -257,6 +269,8 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
                 finish_frame(frame, out, data)
         main.wait_stream(s_epi)
         main.wait_stream(s_gen)
+        for t in state.get("llr", {}).values():                                 # made on s_epi, used by the caller on main from here on
+            t.record_stream(main)
     else:
         for frame in range(num_frames):
             rx, data = make_frame(frame)
@@ -278,6 +292,8 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
     ret = dict(SER=SER.cpu(), Var_est=Var_est.cpu(), var=torch.tensor(var_np), engine=eng)
     if INFO is not None:
         ret["info"] = {k: v.cpu() for k, v in INFO.items()}
+    if "llr" in state:
+        ret["llr"] = state["llr"]
     if last is not None:
         ret["last"] = last
     return ret

@@ -336,6 +336,11 @@ class AWGNEngine:
         y[R,2,N], data[R,2,N] f16 and shift[R], demapped with the engine's P, amp_mean and var."""
         return awgn_info(y=y, data=data, amp_levels=self.amp, P=self.P, amp_mean=self.amp_mean, var=self.var, shift=shift)
 
+    def llr(self, y, shift, hyp):
+        """Per-bit LLRs of a validation frame (awgn_llr, y-mode) [R,2b,N]: y[R,2,N] and shift[R] from validate / validate_clean, hyp[R] from info on
+        them, demapped with the engine's amp_mean and var -- the posteriors whose GMI info reports."""
+        return awgn_llr(y=y, amp_levels=self.amp, amp_mean=self.amp_mean, var=self.var, shift=shift, hyp=hyp)
+
 
 class NNEngine:
     """R independent AWGN VAE-NN runs (AWGN_channel/func_VAENN_MQAM.py): flat per-run parameter vectors
@@ -458,6 +463,27 @@ class NNEngine:
             parts.append(awgn_info(q=q, data=data[s:e], amp_levels=self.amp, P=P[s:e], shift=shift[s:e]))
         return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
 
+    def llr(self, x, shift, hyp):
+        """Per-bit LLRs of a validation frame (awgn_llr, q-mode on the eval forward's posteriors) [R,2b,N]: x[R,2,N*sps], shift[R] = validate's,
+        hyp[R] = info's.  The posteriors are formed and consumed in chunks of runs of at most 1 GiB each, as in info."""
+        R, N = x.shape[0], x.shape[-1] // self.sps
+        if R != self.R or x.dim() != 3 or x.shape[1] != 2:
+            raise ValueError(f"x must be [R={self.R}, 2, N*sps], got {tuple(x.shape)}")
+        n = self.n_lev
+        x = x.contiguous()
+        shift, hyp = _i32(shift, R, self.device), _i32(hyp, R, self.device)
+        chunk = max(1, (1 << 30) // (2 * n * N * 4))
+        parts = []
+        for s in range(0, R, chunk):
+            e = min(R, s + chunk)
+            q = torch.empty(e - s, 2 * n, N, dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                nat.check(nat.lib().vaeq_nn_forward(e - s, N, self.sps, self.M, n, self.k1, self.k2, nat.ptr(x[s:e]), nat.ptr(self.theta[s:e]),
+                                                    None if self.bn is None else nat.ptr(self.bn[s:e]), nat.ptr(q),
+                                                    nat.current_stream(self.device)), "vaeq_nn_forward")
+            parts.append(awgn_llr(q=q, amp_levels=self.amp, shift=shift[s:e], hyp=hyp[s:e]))
+        return torch.cat(parts)
+
 
 def dp_epilogue(q, y, data, amp_levels, nu_sc, var, batch_len=None):
     """Per-frame epilogue on the device (vaeq_dp_epilogue): q[R,2,2n,N], y[R,2,2,N], data[R,2,2,N] fp16 ->
@@ -555,6 +581,74 @@ def awgn_info(q=None, y=None, data=None, amp_levels=None, P=None, amp_mean=None,
                                            nat.ptr(shift, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32), nat.current_stream(dev)),
                   "vaeq_awgn_info")
     return _info_dict(info, counts, P)
+
+
+def dp_epilogue_llr(q=None, y=None, amp_levels=None, nu_sc=None, var=None, shift=None, r=None, hyp=None, batch_len=None):
+    """Per-bit a-posteriori LLRs of one frame on the device (vaeq_dp_epilogue_llr), the input of a bit-wise decoder: exactly one of q[R,2,2n,N] and
+    y[R,2,2,N] (y: the soft demapper's posteriors are recomputed from var / nu_sc, in the log domain), shift[R,2] / r[R] = dp_epilogue's shift_q /
+    r_q, hyp[R,2] = dp_epilogue_info's hyp on the same alignment -> llr[R,2,2b,N] f32 in nats, positive = bit 0, b = log2 n: plane a b + k of
+    polarisation p at TX index n is bit k (b-1 = the top bit of the Gray label i ^ (i >> 1)) of TX axis a (0 = I, 1 = Q), aligned with
+    label_bits(data, n); the symbols dp_epilogue_info does not keep are erasures, +0.0."""
+    if (q is None) == (y is None):
+        raise ValueError("dp_epilogue_llr takes exactly one of q and y")
+    src = q if y is None else y
+    dev, R, N = src.device, src.shape[0], src.shape[-1]
+    amp = _amp(amp_levels, dev)
+    n = amp.numel()
+    if tuple(src.shape) != (R, 2, 2 * n if y is None else 2, N):
+        raise ValueError(f"expected q[R,2,{2 * n},N] or y[R,2,2,N], got {tuple(src.shape)}")
+    var_t = nu_t = None
+    if y is not None:
+        var_t, nu_t = _var_nu(var, nu_sc, R, dev)
+    src = src.contiguous()
+    shift, r, hyp = _i32(shift, (R, 2), dev), _i32(r, R, dev), _i32(hyp, (R, 2), dev)
+    llr = torch.empty(R, 2, 2 * (n.bit_length() - 1), N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_dp_epilogue_llr(R, N, n, int(batch_len or 0), nat.ptr(src if y is None else None), nat.ptr(src if y is not None else None),
+                                                 nat.ptr(amp), nat.ptr(var_t), nat.ptr(nu_t), nat.ptr(shift, torch.int32), nat.ptr(r, torch.int32),
+                                                 nat.ptr(hyp, torch.int32), nat.ptr(llr), nat.current_stream(dev)), "vaeq_dp_epilogue_llr")
+    return llr
+
+
+def awgn_llr(q=None, y=None, amp_levels=None, amp_mean=None, var=None, shift=None, hyp=None):
+    """Per-bit a-posteriori LLRs of an AWGN validation frame on the device (vaeq_awgn_llr): exactly one of q[R,2n,N] (stored posteriors) and
+    y[R,2,N] (the validation's un-normalised output; the VAE-LE demapper's posteriors are recomputed from amp_mean[R] / var[R] as awgn_info
+    does), shift[R], hyp[R] = awgn_info's hyp on the same shift -> llr[R,2b,N] f32 in nats, positive = bit 0: plane a b + k at TX index n is bit
+    k of TX axis a, aligned with label_bits(data, n); everything outside TX indices [11, N - 11 - shift) is an erasure, +0.0."""
+    if (q is None) == (y is None):
+        raise ValueError("awgn_llr takes exactly one of q and y")
+    src = q if y is None else y
+    dev, R, N = src.device, src.shape[0], src.shape[-1]
+    amp = _amp(amp_levels, dev)
+    n = amp.numel()
+    if tuple(src.shape) != (R, 2 * n if y is None else 2, N):
+        raise ValueError(f"expected q[R,{2 * n},N] or y[R,2,N], got {tuple(src.shape)}")
+    am_t = var_t = None
+    if y is not None:
+        am_t = _f32(amp_mean, dev).expand(R).contiguous()
+        var_t = _f32(var, dev).expand(R).contiguous()
+    src = src.contiguous()
+    shift, hyp = _i32(shift, R, dev), _i32(hyp, R, dev)
+    llr = torch.empty(R, 2 * (n.bit_length() - 1), N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_awgn_llr(R, N, n, nat.ptr(src if y is None else None), nat.ptr(src if y is not None else None), nat.ptr(amp),
+                                          nat.ptr(am_t), nat.ptr(var_t), nat.ptr(shift, torch.int32), nat.ptr(hyp, torch.int32), nat.ptr(llr),
+                                          nat.current_stream(dev)), "vaeq_awgn_llr")
+    return llr
+
+
+def label_bits(data, n_lev):
+    """The transmitted label bits in the plane order of dp_epilogue_llr / awgn_llr: data[..., 2, N] (the TX reference, axis 0 = I, 1 = Q) ->
+    int8[..., 2b, N], plane a b + k = bit k of the Gray label t ^ (t >> 1) of the level t = clamp(rint((n-1)/2 data + (n-1)/2), 0, n-1) of
+    axis a.  Plain torch ops, on the device data lives on."""
+    n = int(n_lev)
+    b = n.bit_length() - 1
+    scale = 0.5 * (n - 1)
+    t = torch.clamp(torch.round(scale * data.to(torch.float16).to(torch.float32) + scale), 0, n - 1).to(torch.int32)
+    g = t ^ (t >> 1)
+    k = torch.arange(b, dtype=torch.int32, device=data.device)
+    bits = (g.unsqueeze(-2) >> k.unsqueeze(-1)) & 1                              # [..., 2, b, N]
+    return bits.reshape(*data.shape[:-2], 2 * b, data.shape[-1]).to(torch.int8)
 
 
 def cma_epilogue(y, data, amp_levels, nu_sc, var):
