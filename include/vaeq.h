@@ -374,6 +374,24 @@ int vaeq_cma_epilogue_info(int32_t R, int64_t N, int32_t n_lev, const float *y, 
                            const float *var, const float *nu_sc, const int32_t *shift_c, const int32_t *r_c, const int32_t *shift_q,
                            const int32_t *r_q, float *info, int32_t *counts, void *stream);
 
+/* The per-bit a-posteriori LLRs of one frame of the constant-modulus baselines, under the definition of vaeq_dp_epilogue_llr (lam, hypotheses,
+ * plane order) with the posteriors of vaeq_cma_epilogue_info, term for term: y[R][2][2][N], tx_f16[R][2][2][N] (needed for fac only), amp[n_lev],
+ * var[R][2], nu_sc[R], shift_c[R][2], r_c[R], shift_q[R][2], r_q[R] are what that call got; hyp[R][2] = its counts[..][3], used as hyp & 7 (it
+ * selects values only, no address depends on it).  Both shifts are clamped to +-10, ya wraps around the frame, fac is summed over W_c and both
+ * polarisations in that kernel's order (per thread at stride 256, over the wave's lanes, over the four waves in order) so that the LLRs are those
+ * of the posteriors whose GMI it reports, a sample is scaled by fac exactly where its stage-c index lies in W_c, and output polarisation p is
+ * demapped with var of the stage-c aligned row (p - r_q) & 1, each bit-wise set a log-sum-exp around its own maximum.
+ * llr[R][2][2 b][N] float32, nats, positive = bit 0: plane a b + k of output polarisation p holds bit k of TX axis a (0 = I, 1 = Q), indexed by the
+ * TX symbol index n, so the planes line up with tx[R][2][2][N].  Kept are n in [11, N - 11 - max|shift_q|); every other entry is an erasure,
+ * written as +0.0, and a run whose sum of |ya| over W_c is zero writes all zeros (the buffer may be uninitialised: every entry is written).
+ * One workgroup per run, or per (run, polarisation) for R <= 512, each forming fac for itself; no atomics: two calls give identical bits, R runs
+ * in one call the bits of R single calls on either grid.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); any NULL pointer is VAEQ_ERR_NULL, before any shape rule; R < 0, N < 43, N > 0x3fffffff or n_lev
+ * not in {2, 4, 8} is VAEQ_ERR_SHAPE. */
+int vaeq_cma_epilogue_llr(int32_t R, int64_t N, int32_t n_lev, const float *y, const void *tx_f16, const float *amp, const float *var,
+                          const float *nu_sc, const int32_t *shift_c, const int32_t *r_c, const int32_t *shift_q, const int32_t *r_q,
+                          const int32_t *hyp, float *llr, void *stream);
+
 /* ------------------------------------------------------------------------
  * Seeded on-device DP channel simulator (input producer): optical_DP_channel/shared_funcs.py:65-90 in three stages with
  * the FFT / inverse FFT over Ls done by the caller (hipFFT through torch.fft) between them.  Counter-based RNG (Philox4x32-10):
@@ -594,6 +612,22 @@ int64_t vaeq_awgn_dfe_ws_bytes(int32_t R, int64_t N, int32_t C);
 int vaeq_awgn_track_info(int32_t R, int64_t Nz, int64_t Nd, int32_t n_lev, int32_t edge, int32_t interleaved, const float *z,
                          const void *data_f16, const float *amp, const float *P, const float *var, const int32_t *shift, float *info,
                          int32_t *counts, void *stream);
+
+/* The per-bit a-posteriori LLRs of an AWGN baseline's soft sequence, under the definition of vaeq_dp_epilogue_llr with the four rotation hypotheses
+ * of vaeq_awgn_track_info (hyp[R] = its counts[..][3], used as hyp & 3; no IQ flip) and that call's window, layouts, normalisation and demapper:
+ * z planar [R][2][Nz] (interleaved = 0) or [R][Nz][2] (interleaved = 1), data_f16[R][2][Nd] (needed for the normalisation only), amp[n_lev], var[R],
+ * shift[R] unclamped, the window in 64 bits.  scale = (sum_{j<L} |tx_j| / L) / (sum_{m<Lz} |z[e+sh+m]| / Lz) over ALL Lz samples of the slice, summed
+ * in that kernel's order so that the LLRs are those of the posteriors whose GMI it reports; v_i = -(zhat_c - a_i)^2 / var, each bit-wise set a
+ * log-sum-exp around its own maximum.
+ * llr[R][2 b][Nd] float32, nats, positive = bit 0: plane a b + k holds bit k of TX axis a, indexed by the TX symbol index; TX index e + j, j < L,
+ * holds the LLRs of sample e + sh + j.  Everything else is an erasure, written as +0.0, and an empty window or a slice whose sum of |z| is zero
+ * writes the whole row as zeros (the buffer may be uninitialised: every entry is written).
+ * One 256-thread workgroup per run, a pre-pass and one elementwise pass; no atomics: two calls give identical bits.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); any NULL pointer is VAEQ_ERR_NULL, before any shape rule; R < 0, Nd < 1, Nz not in {Nd, Nd + 1},
+ * Nz > 0x3fffffff, edge < 0, interleaved not in {0, 1} or n_lev not in {2, 4, 8} is VAEQ_ERR_SHAPE. */
+int vaeq_awgn_track_llr(int32_t R, int64_t Nz, int64_t Nd, int32_t n_lev, int32_t edge, int32_t interleaved, const float *z,
+                        const void *data_f16, const float *amp, const float *var, const int32_t *shift, const int32_t *hyp, float *llr,
+                        void *stream);
 
 /* The DFE's soft sequence.  The reference's dfe() leaves only hard decisions; its soft value is the slicer input (DFE_MQAM_shaping.py:215-221),
  * rebuilt here from what vaeq_awgn_dfe returns: ff[R][N] complex64 (ff_out), fb[R][2][K2] (re, im; the feedback taps), dec[R][N] int8, amp[n_lev]

@@ -181,7 +181,7 @@ def _filters(h, SNR):
 
 
 def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.0270955, *, seed=None, generator=None, device=None,
-                  verbose=False, C=None, W=None, want_info=False):
+                  verbose=False, C=None, W=None, want_info=False, want_llr=False):
     """The script's loop nest (:264-296) for a channel (h_orig: symbol-spaced taps, default h_1) and a modulation, all frames at once:
     R = len(SNRs) * num_epochs frames, one generator call, ONE LMMSE evaluation launch and ONE DFE launch.
 
@@ -190,9 +190,15 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
     Returns dict(SER_mmse [num_snr, num_epochs], SER_dfe (CPU float32), shift_mmse, shift_dfe, repairs (numpy), C, W); with want_info also
     info_mmse and info_dfe, each dict(AIR, GMI, NGMI, BER f32; kept, sym_err, bit_err, hyp int64) of [num_snr, num_epochs] CPU tensors:
     engine.awgn_track_info at edge N_cut + 11 on the LMMSE output (one sample longer than the data) at shift_mmse and on the DFE's slicer input
-    (engine.awgn_dfe_soft) at shift_dfe, demapped at var = 10^(-SNR/10), the VAE-LE's of the same SNR (func_VAELE_MQAM_shaping.py:272)."""
+    (engine.awgn_dfe_soft) at shift_dfe, demapped at var = 10^(-SNR/10), the VAE-LE's of the same SNR (func_VAELE_MQAM_shaping.py:272).
+    With want_llr also llr_mmse and llr_dfe, each dict(llr[num_snr, num_epochs, 2b, N_valid] f32, bits[num_snr, num_epochs, 2b, N_valid] int8,
+    hyp[num_snr, num_epochs]) ON THE DEVICE: engine.awgn_track_llr on the same two tracks, shifts, edge and var under the hypothesis of
+    awgn_track_info on them (want_info's call, when that is on), and engine.label_bits of the TX data.  All frames go through one launch, so
+    all of them are returned; the two dicts share one bits tensor: num_snr x num_epochs x 2b x N_valid x (2 x 4 + 1) bytes (64-QAM, 15 SNRs x
+    10 epochs x 10 000 symbols: 81 MB).
+    Every other output is the same with and without it."""
     from .dp_runs import default_device, fresh_seed, resolve_generator
-    from .engine import awgn_dfe, awgn_dfe_soft, awgn_lmmse_eval, awgn_track_info
+    from .engine import awgn_dfe, awgn_dfe_soft, awgn_lmmse_eval, awgn_track_info, awgn_track_llr, label_bits
     device = default_device() if device is None else torch.device(device)
     h = channel_taps(CHANNELS["h1"] if h_orig is None else np.asarray(h_orig), sps)
     q = qam_constants(mod)
@@ -216,15 +222,21 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
                                              fresh_seed() if seed is None else seed, 0)
     else:
         raise ValueError(f"unknown generator {generator!r}")
-    ser_m, sh_m, dec_m, out_m = awgn_lmmse_eval(rx, lm, data, amps, N_SHIFT_LMMSE, N_cut, want_out=want_info)
-    r = awgn_dfe(rx, ff, fb, dec_m, amps, data, N_SHIFT_DFE, N_cut, C=C, W=W, want_ff=want_info)
+    ser_m, sh_m, dec_m, out_m = awgn_lmmse_eval(rx, lm, data, amps, N_SHIFT_LMMSE, N_cut, want_out=want_info or want_llr)
+    r = awgn_dfe(rx, ff, fb, dec_m, amps, data, N_SHIFT_DFE, N_cut, C=C, W=W, want_ff=want_info or want_llr)
     info = {}
-    if want_info:
+    if want_info or want_llr:
         P = ch.pcs_probabilities(amps, nu)
         var = [10 ** (-SNRs[k // E] / 10) for k in range(R)]
         on_grid = lambda d: {k: v.cpu().reshape(S, E) for k, v in d.items()}  # noqa: E731
-        info["info_mmse"] = on_grid(awgn_track_info(out_m, data, amps, P, var, sh_m, N_cut + 11))
-        info["info_dfe"] = on_grid(awgn_track_info(awgn_dfe_soft(r["ff"], fb, r["dec"], amps), data, amps, P, var, r["shift"], N_cut + 11))
+        bits = label_bits(data, len(amps)).reshape(S, E, -1, data.shape[-1]) if want_llr else None
+        for key, z, sh in (("mmse", out_m, sh_m), ("dfe", awgn_dfe_soft(r["ff"], fb, r["dec"], amps), r["shift"])):
+            fig = awgn_track_info(z, data, amps, P, var, sh, N_cut + 11)
+            if want_info:
+                info["info_" + key] = on_grid(fig)
+            if want_llr:                                                        # the same track, shift, edge and var as fig, under its hypothesis
+                llr = awgn_track_llr(z, data, amps, var, sh, fig["hyp"], N_cut + 11)
+                info["llr_" + key] = dict(llr=llr.reshape(S, E, *llr.shape[1:]), bits=bits, hyp=fig["hyp"].reshape(S, E))
     out = dict(SER_mmse=ser_m.cpu().reshape(S, E), SER_dfe=r["ser"].cpu().reshape(S, E), shift_mmse=sh_m.cpu().numpy().reshape(S, E),
                shift_dfe=r["shift"].cpu().numpy().reshape(S, E), repairs=r["repairs"].cpu().numpy().reshape(S, E), C=r["C"], W=r["W"])
     out.update(info)

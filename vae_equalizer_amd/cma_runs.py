@@ -20,16 +20,24 @@ from .engine import cma, cpe, soft_demap
 N_CUT = 10   # symbols cut at both frame ends before the phase estimation (func_CMA_DP_MQAM_shaping.py:26,39)
 
 
-def cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=None):
+def cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=None, want_llr=False):
     """out_const[R,2,2,K] (CMA output of one frame), data[R,2,2,K] fp16 -> dict(SER[R,4], shift_c, r_c, shift_q, r_q): phase estimation
     (vaeq_cpe) + the two-stage epilogue in one HIP launch (vaeq_cma_epilogue; q is never materialised).  P[R,n] (the runs' per-axis pmf): also
-    "info" = engine.cma_epilogue_info on the same y and the alignment just found (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp, each [R,2])."""
-    from .engine import cma_epilogue, cma_epilogue_info
+    "info" = engine.cma_epilogue_info on the same y and the alignment just found (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp, each [R,2]).
+    want_llr (needs P): also "llr" = dict(llr[R,2,2b,K-20] f32, bits[R,2,2b,K-20] int8, hyp[R,2]) on the device: engine.cma_epilogue_llr on the
+    same y and alignment under that info call's hypothesis, and engine.label_bits of the cut TX reference."""
+    from .engine import cma_epilogue, cma_epilogue_info, cma_epilogue_llr, label_bits
     y = cpe(out_const[..., N_CUT:-N_CUT].contiguous())                          # :39
     d = data[..., N_CUT:-N_CUT]
     res = cma_epilogue(y, d, amp, nu_sc, var)                                   # :40-52
     if P is not None:
         res["info"] = cma_epilogue_info(y, d, amp, P, nu_sc, var, res["shift_c"], res["r_c"], res["shift_q"], res["r_q"])
+    if want_llr:
+        if P is None:
+            raise ValueError("want_llr needs P: the hypothesis is cma_epilogue_info's")
+        hyp = res["info"]["hyp"]
+        res["llr"] = dict(llr=cma_epilogue_llr(y, d, amp, nu_sc, var, res["shift_c"], res["r_c"], res["shift_q"], res["r_q"], hyp),
+                          bits=label_bits(d, amp.numel()), hyp=hyp)
     return res
 
 
@@ -57,11 +65,15 @@ def cma_frame_epilogue_torch(out_const, data, amp, nu_sc, var):
 
 
 def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frames, flex_step, channel, tau_cd, tau_pmd, phiIQ, N_lrhalf,
-                  device=None, generator=None, verbose=False, want_info=False):
+                  device=None, generator=None, verbose=False, want_info=False, want_llr=False):
     """R baseline runs (list of dp_runs.DPRun; lr_optim = the CMA step size) -> dict(SER[R,4,num_frames], Var_est[R,2,num_frames] (zeros,
     like the reference), var[R,2], h).  mode: "CMA" | "CMAbatch" | "CMAflex".
     want_info: also dict(AIR, GMI, NGMI, BER [R,2,num_frames] f32; kept, sym_err, bit_err, hyp [R,2,num_frames] int64) under "info", on the CPU
-               like run_dp_batch's: engine.cma_epilogue_info after every frame's epilogue, on the runs' PCS pmf rows."""
+               like run_dp_batch's: engine.cma_epilogue_info after every frame's epilogue, on the runs' PCS pmf rows.
+    want_llr:  also dict(llr[R,2,2b,N'] f32, bits[R,2,2b,N'] int8, hyp[R,2]) under "llr", on the device, for the LAST frame only, like
+               run_dp_batch's (N' = N_train_max - 20, the [10:-10] cut the epilogue gets): engine.cma_epilogue_llr on that frame's alignment
+               under the winning hypothesis of one cma_epilogue_info call (want_info's, when that is on), and engine.label_bits of the cut TX
+               reference.  Every other output is the same with and without it."""
     if mode not in ("CMA", "CMAbatch", "CMAflex"):
         raise ValueError(f"unknown CMA variant {mode!r}")
     device = default_device() if device is None else torch.device(device)
@@ -83,9 +95,10 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
     streams = [ch.SeededStreams(r.seed) if r.seed is not None else None for r in runs]
     SER = torch.empty(R, 4, num_frames, dtype=torch.float32, device=device)
     P = np.stack([t["P"] for t in tabs])
-    P_t = INFO = None
-    if want_info:
+    P_t = INFO = LLR = None
+    if want_info or want_llr:
         P_t = torch.tensor(P, dtype=torch.float32, device=device)
+    if want_info:
         INFO = {k: torch.empty(R, 2, num_frames, dtype=torch.float32 if k in INFO_FLOAT else torch.int64, device=device)
                 for k in INFO_FLOAT + INFO_INT}
     check_one_symb_rate(runs, generator)
@@ -109,8 +122,14 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
             raise ValueError(f"unknown generator {generator!r}")
         theta = theta + theta_diff
         out_const, e = cma(rx, h, lr.astype(np.float32), sps, mode, batch_len, flex_step, 1.0, want_e=verbose)
-        res = cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=P_t)
+        need_llr = want_llr and frame == num_frames - 1
+        if need_llr:
+            res = cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=P_t, want_llr=True)
+        else:
+            res = cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=P_t if want_info else None)
         SER[:, :, frame] = res["SER"]
+        if need_llr:
+            LLR = res["llr"]
         if want_info:
             for k in INFO:
                 INFO[k][:, :, frame] = res["info"][k]
@@ -125,6 +144,8 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
     ret = dict(SER=SER.cpu(), Var_est=torch.zeros(R, 2, num_frames), var=torch.tensor(var_np), h=h)
     if INFO is not None:
         ret["info"] = {k: v.cpu() for k, v in INFO.items()}
+    if LLR is not None:
+        ret["llr"] = LLR
     return ret
 
 

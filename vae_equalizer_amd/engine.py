@@ -696,6 +696,31 @@ def cma_epilogue_info(y, data, amp_levels, P, nu_sc, var, shift_c, r_c, shift_q,
     return _info_dict(info, counts, P)
 
 
+def cma_epilogue_llr(y, data, amp_levels, nu_sc, var, shift_c, r_c, shift_q, r_q, hyp):
+    """Per-bit a-posteriori LLRs of one frame of the constant-modulus baselines on the device (vaeq_cma_epilogue_llr), the input of a bit-wise
+    decoder: y[R,2,2,N], data[R,2,2,N] fp16 (needed for the mean-radius factor only), nu_sc, var and the four alignment outputs as
+    cma_epilogue_info got them, hyp[R,2] = that call's hyp -> llr[R,2,2b,N] f32 in nats, positive = bit 0, b = log2 n: plane a b + k of output
+    polarisation p at TX index n is bit k of TX axis a, aligned with label_bits(data, n).  The posteriors are cma_epilogue_info's; the symbols
+    it does not keep are erasures, +0.0, and a run without a normalisation is all zeros."""
+    dev, R, N = y.device, y.shape[0], y.shape[-1]
+    amp = _amp(amp_levels, dev)
+    n = amp.numel()
+    if tuple(y.shape) != (R, 2, 2, N) or tuple(data.shape) != (R, 2, 2, N):
+        raise ValueError(f"expected y[R,2,2,N] and data[R,2,2,N], got {tuple(y.shape)}, {tuple(data.shape)}")
+    var_t, nu_t = _var_nu(var, nu_sc, R, dev)
+    y = y.contiguous()
+    data = _f16(data)
+    sc, rc, sq, rq = _i32(shift_c, (R, 2), dev), _i32(r_c, R, dev), _i32(shift_q, (R, 2), dev), _i32(r_q, R, dev)
+    hyp = _i32(hyp, (R, 2), dev)
+    llr = torch.empty(R, 2, 2 * (n.bit_length() - 1), N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_cma_epilogue_llr(R, N, n, nat.ptr(y), nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(var_t), nat.ptr(nu_t),
+                                                  nat.ptr(sc, torch.int32), nat.ptr(rc, torch.int32), nat.ptr(sq, torch.int32),
+                                                  nat.ptr(rq, torch.int32), nat.ptr(hyp, torch.int32), nat.ptr(llr), nat.current_stream(dev)),
+                  "vaeq_cma_epilogue_llr")
+    return llr
+
+
 def awgn_loss(q, x, h, amp_levels, P=None):
     """ELBO of the single-polarisation variants for a given q (vaeq_awgn_loss): q[R,2n,B] (or [2n,B]), x[R,2,B*sps], h[R,2,M];
     P[R,n] / [n] -> the VAE-LE form (KL to the prior), P None -> the VAE-NN form (entropy).  Returns loss[R] (or a 0-dim tensor)."""
@@ -902,6 +927,33 @@ def awgn_track_info(z, data, amp_levels, P, var, shift, edge=11):
                                                  nat.ptr(P), nat.ptr(var_t), nat.ptr(shift, torch.int32), nat.ptr(info),
                                                  nat.ptr(counts, torch.int32), nat.current_stream(dev)), "vaeq_awgn_track_info")
     return _info_dict(info, counts, P)
+
+
+def awgn_track_llr(z, data, amp_levels, var, shift, hyp, edge=11):
+    """Per-bit a-posteriori LLRs of an AWGN baseline's soft sequence on the device (vaeq_awgn_track_llr), the input of a bit-wise decoder: z, data,
+    var, shift and edge as awgn_track_info got them (z float [R,2,Nz] planar or complex [R,Nz]; the layout follows from the dtype; data is needed
+    for the normalisation only), hyp[R] = that call's hyp -> llr[R,2b,Nd] f32 in nats, positive = bit 0: plane a b + k at TX index edge + j,
+    j < Nd - 2 edge - shift, is bit k of TX axis a of sample edge + shift + j, aligned with label_bits(data, n); everything else is an erasure,
+    +0.0, and a run whose window is empty or whose slice is zero is all zeros."""
+    dev, R = z.device, z.shape[0]
+    amp = _amp(amp_levels, dev)
+    n = amp.numel()
+    interleaved = z.is_complex()
+    if interleaved:
+        z = torch.view_as_real(z.to(torch.complex64).contiguous())
+    Nz, Nd = (z.shape[1] if interleaved else z.shape[-1]), data.shape[-1]
+    if tuple(z.shape) != ((R, Nz, 2) if interleaved else (R, 2, Nz)) or tuple(data.shape) != (R, 2, Nd):
+        raise ValueError(f"expected z[R,2,Nz] float or z[R,Nz] complex and data[R,2,Nd], got {tuple(z.shape)}, {tuple(data.shape)}")
+    var_t = _f32(var, dev).expand(R).contiguous()
+    z = z.float().contiguous()
+    data = _f16(data)
+    shift, hyp = _i32(shift, R, dev), _i32(hyp, R, dev)
+    llr = torch.empty(R, 2 * (n.bit_length() - 1), Nd, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_awgn_track_llr(R, Nz, Nd, n, int(edge), int(interleaved), nat.ptr(z), nat.ptr(data, torch.float16), nat.ptr(amp),
+                                                nat.ptr(var_t), nat.ptr(shift, torch.int32), nat.ptr(hyp, torch.int32), nat.ptr(llr),
+                                                nat.current_stream(dev)), "vaeq_awgn_track_llr")
+    return llr
 
 
 def awgn_dfe_soft(ff, fb_taps, dec, amp_levels):
