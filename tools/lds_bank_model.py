@@ -114,7 +114,77 @@ def half_split(NG, P):
     return out
 
 
+def half_passes(addrs):
+    """addrs: a float2 index for each of the 64 lanes (shadow lanes carry the address they really read) -> LDS passes of either half-wave"""
+    out = []
+    for h in range(2):
+        banks = defaultdict(set)
+        for a in addrs[32 * h:32 * h + 32]:
+            for d in (2 * a, 2 * a + 1):
+                banks[d % 64].add(d)
+        out.append(max(len(s) for s in banks.values()))
+    return out
+
+
+def dp_d3_model(B=100, M=25):
+    """D phase (P3) of the DP wave kernel at the baked B = 100 (csrc/vaeq_dp_wave_kernel.h): passes per half-wave of the mu reads of a tap stage and
+    of the six x / e cells, for the three-tau-per-lane mapping (D3Map) and for the plain one (lane l' < nq owns tau = 2l', 2l'+1 of both chi; the
+    lanes beyond shadow lane 0).  Tap reads are one word per half-wave (chi = lane >> 5) resp. per wave: one pass.    python tools/lds_bank_model.py dp_d3"""
+    mh = M // 2
+    Mh = 2 * mh
+    nm = 2 * B - Mh
+    T = nm // 2
+    Lph, Uph = wave_lph(2 * B + M - 1), B // 2 + 1
+    X, E = 0, 2 * 4 * wave_lph(2 * B + M - 1)
+    U = 2 * E
+    worst = {}
+    # three tau per lane: m = lane & 31 (m >= 30 shadows m = 0), chi = lane >> 5
+    m3 = [(l & 31) if (l & 31) < (T + 2) // 3 else 0 for l in range(64)]
+    chi = [l >> 5 for l in range(64)]
+    uE = [U + (m & 1) * Uph + ((3 * m) >> 1) for m in m3]
+    uO = [U + ((m & 1) ^ 1) * Uph + ((3 * m) >> 1) + (m & 1) for m in m3]
+    mu = []
+    for nu in range(2):
+        for b in range((mh + 1) // 2):
+            sl = (mh >> 1) - b
+            for base, o in ((uO, sl - 1), (uE, sl), (uO, sl), (uE, sl + 1)):
+                mu.append(max(half_passes([a + nu * 2 * Uph + o for a in base])))
+    worst["new mu"] = max(mu)
+    cells = []
+    for k in range(6):
+        off = []
+        for l in range(64):
+            m, q = m3[l], 2 * (m3[l] & 1)
+            off.append(chi[l] * 4 * Lph + (Mh >> 2) + ((3 * m) >> 1) + ((q + k) & 3) * Lph + ((q + k) >> 2))
+        cells.append(max(max(half_passes([X + o for o in off])), max(half_passes([E + o for o in off]))))
+    worst["new x / e cells"] = max(cells)
+    # plain mapping: lane l' < nq, the rest shadow lane 0
+    nq = (nm + 3) // 4
+    lq = [l if l < nq else 0 for l in range(64)]
+    mu = []
+    ph = mh & 1
+    for nu in range(2):
+        for b in range((mh + 1) // 2):
+            sl = (mh >> 1) - b
+            for o in (ph * Uph + sl, (ph ^ 1) * Uph + sl + ph, (ph ^ 1) * Uph + sl + ph - 1):
+                mu.append(max(half_passes([U + nu * 2 * Uph + l + o for l in lq])))
+    worst["plain mu"] = max(mu)
+    cells = []
+    for c in range(2):
+        for i in range(4):
+            ce = Mh + i
+            cells.append(max(half_passes([X + (c * 4 + (ce & 3)) * Lph + l + (ce >> 2) for l in lq])))
+    worst["plain x / e cells"] = max(cells)
+    print(f"DP wave kernel, D phase, B = {B}, M = {M}: Lph = {Lph}, Uph = {Uph}; worst LDS passes per half-wave and read:")
+    for k, v in worst.items():
+        print(f"  {k:18s} {v}")
+    return worst
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "dp_d3":
+        dp_d3_model()
+        sys.exit(0)
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 350
     M = int(sys.argv[2]) if len(sys.argv) > 2 else 25
     mh = M // 2

@@ -209,6 +209,41 @@ constexpr bool uniform_parts(int B, int M, int NP)
     return true;
 }
 
+// D phase (P3) of the baked B = 100, M = 25 kernel on one wave: the 2 chi x T (T = B - mh = 88) outputs pairs D[chi, 2 tau], D[chi, 2 tau + 1] are
+// independent of each other, and 2 T = 176 <= 64 x 3: lane L takes chi = L >> 5 and the TPL = 3 consecutive tau = 3 m + i of m = L & 31; the NM = 30
+// lanes m < NM of each half cover tau = 0..T-1, the two lanes beyond shadow m = 0 (no divergence, nothing stored).  Only m = NM - 1 has units past T
+// (tau = 88, 89): computed from cells inside the arrays, never stored.  208 complex MACs per lane become 150.
+// (No other phase splits like this: FIR, dL/dU and the demapper have 200 independent units > 192, the two tap gradients are sums with pinned parts.)
+struct D3Map {
+    static constexpr int TPL = 3;                                              // tau per lane
+    static constexpr int nm_lanes(int T) { return (T + TPL - 1) / TPL; }       // working lanes per chi
+    static constexpr int chi(int lane) { return lane >> 5; }
+    static constexpr bool works(int lane, int T) { return (lane & 31) < nm_lanes(T); }
+    static constexpr int m(int lane, int T) { return works(lane, T) ? (lane & 31) : 0; }
+    static constexpr bool stores(int lane, int i, int T) { return works(lane, T) && TPL * m(lane, T) + i < T; }
+    // every (chi, tau < T) is stored by exactly one (lane, i), nothing else is, and no mu cell beyond U[0 .. 2 Uph - 1] is read (a = 0: tau + mh)
+    static constexpr bool exact(int B, int M)
+    {
+        const int mh = M / 2, T = B - mh, Uph = B / 2 + 1;
+        if (nm_lanes(T) > 32 || T > 128) return false;
+        for (int c = 0; c < 2; c++) {
+            int cnt[128] = {};
+            for (int lane = 0; lane < 64; lane++)
+                for (int i = 0; i < TPL; i++) {
+                    const int tau = TPL * m(lane, T) + i;
+                    if (tau + mh >= 2 * Uph) return false;
+                    if (chi(lane) != c || !stores(lane, i, T)) continue;
+                    if (tau >= T) return false;
+                    cnt[tau]++;
+                }
+            for (int tau = 0; tau < 128; tau++)
+                if (cnt[tau] != (tau < T ? 1 : 0)) return false;
+        }
+        return true;
+    }
+};
+static_assert(D3Map::exact(100, 25), "B = 100: three tau per lane must cover tau = 0..87 of both chi exactly once");
+
 // OUT: 0 = every output nullable at run time; 1 = no compact outputs (eq_out / dec_out ignored); 2 = compact outputs, q not written.
 // The specialisations only drop dead code: fewer live scalars, fewer SGPR spills in the step loop.
 // NW = wavefronts per run: 1 (B <= 128, no barriers at all) or 2 / 4 / 8 (B <= 256 / 512 / 1024): thread gl = 64 wv + lane owns the symbol pair
@@ -232,7 +267,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     constexpr bool PIPE = VAEQ_PIPE && FIXL;               // run-time layouts keep more addresses live: there one operand set,
     constexpr bool WIDE = FIXL;                            // ... 8 accumulator chains and one chi at a time in dL/dU (fits the register file)
     // B100: the baked B = 100 kernel on one wave, the shape that is measured step by step and whose bits are pinned (tests/test_dp_wave_bits_gpu.py).
-    // It alone takes three forms; every other instantiation keeps the plain one, instruction for instruction:
+    // It alone takes four forms; every other instantiation keeps the plain one, instruction for instruction:
     //  * the halves of the two tap gradients meet on v_permlane32_swap (half_sum: one swap + one add per kept value) instead of 16 ds_bpermute_b32
     //    through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms (profiles/r04/kernel_variants_ab.txt)
     //  * the next window's prefetch is issued without a branch around it (the launch's very last step fetches with every lane out of range: zeros, no
@@ -241,6 +276,9 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     //    flight.  Now the first wait for them is P0 of the next step (profiles/r05/kernel_variants_ab.txt)
     //  * the q stores leave with the streaming ("nt") cache policy: 32 rows x 400 B per wave-step that nothing reads back before the launch ends
     //    (profiles/r05/kernel_variants_ab.txt; what the stores cost in total: profiles/r05/q_store_bound.txt)
+    //  * (M = 25) the D convolution of P3 runs three tau of one chi per lane on 60 lanes (D3Map) instead of two tau of both chi on 44: 300 instead of 416
+    //    packed FMAs per lane, every output's chain of FMAs in its old order; the residual's energy sum reads e back from LDS on its old lanes
+    //    (profiles/r06/kernel_variants_ab.txt)
     constexpr bool B100 = BT == 100 && NW == 1;
     constexpr int QAUX = B100 ? 2 : 0;                         // cache policy of the q stores
     const int B = BT ? BT : a.B;
@@ -563,7 +601,108 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 hq1 = h1.x * h1.x + h1.y * h1.y;
             }
             const float vsl = worker ? VS[half * M + tk] : 0.f;
-            {
+            if constexpr (B100 && M == 25) {
+                // B = 100: three tau of ONE chi per lane (D3Map) instead of two tau of both: 6 chains and 150 complex MACs per lane instead of 8 and 208.
+                // Every output keeps its chain: nu = 0: a = mh, 0, 1, .. mh - 1, then nu = 1 the same, the first term starting the accumulator.  Only the
+                // a = mh term of the odd parity is gone: it multiplies the zero pad tap (j = M), a +-0 that starts the chain or is added to it, which can
+                // change at most the sign of a D that is zero -- and x - (+-0) = x for every received sample x other than -0 (all pinned bits equal).
+                constexpr int T = 100 - mh, NB = (mh + 1) / 2;
+                static_assert((mh & 1) == 0 && (Mh & 3) == 0 && D3Map::exact(100, M), "D3Map: mh even (a = mh stands alone, its odd tap is the pad)");
+                int l3 = lane;                                 // the per-lane pointers are derived once per STEP: hoisted out of the step loop they
+                asm volatile("" : "+v"(l3));                   // would be ten more registers live through every phase, the register peak included
+                const int m3 = D3Map::m(l3, T), modd = m3 & 1, m3h = (3 * m3) >> 1;
+                cacc D3[3][2];                                 // [i][par]: D[chi, 2 (3 m + i) + par]
+                // the lane's six cells are the consecutive samples c = Mh + 6 m + k of its chi; 6 m = 2 (mod 4) for odd m: two pointer cases.
+                // x is read here, so that its LDS latency hides behind the tap loop
+                const int xo = D3Map::chi(l3) * 4 * Lph + (Mh >> 2) + m3h;
+                const int o0 = xo + (modd ? 2 * Lph : 0), o2 = xo + (modd ? 1 : 2 * Lph);
+                const int off[6] = {o0, o0 + Lph, o2, o2 + Lph, o0 + 1, o0 + Lph + 1};
+                v2f x6[6];
+#pragma unroll
+                for (int k = 0; k < 6; k++) x6[k] = lds2(Xs + off[k]);
+                {
+                    // U[nu][3 m + k] = (k even ? uE[k / 2] : uO[(k - 1) / 2]) + nu * 2 Uph: the polyphase component is a per-lane constant
+                    const float2 *uE = Us + modd * Uph + m3h, *uO = Us + (modd ^ 1) * Uph + m3h + modd;
+                    const float2 *hc = Ht + D3Map::chi(l3) * 2 * MP;
+                    v2f am[2][4];                              // a = mh of both nu: its reads never stand between two tap loops
+#pragma unroll
+                    for (int v = 0; v < 2; v++) {
+                        am[v][0] = lds2(hc + v * MP + Mh);
+                        am[v][1] = lds2(uE + v * 2 * Uph); am[v][2] = lds2(uO + v * 2 * Uph); am[v][3] = lds2(uE + v * 2 * Uph + 1);
+                    }
+#pragma unroll
+                    for (int v = 0; v < 2; v++) {
+                        const float2 *hv = hc + v * MP, *ue = uE + v * 2 * Uph, *uo = uO + v * 2 * Uph;
+                        {                                      // a = mh: U[3 m + i], even tap h[2 mh] (read ahead of the loops, below)
+                            const v2f t = am[v][0], u0 = am[v][1], u1 = am[v][2], u2 = am[v][3];
+                            if (v == 0) { cmul(D3[0][0], t, u0); cmul(D3[1][0], t, u1); cmul(D3[2][0], t, u2); }
+                            else { cmac(D3[0][0], t, u0); cmac(D3[1][0], t, u1); cmac(D3[2][0], t, u2); }
+                        }
+                        // stage b: a = 2b, 2b + 1: cells U[3 m + mh - 2b + d], d = -1..2, and taps h[4b .. 4b + 3]: 8 LDS reads feeding 24 packed FMAs
+                        auto load = [&](int b, v2f (&r)[8]) {
+                            const int sl = (mh >> 1) - b;      // 3 m + mh - 2b = even index 2 sl past the lane's base
+                            r[0] = lds2(uo + sl - 1); r[1] = lds2(ue + sl); r[2] = lds2(uo + sl); r[3] = lds2(ue + sl + 1);
+#pragma unroll
+                            for (int t = 0; t < 4; t++) r[4 + t] = lds2(hv + 4 * b + t);           // (even, odd) tap of a = 2b, of a = 2b + 1
+                        };
+                        auto fma = [&](int, const v2f (&r)[8], auto first) {
+                            constexpr bool F = decltype(first)::value;     // nu = 0, b = 0 starts the odd-parity chains
+                            // pin: the taps stay 8-byte registers up to here (the optimiser otherwise splits the set that lives across the loop's back edge
+                            // into halves at its loads: four copies behind s_waitcnt lgkmcnt(3..0) at the end of every trip)
+                            v2f t0 = r[4], t1 = r[5], t2 = r[6], t3 = r[7];
+                            asm volatile("" : "+v"(t0), "+v"(t1));         // (volatile: stays behind the next stage's loads)
+#pragma unroll
+                            for (int i = 0; i < 3; i++) {
+                                cmac(D3[i][0], t0, r[i + 1]);
+                                cmacf<F>(D3[i][1], t1, r[i + 1]);
+                                // the chain's first product is rounded on its own, as it is where the pad term starts the chain (0 * u + h U): pinned, or the
+                                // next term's multiply would be the one left unfused
+                                if constexpr (F) asm volatile("" : "+v"(D3[i][1].a), "+v"(D3[i][1].b));
+                            }
+                            asm volatile("" : "+v"(t2), "+v"(t3));
+#pragma unroll
+                            for (int i = 0; i < 3; i++) { cmac(D3[i][0], t2, r[i]); cmac(D3[i][1], t3, r[i]); }
+                        };
+                        if (v == 0) pipe2<8, true, PIPE>(NB, load, fma);
+                        else pipe2<8, false, PIPE>(NB, load, fma);
+                    }
+                }
+                VAEQ_STAMP(6);
+                {
+                    float2 e[6];
+#pragma unroll
+                    for (int k = 0; k < 6; k++) {
+                        const float2 x = f2(x6[k]);
+                        const float2 Dv = cfin(D3[k >> 1][k & 1]);
+                        e[k] = make_float2(x.x - Dv.x, x.y - Dv.y);
+                        if (6 * (D3Map::nm_lanes(T) - 1) + k >= 2 * T && 6 * m3 + k >= nm) e[k] = make_float2(0.f, 0.f);   // past nm: the pad stays zero
+                    }
+                    if (D3Map::works(l3, T)) {
+#pragma unroll
+                        for (int k = 0; k < 6; k++) Es[off[k]] = e[k];
+                    }
+                }
+                // sum |e|^2 keeps its lanes and its order (they set the bits of C and of the loss): lanes l' < nq read their quad back (one wave: LDS
+                // executes in issue order) and add exactly as the plain form below does
+                sync_lds<NW>();
+                {
+                    const float2 *Eq = Es + (gl < nq ? gl : 0);   // lanes without a quad read lane 0's and add nothing (no branch)
+                    v2f eq[2][4];                              // all eight reads in flight at once (lds2: one round trip, not four)
+#pragma unroll
+                    for (int chi = 0; chi < 2; chi++)
+#pragma unroll
+                        for (int i = 0; i < 4; i++) eq[chi][i] = lds2(Eq + (chi * 4 + ((Mh + i) & 3)) * Lph + ((Mh + i) >> 2));
+#pragma unroll
+                    for (int chi = 0; chi < 2; chi++)
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const float2 e = f2(eq[chi][i]);
+                            const float e2 = __builtin_fmaf(e.x, e.x, e.y * e.y);   // the contraction the plain form's e.x * e.x + e.y * e.y compiles to, spelled out
+                            if (chi) se1 += e2; else se0 += e2;
+                        }
+                    if (gl >= nq) se0 = se1 = 0.f;
+                }
+            } else {
                 cacc D[2][4];                                  // [chi][i], i = 2*dl + par; lanes without a quad shadow lane 0 (no divergence, unused)
                 constexpr int NA = mh + 1, NB = NA / 2;        // a = 0..mh; pairs (2b, 2b+1)
 #pragma unroll
