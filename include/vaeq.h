@@ -639,6 +639,38 @@ int vaeq_awgn_track_llr(int32_t R, int64_t Nz, int64_t Nd, int32_t n_lev, int32_
 int vaeq_awgn_dfe_soft(int32_t R, int64_t N, int32_t n_lev, int32_t K2, const float *ff, const float *fb, const int8_t *dec, const float *amp,
                        float *z, void *stream);
 
+/* Post-FEC figures on the device: a batched decoder of quasi-cyclic LDPC codes over the per-bit LLRs of the calls above (no reference counterpart:
+ * the reference stops at the SER).  The code: shifts_host[mb][nb] int32 in HOST memory, -1 = a zero block, 0 <= s < Z = a Z x Z circulant that
+ * connects check l Z + i to variable c Z + (i + s) mod Z; n = nb Z bits, m = mb Z checks.  The table is validated on every call and travels to
+ * the kernel by value in its arguments (no copy from pageable memory, nothing to keep alive).
+ * llr[R][w][N] float32 (positive = bit 0) and bits[R][w][N] int8 (the TX bits): the DP tensors [R][2][2b][N] with w = 4 b, the AWGN tensors with
+ * w = 2 b.  Bit j of codeword c of a run is global bit g = c n + j: symbol t0 + g / w, plane g % w -- symbol-major, so a codeword mixes all bit
+ * levels (and both polarisations) as BICM needs; n % w may be non-zero.  C codewords per run, t0 w + C n <= N w.
+ * No encoder: the TX bits are not a codeword, so the decoder works towards their syndrome sigma = H bits mod 2 (coset decoding).
+ * Layered normalized min-sum in float32, every multiply, add and subtract rounded on its own (nothing contracts to a fused multiply-add), in
+ * this order, so that a float32 model reproduces every bit:
+ *   start      L[v] = llr of bit v; sigma_i = parity of the TX bits on check i; every check's (m1, m2, idx, signs) = (0, 0, 0, 0).
+ *   negative   means x < 0: +-0 is bit 0, for the hard decisions x_v = (L[v] < 0) and for message signs alike.
+ *   test       H x = sigma, before the first iteration and after every full one; decoding stops at success or after max_iter iterations.
+ *   iteration  layers l = 0 .. mb - 1 in order; in layer l check i takes its edges e = 0, 1, .. in ascending block column, v_e its variable:
+ *              r_e = +-(alpha m2 if e == idx else alpha m1) from the check's stored state, negative iff bit e of signs;  t_e = L[v_e] - r_e;
+ *              m1, m2 = the smallest and second smallest |t_e|, idx = the first edge that attains m1;  s_e = (t_e < 0), S = xor_e s_e xor sigma_i;
+ *              r'_e = +-(alpha m2 if e == idx else alpha m1) of the NEW state, negative iff S xor s_e;  L[v_e] = t_e + r'_e.
+ *              (The checks of a layer own disjoint variables: they run in parallel with the result of any serial order.)
+ * out[R][C][5] int32 = iters (full iterations executed: 0 for a codeword that passes the first test), ok (the test passed at exit), post_err
+ * (decisions of the final L against the TX bits, over the n bits), pre_err (the same of the input), erased (inputs equal to +-0).
+ * post[R][C][n] float32 (nullable): the final L in codeword order.
+ * One workgroup per codeword, one thread per check of the layer in flight, the whole state in LDS: vaeq_ldpc_lds_bytes(mb, nb, Z) bytes (L,
+ * the TX bits as bytes, 16 bytes per check), VAEQ_ERR_SHAPE from that call outside the ranges of mb, nb and Z below.  Integer counts and a
+ * fixed operation order: two calls give identical bits.
+ * R == 0 is VAEQ_OK (its pointers may be NULL); a NULL shifts_host, llr, bits or out is VAEQ_ERR_NULL, before any shape rule; VAEQ_ERR_SHAPE, all
+ * before any HIP call: R < 0, C < 1, R C > 0x7fffffff, N < 1, N > 0x3fffffff, w outside 1 .. 64, t0 < 0, t0 w + C n > N w, max_iter outside
+ * 1 .. 100, mb outside 1 .. 8, nb outside 2 .. 64, Z outside 2 .. 512, a state above 64 KiB, a shift < -1 or >= Z, a block row with fewer than 2 or
+ * more than 32 non-zero blocks. */
+int vaeq_ldpc_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t mb, int32_t nb, int32_t Z, const int32_t *shifts_host,
+                     const float *llr, const int8_t *bits, float alpha, int32_t max_iter, int32_t *out, float *post, void *stream);
+int64_t vaeq_ldpc_lds_bytes(int32_t mb, int32_t nb, int32_t Z);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

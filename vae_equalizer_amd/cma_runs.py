@@ -15,7 +15,7 @@ from . import channel as ch
 from . import epilogue as epi
 from . import shared_funcs as sfun
 from .dp_runs import INFO_FLOAT, INFO_INT, DPRun, _host_pool, check_one_symb_rate, default_device, fresh_seed, resolve_generator  # noqa: F401
-from .engine import cma, cpe, soft_demap
+from .engine import cma, cpe, fec_figures, soft_demap
 
 N_CUT = 10   # symbols cut at both frame ends before the phase estimation (func_CMA_DP_MQAM_shaping.py:26,39)
 
@@ -65,7 +65,7 @@ def cma_frame_epilogue_torch(out_const, data, amp, nu_sc, var):
 
 
 def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frames, flex_step, channel, tau_cd, tau_pmd, phiIQ, N_lrhalf,
-                  device=None, generator=None, verbose=False, want_info=False, want_llr=False):
+                  device=None, generator=None, verbose=False, want_info=False, want_llr=False, fec=None):
     """R baseline runs (list of dp_runs.DPRun; lr_optim = the CMA step size) -> dict(SER[R,4,num_frames], Var_est[R,2,num_frames] (zeros,
     like the reference), var[R,2], h).  mode: "CMA" | "CMAbatch" | "CMAflex".
     want_info: also dict(AIR, GMI, NGMI, BER [R,2,num_frames] f32; kept, sym_err, bit_err, hyp [R,2,num_frames] int64) under "info", on the CPU
@@ -73,7 +73,9 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
     want_llr:  also dict(llr[R,2,2b,N'] f32, bits[R,2,2b,N'] int8, hyp[R,2]) under "llr", on the device, for the LAST frame only, like
                run_dp_batch's (N' = N_train_max - 20, the [10:-10] cut the epilogue gets): engine.cma_epilogue_llr on that frame's alignment
                under the winning hypothesis of one cma_epilogue_info call (want_info's, when that is on), and engine.label_bits of the cut TX
-               reference.  Every other output is the same with and without it."""
+               reference.  Every other output is the same with and without it.
+    fec:       dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75): also engine.ldpc_decode's figures of the LAST frame's LLRs (the pass
+               want_llr runs; "llr" itself is returned only with want_llr) under "fec", on the device.  None: no output changes."""
     if mode not in ("CMA", "CMAbatch", "CMAflex"):
         raise ValueError(f"unknown CMA variant {mode!r}")
     device = default_device() if device is None else torch.device(device)
@@ -95,8 +97,8 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
     streams = [ch.SeededStreams(r.seed) if r.seed is not None else None for r in runs]
     SER = torch.empty(R, 4, num_frames, dtype=torch.float32, device=device)
     P = np.stack([t["P"] for t in tabs])
-    P_t = INFO = LLR = None
-    if want_info or want_llr:
+    P_t = INFO = LLR = FEC = None
+    if want_info or want_llr or fec is not None:
         P_t = torch.tensor(P, dtype=torch.float32, device=device)
     if want_info:
         INFO = {k: torch.empty(R, 2, num_frames, dtype=torch.float32 if k in INFO_FLOAT else torch.int64, device=device)
@@ -122,7 +124,7 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
             raise ValueError(f"unknown generator {generator!r}")
         theta = theta + theta_diff
         out_const, e = cma(rx, h, lr.astype(np.float32), sps, mode, batch_len, flex_step, 1.0, want_e=verbose)
-        need_llr = want_llr and frame == num_frames - 1
+        need_llr = (want_llr or fec is not None) and frame == num_frames - 1
         if need_llr:
             res = cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=P_t, want_llr=True)
         else:
@@ -130,6 +132,8 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
         SER[:, :, frame] = res["SER"]
         if need_llr:
             LLR = res["llr"]
+            if fec is not None:
+                FEC = fec_figures(LLR, fec)
         if want_info:
             for k in INFO:
                 INFO[k][:, :, frame] = res["info"][k]
@@ -144,8 +148,10 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
     ret = dict(SER=SER.cpu(), Var_est=torch.zeros(R, 2, num_frames), var=torch.tensor(var_np), h=h)
     if INFO is not None:
         ret["info"] = {k: v.cpu() for k, v in INFO.items()}
-    if LLR is not None:
+    if LLR is not None and want_llr:
         ret["llr"] = LLR
+    if FEC is not None:
+        ret["fec"] = FEC
     return ret
 
 

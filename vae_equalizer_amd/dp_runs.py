@@ -15,7 +15,7 @@ import torch
 
 from . import channel as ch
 from . import shared_funcs as sfun
-from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info, dp_epilogue_llr, label_bits  # noqa: F401
+from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info, dp_epilogue_llr, fec_figures, label_bits  # noqa: F401
 
 
 @dataclass
@@ -109,7 +109,7 @@ def default_device():
 
 def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex_step, channel, tau_cd, tau_pmd, phiIQ,
                  N_lrhalf, flex=False, device=None, generator=None, verbose=False, threads=0, keep_last=False, want_info=False,
-                 want_llr=False):
+                 want_llr=False, fec=None):
     """Train + evaluate R runs.  Returns dict(SER[R,4,num_frames], Var_est[R,2,num_frames], var[R,2]) on the CPU.
 
     generator: None    = "hip" when no run carries a seed, "numpy" otherwise (resolve_generator);
@@ -123,6 +123,8 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
                sweep's LLRs would be tens of GB): engine.dp_epilogue_llr on that frame's soft-demapper alignment under the winning hypothesis
                of one dp_epilogue_info call (want_info's, when that is on) -- from q when the frame's q is materialised, from y otherwise --
                and engine.label_bits of the frame's TX reference.  Every other output is the same with and without it.
+    fec:       dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75): also engine.ldpc_decode's figures of the LAST frame's LLRs (the pass
+               want_llr runs; "llr" itself is returned only with want_llr) under "fec", on the device.  None: no output changes.
     """
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
@@ -165,7 +167,7 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
     SER = torch.empty(R, 4, num_frames, dtype=torch.float32, device=device)
     Var_est = torch.empty(R, 2, num_frames, dtype=torch.float32, device=device)
     INFO = None
-    if want_info or want_llr:
+    if want_info or want_llr or fec is not None:
         P_t = torch.tensor(P, dtype=torch.float32, device=device)
     if want_info:
         INFO = {k: torch.empty(R, 2, num_frames, dtype=torch.float32 if k in INFO_FLOAT else torch.int64, device=device)
@@ -215,7 +217,7 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
         Var_est[:, :, frame] = ve.mean(dim=2)                                   # :69
         res = dp_epilogue_compact(out["eq"][:, 0], out["dec"][:, 0], out["y"][:, 0], data, amp, nu_sc_t, var, None if flex else batch_len)
         SER[:, :, frame] = res["SER"]
-        need_llr = want_llr and frame == num_frames - 1
+        need_llr = (want_llr or fec is not None) and frame == num_frames - 1
         if want_info or need_llr:
             bl = None if flex else batch_len
             if out.get("q") is not None:
@@ -230,6 +232,8 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
                 src = dict(q=out["q"][:, 0]) if out.get("q") is not None else dict(y=out["y"][:, 0], nu_sc=nu_sc_t, var=var)
                 state["llr"] = dict(llr=dp_epilogue_llr(amp_levels=amp, shift=res["shift_q"], r=res["r_q"], hyp=fig["hyp"], batch_len=bl, **src),
                                     bits=label_bits(data, n_lev), hyp=fig["hyp"])
+                if fec is not None:
+                    state["fec"] = fec_figures(state["llr"], fec)
         return res, ve
 
     # Small batches (fewer runs than the device keeps resident: the script-faithful sweeps, 15 ... 300 runs) leave most of the chip idle
@@ -269,7 +273,7 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
                 finish_frame(frame, out, data)
         main.wait_stream(s_epi)
         main.wait_stream(s_gen)
-        for t in state.get("llr", {}).values():                                 # made on s_epi, used by the caller on main from here on
+        for t in (*state.get("llr", {}).values(), *state.get("fec", {}).values()):   # made on s_epi, used by the caller on main from here on
             t.record_stream(main)
     else:
         for frame in range(num_frames):
@@ -292,8 +296,10 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
     ret = dict(SER=SER.cpu(), Var_est=Var_est.cpu(), var=torch.tensor(var_np), engine=eng)
     if INFO is not None:
         ret["info"] = {k: v.cpu() for k, v in INFO.items()}
-    if "llr" in state:
+    if "llr" in state and want_llr:
         ret["llr"] = state["llr"]
+    if "fec" in state:
+        ret["fec"] = state["fec"]
     if last is not None:
         ret["last"] = last
     return ret

@@ -651,6 +651,79 @@ def label_bits(data, n_lev):
     return bits.reshape(*data.shape[:-2], 2 * b, data.shape[-1]).to(torch.int8)
 
 
+class LdpcCode:
+    """A quasi-cyclic LDPC code for ldpc_decode: shifts[mb, nb] of circulant shifts, -1 = a zero block, 0 <= s < Z = the Z x Z block that connects
+    check l Z + i to variable c Z + (i + s) mod Z.  n = nb Z bits, m = mb Z checks.  The decoder's envelope (1 <= mb <= 8, 2 <= nb <= 64,
+    2 <= Z <= 512, 2 .. 32 non-zero blocks in every block row, 64 KiB of state) is vaeq_ldpc_decode's to refuse."""
+
+    def __init__(self, shifts, Z):
+        import numpy as np
+        self.shifts = np.ascontiguousarray(np.asarray(shifts, dtype=np.int32))
+        if self.shifts.ndim != 2:
+            raise ValueError(f"expected shifts[mb, nb], got shape {self.shifts.shape}")
+        self.Z = int(Z)
+        self.mb, self.nb = (int(d) for d in self.shifts.shape)
+        self.n, self.m = self.nb * self.Z, self.mb * self.Z
+
+    def H(self):
+        """The dense parity-check matrix, uint8 [m, n] (for tests: n m bytes)."""
+        import numpy as np
+        H = np.zeros((self.m, self.n), np.uint8)
+        i = np.arange(self.Z)
+        for l in range(self.mb):
+            for c in range(self.nb):
+                s = int(self.shifts[l, c])
+                if s >= 0:
+                    H[l * self.Z + i, c * self.Z + (i + s) % self.Z] = 1
+        return H
+
+
+def array_code(mb, nb, Z):
+    """The array code: shift (l c) mod Z in block (l, c).  For a prime Z >= nb it has no 4-cycles."""
+    import numpy as np
+    return LdpcCode(np.outer(np.arange(mb), np.arange(nb)) % Z, Z)
+
+
+def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=0.75, want_post=False):
+    """Post-FEC figures of per-bit LLRs on the device (vaeq_ldpc_decode): layered normalized min-sum towards the syndrome of the TX bits (no
+    encoder).  llr f32 and bits int8 of one shape, [R,2,2b,N] (dp_epilogue_llr / cma_epilogue_llr with label_bits) or [R,w,N] (awgn_llr,
+    awgn_track_llr); bit j of codeword c of a run is global bit c n + j, at symbol t0 + (c n + j) // w in plane (c n + j) % w.  codewords: per
+    run, default the most that fit behind t0.  -> dict(iters, ok, bit_err, pre_err, erased [R,C] int64; BER_post[R], BER_pre[R], FER[R] f32
+    (FER: the share of codewords with bit_err > 0); post[R,C,n] f32, the final LLRs in codeword order, if want_post)."""
+    if llr.shape != bits.shape or llr.dim() not in (3, 4):
+        raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
+    dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
+    llr = llr.reshape(R, -1, N).contiguous()
+    bits = bits.reshape(R, -1, N).contiguous()
+    w, n = llr.shape[1], code.n
+    C_ = int(codewords) if codewords is not None else ((N - int(t0)) * w // n if n > 0 else 0)
+    if codewords is None and C_ < 1:
+        raise ValueError(f"no codeword of {n} bits fits into {N - int(t0)} symbols of {w} bits")
+    out = torch.empty(R, max(C_, 0), 5, dtype=torch.int32, device=dev)
+    post = torch.empty(R, max(C_, 0), n, dtype=torch.float32, device=dev) if want_post else None
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_ldpc_decode(R, C_, N, w, int(t0), code.mb, code.nb, code.Z, code.shifts.ctypes.data_as(C.c_void_p), nat.ptr(llr),
+                                             nat.ptr(bits, torch.int8), float(alpha), int(max_iter), nat.ptr(out, torch.int32), nat.ptr(post),
+                                             nat.current_stream(dev)), "vaeq_ldpc_decode")
+    o = out.long()
+    tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)   # a tensor divisor: a true division, not a product with 1 / tot
+    ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
+               BER_post=(o[..., 2].sum(1).double() / tot).float(), BER_pre=(o[..., 3].sum(1).double() / tot).float(),
+               FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float())
+    if want_post:
+        ret["post"] = post
+    return ret
+
+
+def fec_figures(llr, fec):
+    """run_dp_batch / run_cma_batch's fec= : ldpc_decode of an "llr" dict (llr, bits) under fec = dict(code, t0, max_iter, alpha; all but code
+    optional)."""
+    unknown = set(fec) - {"code", "t0", "max_iter", "alpha"}
+    if unknown or "code" not in fec:
+        raise ValueError(f"fec takes code, t0, max_iter, alpha; got {sorted(fec)}")
+    return ldpc_decode(llr["llr"], llr["bits"], fec["code"], **{k: v for k, v in fec.items() if k != "code"})
+
+
 def cma_epilogue(y, data, amp_levels, nu_sc, var):
     """The constant-modulus baselines' two-stage epilogue of one frame in one launch (vaeq_cma_epilogue): y[R,2,2,N] = phase-corrected output cut
     to [10:-10], data[R,2,2,N] fp16 cut likewise -> dict(SER[R,4] (constellation rows, then soft-demapper rows), shift_c, r_c, shift_q, r_q)."""
