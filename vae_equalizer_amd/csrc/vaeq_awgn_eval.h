@@ -2,6 +2,10 @@
 //   find_shift_symb (func_CMA_MQAM_shaping.py:127-140 = DFE_MQAM_shaping.py:137-150) and SER_CMA / SER_func (:63-94 = DFE_MQAM_shaping.py:107-135).
 // Shared by the CMA validation kernel (vaeq_awgn_cma.hip) and the LMMSE / DFE evaluation kernels (vaeq_awgn_dfe.hip).  A track is any
 // callable m -> float2 (re, im) of the equaliser output; the TX reference is the fp16 data of the run.
+// The window and the normalisation of that SER are also what the information-rate and LLR kernels of the AWGN family evaluate on
+// (vaeq_awgn_track_info / _llr.hip on a track, vaeq_awgn_info / _llr.hip on a validation frame), so they are written once, here: TrackWindow,
+// TrackRow, eval_radius_scale, awgn_row_scales.  A factor formed here multiplies every sample; two kernels that call the same function on the
+// same run get the same float.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -23,6 +27,79 @@ __device__ __forceinline__ float eval_block_sum(float v, float *red, int tid)
     for (int w = 0; w < NT / 64; w++) s += red[w];
     __syncthreads();
     return s;
+}
+
+// The window of a validator's SER, z[:, e+sh : -e] against data[:, e : -e-sh] (func_CMA_MQAM_shaping.py:231-232, DFE_MQAM_shaping.py:281, :293;
+// with Nz = Nd = N and e = AWGN_EDGE the window of validate_tail, vaeq_validate.h): kept symbol j < L pairs sample r0 + j, r0 = edge + shift, with
+// TX symbol edge + j, and the slice of z holds Lz = L + (Nz - Nd) samples from r0 on.  Where it is not empty r0 >= 1, r0 + Lz = Nz - edge and
+// edge + L = Nd - r0 < Nd: every index stays inside its row.  (64-bit: the lengths leave int32 for a shift or an edge nobody can find but anybody
+// can pass.)  An empty window has L = Lz = 0, so that it walks nothing.
+constexpr int AWGN_EDGE = 11;
+struct TrackWindow {
+    bool empty;
+    int L, Lz, edge, sft;
+    __device__ __forceinline__ TrackWindow(int Nz, int Nd, int edge_, int shift) : edge(edge_), sft(shift)
+    {
+        const long long L64 = (long long)Nd - 2LL * edge - sft;
+        empty = (long long)edge + sft <= 0 || L64 <= 0;        // (uniform: every thread of the workgroup takes the same side)
+        L = empty ? 0 : (int)L64;
+        Lz = empty ? 0 : L + (Nz - Nd);
+    }
+    __device__ __forceinline__ int sample(int j) const { return edge + sft + j; }   // of kept symbol j < L, or of slice sample j < Lz
+};
+
+// a track in memory: complex [Nz] (INTERLEAVED) or float [2][Nz] (planar)
+template <bool INTERLEAVED>
+struct TrackRow {
+    const float *zr;
+    int Nz;
+    __device__ __forceinline__ float2 operator()(int m) const
+    {
+        if constexpr (INTERLEAVED) return *reinterpret_cast<const float2 *>(zr + 2 * (size_t)m);
+        else return make_float2(zr[m], zr[(size_t)Nz + m]);
+    }
+};
+
+// The radius normalisation of SER_CMA / SER_func on track[r0 : r0 + Lr] against the TX slice d0, d1 [L], Lr >= L:
+// scale = mean|tx| (L symbols) / mean|track| (ALL Lr samples), per thread strided in index order, then eval_block_sum.  ar: sum |track|, whose
+// zero means a slice without a normalisation.  red: NT / 64 floats.  Returns scale in every thread.
+template <int NT, class Track>
+__device__ __forceinline__ float eval_radius_scale(const Track &track, int r0, int Lr, const __half *d0, const __half *d1, int L, float *red,
+                                                   int tid, float &ar)
+{
+    float at = 0.f;
+    ar = 0.f;
+    for (int m = tid; m < L; m += NT) {
+        const float t0 = __half2float(d0[m]), t1 = __half2float(d1[m]);
+        const float2 v = track(r0 + m);
+        at += sqrtf(t0 * t0 + t1 * t1);
+        ar += sqrtf(v.x * v.x + v.y * v.y);
+    }
+    for (int m = L + tid; m < Lr; m += NT) {                   // the track samples past the data slice (LMMSE: one)
+        const float2 v = track(r0 + m);
+        ar += sqrtf(v.x * v.x + v.y * v.y);
+    }
+    at = eval_block_sum<NT>(at, red, tid);
+    ar = eval_block_sum<NT>(ar, red, tid);
+    return (at / (float)L) / (ar / (float)Lr);
+}
+
+// The VAE-LE demapper's normalisation of a validation frame y[2][N] (func_VAELE_MQAM_shaping.py:228): sc[c] = A / m_c, m_c = sum_n |y_c[n]| / N
+// over the WHOLE row, per thread in index order, then eval_block_sum; walk = false sums nothing (an empty window needs no factor).
+// Returns false where a component is zero throughout: no normalisation, no measurement.
+template <int NT>
+__device__ __forceinline__ bool awgn_row_scales(const float *__restrict__ src, int N, bool walk, float A, float *red, int tid, float (&sc)[2])
+{
+    float sa0 = 0.f, sa1 = 0.f;
+    if (walk) {                                                // (uniform: every thread of the workgroup takes the same side)
+#pragma unroll 4
+        for (int n = tid; n < N; n += NT) { sa0 += fabsf(src[n]); sa1 += fabsf(src[(size_t)N + n]); }
+    }
+    sa0 = eval_block_sum<NT>(sa0, red, tid);
+    sa1 = eval_block_sum<NT>(sa1, red, tid);
+    const float m0 = sa0 / (float)N, m1 = sa1 / (float)N;
+    sc[0] = A / m0; sc[1] = A / m1;
+    return m0 != 0.f && m1 != 0.f;
 }
 
 // find_shift_symb(track, tx, n_shift) (n_shift <= 64): corr[rail][i] = sum_m tx[rail][hs + m] * track(i + m).x, m < 1000 - hs, one wave per
@@ -66,20 +143,8 @@ template <int NT, class Track>
 __device__ __forceinline__ float eval_ser(const Track &track, int r0, int Lr, const __half *d0, const __half *d1, int L, const float *lev,
                                           int n_lev, float *red, int tid)
 {
-    float at = 0.f, ar = 0.f;
-    for (int m = tid; m < L; m += NT) {
-        const float t0 = __half2float(d0[m]), t1 = __half2float(d1[m]);
-        const float2 v = track(r0 + m);
-        at += sqrtf(t0 * t0 + t1 * t1);
-        ar += sqrtf(v.x * v.x + v.y * v.y);
-    }
-    for (int m = L + tid; m < Lr; m += NT) {                   // the track samples past the data slice (LMMSE: one)
-        const float2 v = track(r0 + m);
-        ar += sqrtf(v.x * v.x + v.y * v.y);
-    }
-    at = eval_block_sum<NT>(at, red, tid);
-    ar = eval_block_sum<NT>(ar, red, tid);
-    const float scale = (at / (float)L) / (ar / (float)Lr);
+    float ar;
+    const float scale = eval_radius_scale<NT>(track, r0, Lr, d0, d1, L, red, tid, ar);
     const float sl = 0.5f * (float)(n_lev - 1);
     const int top = n_lev - 1;                                 // 2 * scale: the level index mirror
     int e0 = 0, e1 = 0, e2 = 0, e3 = 0;

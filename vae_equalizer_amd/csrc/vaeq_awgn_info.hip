@@ -12,8 +12,10 @@
 // once and every hypothesis is a selection among (axis, level in {t_I, n-1-t_I, t_Q, n-1-t_Q}).
 // Integer counts are exact; float sums run per thread in symbol order, then over the wave's lanes (DPP, fixed order), then over the four waves in
 // order: no atomics, two calls give identical bits.
-// This file holds the window, the pre-pass for the two means, the early-out and the VAE-LE demapper's exponent; the per-symbol body and the tail
-// are vaeq_info.h's (info_symbol<NL, YMODE, 4>: no IQ flip; info_finish with K = len given, not counted), shared with the two DP kernels.
+// This file holds the early-out and the accumulation.  The window, the pre-pass for the two means, the q-mode load and the VAE-LE demapper's
+// exponent are the text awgn_llr_kernel runs as well (TrackWindow and awgn_row_scales of vaeq_awgn_eval.h, info_load_q and info_awgn_log2 of
+// vaeq_info.h); the per-symbol body and the tail are vaeq_info.h's (info_symbol<NL, YMODE, 4>: no IQ flip; info_finish with K = len given, not
+// counted), shared with the two DP kernels.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -27,7 +29,7 @@
 
 namespace vaeq {
 
-constexpr int AINFO_NT = 256, AINFO_WAVES = AINFO_NT / 64, AINFO_EDGE = 11;
+constexpr int AINFO_NT = 256, AINFO_WAVES = AINFO_NT / 64;
 
 template <int NL, bool YMODE>
 __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float *__restrict__ q, const float *__restrict__ y,
@@ -36,34 +38,22 @@ __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float 
                                                              const float *__restrict__ var, const int32_t *__restrict__ shift,
                                                              float *__restrict__ info, int32_t *__restrict__ counts)
 {
-    constexpr float LOG2E = 1.4426950408889634f;
     __shared__ float red[AINFO_WAVES];                         // eval_block_sum's scratch (y-mode: the two sums of |y_c|)
     __shared__ InfoShared<4, AINFO_WAVES> sh;
     const int run = blockIdx.x, tid = threadIdx.x;
     float *o = info + (size_t)run * 3;
     int32_t *cn = counts + (size_t)run * 4;
     // the window of validate_tail: kept symbol j < len pairs sample 11 + sft + j with TX symbol 11 + j; where it is not empty -10 <= sft <= N - 23,
-    // so both stay inside [11, N - 11).  (64-bit: N - 22 - sft leaves int32 for a shift nobody can find but anybody can pass)
-    const int sft = shift[run];
-    const long long len64 = (long long)N - 2 * AINFO_EDGE - (long long)sft;
-    bool empty = (long long)AINFO_EDGE + sft <= 0 || len64 <= 0;
-    const int len = empty ? 0 : (int)len64;
+    // so both stay inside [11, N - 11)
+    const TrackWindow w(N, N, AWGN_EDGE, shift[run]);
+    bool empty = w.empty;
+    const int len = w.L;
 
     const float *src = YMODE ? y + (size_t)run * 2 * N : q + (size_t)run * 2 * NL * N;
     float amp[NL], sc[2] = {0.f, 0.f}, ivl = 0.f;
     if constexpr (YMODE) {
-        // m_c = sum_n |y_c[n]| / N over the whole row: per thread in index order, over the wave's lanes, over the waves in order
-        float sa0 = 0.f, sa1 = 0.f;
-        if (!empty) {                                          // (uniform: every thread of the workgroup takes the same side)
-#pragma unroll 4
-            for (int n = tid; n < N; n += AINFO_NT) { sa0 += fabsf(src[n]); sa1 += fabsf(src[(size_t)N + n]); }
-        }
-        sa0 = eval_block_sum<AINFO_NT>(sa0, red, tid);
-        sa1 = eval_block_sum<AINFO_NT>(sa1, red, tid);
-        const float m0 = sa0 / (float)N, m1 = sa1 / (float)N, A = amp_mean[run];
-        if (m0 == 0.f || m1 == 0.f) empty = true;              // a component that is zero throughout has no normalisation: no measurement
-        sc[0] = A / m0; sc[1] = A / m1;
-        ivl = LOG2E / var[run];
+        if (!awgn_row_scales<AINFO_NT>(src, N, !empty, amp_mean[run], red, tid, sc)) empty = true;
+        ivl = INFO_LOG2E / var[run];
 #pragma unroll
         for (int i = 0; i < NL; i++) amp[i] = amp_g[i];
     }
@@ -84,22 +74,13 @@ __global__ __launch_bounds__(AINFO_NT) void awgn_info_kernel(int N, const float 
     for (int i = 0; i < 4; i++) se[i] = be[i] = 0;
 
     for (int j = tid; j < len; j += AINFO_NT) {
-        const int m = AINFO_EDGE + sft + j, n = AINFO_EDGE + j;
+        const int m = w.sample(j), n = AWGN_EDGE + j;
         const __half txi = txI[n], txq = txQ[n];
         float v[2][NL];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
-            if constexpr (YMODE) {
-                const float yv = src[(size_t)c * N + m] * sc[c];
-#pragma unroll
-                for (int i = 0; i < NL; i++) {
-                    const float dd = yv - amp[i];
-                    v[c][i] = -(dd * dd) * ivl;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < NL; i++) v[c][i] = src[(size_t)(c * NL + i) * N + m];
-            }
+            if constexpr (YMODE) info_awgn_log2<NL>(src[(size_t)c * N + m] * sc[c], amp, ivl, v[c]);
+            else info_load_q<NL>(src, N, m, c, v[c]);
         }
         info_symbol<NL, YMODE, 4>(v, txi, txq, fs, se, be);
     }
@@ -115,7 +96,7 @@ extern "C" int vaeq_awgn_info(int32_t R, int64_t N, int32_t n_lev, const float *
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if ((q != nullptr) == (y != nullptr)) return VAEQ_ERR_NULL;                                  // exactly one source of posteriors
     if (!data_f16 || !amp || !P || !shift || !info || !counts || (y && (!amp_mean || !var))) return VAEQ_ERR_NULL;
-    if (R < 0 || N < 1 || N > 0x3fffffff) return VAEQ_ERR_SHAPE;
+    if (!vaeq::awgn_frame_shape_ok(R, N)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *tx = reinterpret_cast<const __half *>(data_f16);
     return vaeq::dispatch_nlev(n_lev, [&](auto nl) {

@@ -5,12 +5,12 @@
 // :293).  The reference has no such metric; the definitions are closed-form (include/vaeq.h, DESIGN.md section 5,
 // tests/_ref_awgn_baseline_info.py).
 //
-// awgn_track_info_kernel: one 256-thread workgroup per run.  A pre-pass forms the two radius sums of the validators' normalisation (eval_ser,
-// vaeq_awgn_eval.h: mean|tx| over the L kept symbols, mean|z| over ALL Lz samples of the slice, which for the LMMSE output is one more), in
-// eval_ser's order: per thread strided in index order, then eval_block_sum.  Every kept symbol is then read ONCE, scaled, demapped by the AWGN
-// reference's own demapper (func_VAELE_MQAM_shaping.py:229: -(zhat_c - a_i)^2 / var per axis, no 1/2, no prior term) in the log domain, and all
-// four relabelings of eval_ser (e0..e3, in that order) accumulate in that pass; nothing else goes to memory.  The per-symbol body and the tail
-// are vaeq_info.h's (info_symbol<NL, true, 4>, info_finish with K = L given): this file holds the window, the normalisation and the exponent.
+// awgn_track_info_kernel: one 256-thread workgroup per run.  A pre-pass forms the validators' normalisation (eval_radius_scale, vaeq_awgn_eval.h,
+// which eval_ser calls too: mean|tx| over the L kept symbols, mean|z| over ALL Lz samples of the slice, which for the LMMSE output is one more).
+// Every kept symbol is then read ONCE, scaled, demapped by the AWGN reference's own demapper (info_awgn_log2, vaeq_info.h) in the log domain, and
+// all four relabelings of eval_ser (e0..e3, in that order) accumulate in that pass; nothing else goes to memory.  Window, track, normalisation and
+// exponent are the text awgn_track_llr_kernel runs as well; the per-symbol body and the tail are vaeq_info.h's (info_symbol<NL, true, 4>,
+// info_finish with K = L given).  This file holds the early-outs and the accumulation.
 // Integer counts are exact; float sums run in a fixed order without atomics: two calls give identical bits, R runs the bits of R single calls.
 //
 // dfe_soft_kernel: the soft sequence the reference's DFE never keeps -- the slicer input of dfe() (DFE_MQAM_shaping.py:215-221) rebuilt from the
@@ -37,7 +37,6 @@ __global__ __launch_bounds__(TINFO_NT) void awgn_track_info_kernel(int Nz, int N
                                                                    const int32_t *__restrict__ shift, float *__restrict__ info,
                                                                    int32_t *__restrict__ counts)
 {
-    constexpr float LOG2E = 1.4426950408889634f;
     __shared__ float red[TINFO_WAVES];                         // eval_block_sum's scratch
     __shared__ InfoShared<4, TINFO_WAVES> sh;
     const int run = blockIdx.x, tid = threadIdx.x;
@@ -49,42 +48,21 @@ __global__ __launch_bounds__(TINFO_NT) void awgn_track_info_kernel(int Nz, int N
             cn[0] = cn[1] = cn[2] = cn[3] = 0;
         }
     };
-    // the window: kept symbol j < L pairs sample r0 + j with TX symbol edge + j, and the slice of z holds Lz = L + (Nz - Nd) samples from r0 on.
-    // Where it is not empty r0 >= 1, r0 + Lz = Nz - edge and edge + L = Nd - r0 < Nd: every index stays inside its row.  (64-bit: the lengths
-    // leave int32 for a shift or an edge nobody can find but anybody can pass)
-    const long long sft = shift[run], L64 = (long long)Nd - 2LL * edge - sft;
-    if ((long long)edge + sft <= 0 || L64 <= 0) {              // (uniform: every thread of the workgroup takes the same side)
+    const TrackWindow w(Nz, Nd, edge, shift[run]);
+    if (w.empty) {
         nothing();
         return;
     }
-    const int L = (int)L64, Lz = L + (Nz - Nd), r0 = edge + (int)sft;
-    const float *zr = zg + (size_t)run * 2 * Nz;
-    auto track = [&](int m) {
-        if constexpr (INTERLEAVED) return *reinterpret_cast<const float2 *>(zr + 2 * (size_t)m);
-        else return make_float2(zr[m], zr[(size_t)Nz + m]);
-    };
+    const int L = w.L, r0 = w.sample(0);
+    const TrackRow<INTERLEAVED> track{zg + (size_t)run * 2 * Nz, Nz};
     const __half *txI = txg + (size_t)run * 2 * Nd + edge, *txQ = txI + Nd;
-
-    // eval_ser's normalisation: scale = mean|tx| (L symbols) / mean|z| (all Lz samples of the slice)
-    float at = 0.f, ar = 0.f;
-    for (int m = tid; m < L; m += TINFO_NT) {
-        const float t0 = __half2float(txI[m]), t1 = __half2float(txQ[m]);
-        const float2 v = track(r0 + m);
-        at += sqrtf(t0 * t0 + t1 * t1);
-        ar += sqrtf(v.x * v.x + v.y * v.y);
-    }
-    for (int m = L + tid; m < Lz; m += TINFO_NT) {             // the samples past the data slice (LMMSE: one)
-        const float2 v = track(r0 + m);
-        ar += sqrtf(v.x * v.x + v.y * v.y);
-    }
-    at = eval_block_sum<TINFO_NT>(at, red, tid);
-    ar = eval_block_sum<TINFO_NT>(ar, red, tid);
+    float ar;
+    const float scale = eval_radius_scale<TINFO_NT>(track, r0, w.Lz, txI, txQ, L, red, tid, ar);
     if (ar == 0.f) {                                           // a slice that is zero throughout has no normalisation: no measurement
         nothing();
         return;
     }
-    const float scale = (at / (float)L) / (ar / (float)Lz);
-    const float ivl = LOG2E / var[run];
+    const float ivl = INFO_LOG2E / var[run];
     float amp[NL];
 #pragma unroll
     for (int i = 0; i < NL; i++) amp[i] = amp_g[i];
@@ -97,15 +75,9 @@ __global__ __launch_bounds__(TINFO_NT) void awgn_track_info_kernel(int Nz, int N
     for (int i = 0; i < 4; i++) se[i] = be[i] = 0;
     for (int j = tid; j < L; j += TINFO_NT) {
         const float2 zs = track(r0 + j);
-        const float zc[2] = {zs.x * scale, zs.y * scale};
         float v[2][NL];
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int i = 0; i < NL; i++) {
-                const float dd = zc[c] - amp[i];
-                v[c][i] = -(dd * dd) * ivl;
-            }
+        info_awgn_log2<NL>(zs.x * scale, amp, ivl, v[0]);
+        info_awgn_log2<NL>(zs.y * scale, amp, ivl, v[1]);
         info_symbol<NL, true, 4>(v, txI[j], txQ[j], fs, se, be);
     }
     info_finish<NL, 4, TINFO_WAVES, false>(sh, tid, fs, se, be, L, Pg + (size_t)run * NL, o, cn);
@@ -153,8 +125,7 @@ extern "C" int vaeq_awgn_track_info(int32_t R, int64_t Nz, int64_t Nd, int32_t n
 {
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!z || !data_f16 || !amp || !P || !var || !shift || !info || !counts) return VAEQ_ERR_NULL;
-    if (R < 0 || Nd < 1 || (Nz != Nd && Nz != Nd + 1) || Nz > 0x3fffffff || edge < 0 || (interleaved != 0 && interleaved != 1))
-        return VAEQ_ERR_SHAPE;
+    if (!vaeq::track_shape_ok(R, Nz, Nd, edge, interleaved)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *tx = reinterpret_cast<const __half *>(data_f16);
     return vaeq::dispatch_nlev(n_lev, [&](auto nl) {

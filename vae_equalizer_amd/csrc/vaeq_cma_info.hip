@@ -6,8 +6,9 @@
 //   stage c:  ya[p'][c][m] = y[(p' - r_c) & 1][c][(m + shift_c[p']) mod N],   W_c = [11, N - 11 - max|shift_c|)
 //             fac = sum_{p', m in W_c} |tx[p'][:, m]| / sum_{p', m in W_c} |ya[p'][:, m]|,   yn = ya fac inside W_c, ya outside it
 //   stage q:  kept symbol n in [11, N - 11 - max|shift_q|) of output polarisation p reads yn[p' = (p - r_q) & 1][:, m = n + shift_q[p]]
-// and demaps it with var[p'] in the log domain.  What is this kernel's own is that addressing, the radius walk and the two calls of the tail; the
-// per-symbol body, the tail and the demapper's exponent are vaeq_info.h's (info_symbol, info_finish, info_demap_log2), shared with the siblings.
+// and demaps it with var[p'] in the log domain.  That addressing, the radius walk and the demapper are vaeq_info.h's (CmaFrame, cma_radius_factor,
+// info_demap_setup / info_demap_log2), the one text vaeq_cma_llr.hip runs as well; the per-symbol body and the tail are vaeq_info.h's too
+// (info_symbol, info_finish).  What is this kernel's own is the accumulation over a polarisation's kept symbols and the two calls of the tail.
 //
 // One workgroup per run, three walks: the first forms fac, the second and third the figures of output polarisation 0 and 1.
 // y and tx are read, nothing but the 56 bytes of results per run is written.  Integer counts are exact; float sums run per thread in index order,
@@ -37,52 +38,22 @@ __global__ __launch_bounds__(EPI_NT) void cma_epilogue_info_kernel(int N, const 
                                                                    const int32_t *__restrict__ shift_q, const int32_t *__restrict__ r_q,
                                                                    float *__restrict__ info, int32_t *__restrict__ counts)
 {
-    __shared__ float rad[CMA_INFO_WAVES][2];                   // [wave][0: sum |tx|, 1: sum |ya|] over W_c
+    __shared__ float rad[CMA_INFO_WAVES][2];                   // cma_radius_factor's scratch
     __shared__ InfoShared<8, CMA_INFO_WAVES> sh;
-    const int run = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    // both alignments clamped to what the epilogue can find: with 11 <= n and a window that ends 11 + max|shift| before the row does, n + shift
-    // stays inside [1, N - 1) in either stage; only the stage-c roll of a sample outside W_c can wrap around the frame
-    const int c0 = info_clamp_shift(shift_c[run * 2 + 0]), c1 = info_clamp_shift(shift_c[run * 2 + 1]);
-    const int q0 = info_clamp_shift(shift_q[run * 2 + 0]), q1 = info_clamp_shift(shift_q[run * 2 + 1]);
-    const int rc = r_c[run] & 1, rq = r_q[run] & 1;
-    const int endc = N - EDGE - max(abs(c0), abs(c1)), endq = N - EDGE - max(abs(q0), abs(q1));   // W_c = [EDGE, endc), kept = [EDGE, endq)
-    const float *yr = y + (size_t)run * 4 * N;
-    const __half *txr = txg + (size_t)run * 4 * N;
+    const int run = blockIdx.x, tid = threadIdx.x;
+    const CmaFrame f(run, N, y, txg, shift_c, r_c, shift_q, r_q);
 
-    // ---- walk 1: mean radius of TX over mean radius of the stage-c aligned output, both polarisations, over W_c (shared_funcs.py:242)
-    float st = 0.f, sy = 0.f;
-    for (int n = tid; n < N; n += EPI_NT) {
-        if (n < EDGE || n >= endc) continue;
-#pragma unroll
-        for (int pp = 0; pp < 2; pp++) {
-            const int sp = (pp - rc) & 1, m = n + (pp ? c1 : c0);                                // 1 <= m < N - 1
-            const float ti = __half2float(txr[(size_t)(pp * 2 + 0) * N + n]), tq = __half2float(txr[(size_t)(pp * 2 + 1) * N + n]);
-            const float yi = yr[(size_t)(sp * 2 + 0) * N + m], yq = yr[(size_t)(sp * 2 + 1) * N + m];
-            st += sqrtf(fmaf(ti, ti, tq * tq));
-            sy += sqrtf(fmaf(yi, yi, yq * yq));
-        }
-    }
-    st = wave_sum_dpp(st);
-    sy = wave_sum_dpp(sy);
-    if (lane == 0) { rad[w][0] = st; rad[w][1] = sy; }
-    __syncthreads();
-    st = sy = 0.f;
-    for (int k = 0; k < CMA_INFO_WAVES; k++) { st += rad[k][0]; sy += rad[k][1]; }
-    const bool degenerate = sy == 0.f;                         // no radius, no normalisation: the run reports the empty-window result
-    const float fac = st / sy;
+    // ---- walk 1: the mean-radius factor; a degenerate run reports the empty-window result
+    bool degenerate;
+    const float fac = cma_radius_factor<CMA_INFO_WAVES>(f, rad, tid, degenerate);
 
     // ---- walk 2, once per output polarisation p: its kept symbols
 #pragma unroll 1
     for (int p = 0; p < 2; p++) {
-        const int pp = (p - rq) & 1, sft = p ? q1 : q0;            // stage q: row p comes from aligned row p - r_q, out[n] = in[n + shift_q[p]]
-        const int sp = (pp - rc) & 1, sfc = pp ? c1 : c0;          // stage c: aligned row p' comes from row p' - r_c of y, rolled by shift_c[p'] (wrapping)
-        const float *yI = yr + (size_t)(sp * 2) * N, *yQ = yI + N;
-        const __half *txI = txr + (size_t)(p * 2) * N, *txQ = txI + N;
-        const float nusc = nu_sc[run];
-        const float i2v = 0.5f / var[run * 2 + pp];                // the demapper of the stage-c aligned polarisation, as in the epilogue
+        const float *yI = f.y_row(p), *yQ = yI + N;
+        const __half *txI = f.txr + (size_t)(p * 2) * N, *txQ = txI + N;
         float amp[NL], pen[NL];
-#pragma unroll
-        for (int i = 0; i < NL; i++) { amp[i] = amp_g[i]; pen[i] = nusc * (amp[i] * amp[i]); }
+        const float i2v = info_demap_setup<NL>(amp_g, nu_sc, var, run, f.aligned_row(p), amp, pen);   // the demapper of the stage-c aligned polarisation
 
         float fs[16];
         int se[8], be[8], kept = 0;
@@ -92,12 +63,9 @@ __global__ __launch_bounds__(EPI_NT) void cma_epilogue_info_kernel(int N, const 
         for (int i = 0; i < 8; i++) se[i] = be[i] = 0;
 
         for (int n = tid; n < N && !degenerate; n += EPI_NT) {
-            if (n < EDGE || n >= endq) continue;
-            const int m = n + sft;                                 // index in the stage-c aligned sequence, 1 <= m < N - 1
-            int ms = m + sfc;                                      // index in y: -9 <= ms < N + 9, one wrap at most (N >= 43)
-            if (ms >= N) ms -= N;
-            if (ms < 0) ms += N;
-            const float g = (m >= EDGE && m < endc) ? fac : 1.0f;  // scaled exactly where the aligned index lies in W_c
+            if (!f.kept(n)) continue;
+            float g;
+            const int ms = f.source(p, n, fac, g);
             kept++;
             const __half txi = txI[n], txq = txQ[n];
             float v[2][NL];
@@ -120,7 +88,7 @@ extern "C" int vaeq_cma_epilogue_info(int32_t R, int64_t N, int32_t n_lev, const
 {
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!y || !tx_f16 || !amp || !P || !var || !nu_sc || !shift_c || !r_c || !shift_q || !r_q || !info || !counts) return VAEQ_ERR_NULL;
-    if (R < 0 || N < 2 * vaeq::EDGE + vaeq::N_SHIFT || N > 0x3fffffff) return VAEQ_ERR_SHAPE;
+    if (!vaeq::epi_frame_shape_ok(R, N, 0)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *tx = reinterpret_cast<const __half *>(tx_f16);
     return vaeq::dispatch_nlev(n_lev, [&](auto nl) {

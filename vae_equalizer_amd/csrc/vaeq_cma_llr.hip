@@ -1,18 +1,18 @@
 // vaeq_cma_llr.hip -- the per-bit a-posteriori LLRs of one frame of the constant-modulus DP baselines on the device: what a bit-wise (LDPC) decoder
-// behind CMA / CMAbatch / CMAflex reads, and what the GMI of vaeq_cma_epilogue_info is the rate of.  The posteriors are that kernel's, term for
-// term (vaeq_cma_info.hip has the derivation): both shifts clamped, the stage-c roll wrapping around the frame, the mean-radius factor
+// behind CMA / CMAbatch / CMAflex reads, and what the GMI of vaeq_cma_epilogue_info is the rate of.  The posteriors are that kernel's because the
+// text that forms them is: CmaFrame, cma_radius_factor and the demapper of vaeq_info.h, which both kernels call (vaeq_cma_info.hip has the
+// derivation) -- both shifts clamped, the stage-c roll wrapping around the frame, the mean-radius factor
 //     fac = sum_{p', m in W_c} |tx[p'][:, m]| / sum_{p', m in W_c} |ya[p'][:, m]|,   W_c = [11, N - 11 - max|shift_c|)
 // applied exactly where a sample's stage-c index lies in W_c, and the demapper of the stage-c aligned row p' = (p - r_q) & 1.  Over the symbols it
 // keeps, n in [11, N - 11 - max|shift_q|), and under the hypothesis it picked (hyp & 7), the LLRs land in TX order: plane a b + k of output
 // polarisation p at TX index n is bit k of TX axis a; every other entry is an erasure, +0.0, and a run without a radius (sum |ya| == 0) is all zeros.
 //
 // 256 threads; grid (run, polarisation) for a batch that leaves the device idle otherwise, grid (run) -- one workgroup takes both polarisations
-// in turn -- for a large one.  fac decides every LLR of the run, and the LLRs are those of the posteriors whose GMI is reported only if it is the
-// same float: the radius walk is cma_epilogue_info_kernel's walk 1 restated (per thread at stride EPI_NT, wave_sum_dpp, the waves in order), and
-// on the split grid each of the run's two workgroups redoes it identically.  After it the work is elementwise: thread t takes n = t, t + 256, ...,
-// consecutive lanes on consecutive n, so every read and each of the 2 b plane stores is contiguous across the wave.  32 bytes of LDS (the cross-wave
-// radius scratch), no atomics: two calls give identical bits, R runs in one call the bits of R single calls.
-// This file holds the addressing and the radius walk; the per-symbol body is vaeq_llr.h's, the demapper's exponent vaeq_info.h's.
+// in turn -- for a large one.  fac decides every LLR of the run; on the split grid each of the run's two workgroups forms it identically.  After
+// it the work is elementwise: thread t takes n = t, t + 256, ..., consecutive lanes on consecutive n, so every read and each of the 2 b plane
+// stores is contiguous across the wave.  32 bytes of LDS (the cross-wave radius scratch), no atomics: two calls give identical bits, R runs in one
+// call the bits of R single calls.
+// This file holds the grid, the erasures and the plane stores; the per-symbol body is vaeq_llr.h's.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,59 +40,26 @@ __global__ __launch_bounds__(EPI_NT) void cma_epilogue_llr_kernel(int N, const f
                                                                   float *__restrict__ llr)
 {
     constexpr int NB = llr_bits(NL);
-    __shared__ float rad[CMA_LLR_WAVES][2];                    // [wave][0: sum |tx|, 1: sum |ya|] over W_c
-    const int run = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int c0 = info_clamp_shift(shift_c[run * 2 + 0]), c1 = info_clamp_shift(shift_c[run * 2 + 1]);
-    const int q0 = info_clamp_shift(shift_q[run * 2 + 0]), q1 = info_clamp_shift(shift_q[run * 2 + 1]);
-    const int rc = r_c[run] & 1, rq = r_q[run] & 1;
-    const int endc = N - EDGE - max(abs(c0), abs(c1)), endq = N - EDGE - max(abs(q0), abs(q1));   // W_c = [EDGE, endc), kept = [EDGE, endq)
-    const float *yr = y + (size_t)run * 4 * N;
-    const __half *txr = txg + (size_t)run * 4 * N;
-
-    // ---- the radius walk: cma_epilogue_info_kernel's walk 1, expression for expression
-    float st = 0.f, sy = 0.f;
-    for (int n = tid; n < N; n += EPI_NT) {
-        if (n < EDGE || n >= endc) continue;
-#pragma unroll
-        for (int pp = 0; pp < 2; pp++) {
-            const int sp = (pp - rc) & 1, m = n + (pp ? c1 : c0);                                // 1 <= m < N - 1
-            const float ti = __half2float(txr[(size_t)(pp * 2 + 0) * N + n]), tq = __half2float(txr[(size_t)(pp * 2 + 1) * N + n]);
-            const float yi = yr[(size_t)(sp * 2 + 0) * N + m], yq = yr[(size_t)(sp * 2 + 1) * N + m];
-            st += sqrtf(fmaf(ti, ti, tq * tq));
-            sy += sqrtf(fmaf(yi, yi, yq * yq));
-        }
-    }
-    st = wave_sum_dpp(st);
-    sy = wave_sum_dpp(sy);
-    if (lane == 0) { rad[w][0] = st; rad[w][1] = sy; }
-    __syncthreads();
-    st = sy = 0.f;
-    for (int k = 0; k < CMA_LLR_WAVES; k++) { st += rad[k][0]; sy += rad[k][1]; }
-    const bool degenerate = sy == 0.f;                         // no radius, no normalisation: the run kept nothing
-    const float fac = st / sy;
+    __shared__ float rad[CMA_LLR_WAVES][2];                    // cma_radius_factor's scratch
+    const int run = blockIdx.x, tid = threadIdx.x;
+    const CmaFrame f(run, N, y, txg, shift_c, r_c, shift_q, r_q);
+    bool degenerate;                                           // no radius, no normalisation: the run kept nothing
+    const float fac = cma_radius_factor<CMA_LLR_WAVES>(f, rad, tid, degenerate);
 
     // ---- the elementwise pass of output polarisation p (grid.y = 2: this workgroup's one; grid.y = 1: both in turn)
     for (int p = blockIdx.y; p < 2; p += gridDim.y) {
-        const int pp = (p - rq) & 1, sft = p ? q1 : q0;            // stage q: row p comes from aligned row p - r_q, out[n] = in[n + shift_q[p]]
-        const int sp = (pp - rc) & 1, sfc = pp ? c1 : c0;          // stage c: aligned row p' comes from row p' - r_c of y, rolled by shift_c[p'] (wrapping)
-        const float *yI = yr + (size_t)(sp * 2) * N, *yQ = yI + N;
-        const float nusc = nu_sc[run];
-        const float i2v = 0.5f / var[run * 2 + pp];                // the demapper of the stage-c aligned polarisation, as in the epilogue
+        const float *yI = f.y_row(p), *yQ = yI + N;
         float amp[NL], pen[NL];
-#pragma unroll
-        for (int i = 0; i < NL; i++) { amp[i] = amp_g[i]; pen[i] = nusc * (amp[i] * amp[i]); }
+        const float i2v = info_demap_setup<NL>(amp_g, nu_sc, var, run, f.aligned_row(p), amp, pen);   // the demapper of the stage-c aligned polarisation
         const int h = hyp[run * 2 + p] & 7;
         float *dst = llr + ((size_t)run * 2 + p) * (2 * NB) * N;
         for (int n = tid; n < N; n += EPI_NT) {
             float out[2 * NB];
 #pragma unroll
             for (int i = 0; i < 2 * NB; i++) out[i] = 0.f;         // an erasure
-            if (!degenerate && n >= EDGE && n < endq) {
-                const int m = n + sft;                             // index in the stage-c aligned sequence, 1 <= m < N - 1
-                int ms = m + sfc;                                  // index in y: -9 <= ms < N + 9, one wrap at most (N >= 43)
-                if (ms >= N) ms -= N;
-                if (ms < 0) ms += N;
-                const float g = (m >= EDGE && m < endc) ? fac : 1.0f;  // scaled exactly where the aligned index lies in W_c
+            if (!degenerate && f.kept(n)) {
+                float g;
+                const int ms = f.source(p, n, fac, g);
                 float v[2][NL];
                 info_demap_log2<NL>(yI[ms] * g, amp, pen, i2v, v[0]);
                 info_demap_log2<NL>(yQ[ms] * g, amp, pen, i2v, v[1]);
@@ -112,7 +79,7 @@ extern "C" int vaeq_cma_epilogue_llr(int32_t R, int64_t N, int32_t n_lev, const 
 {
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!y || !tx_f16 || !amp || !var || !nu_sc || !shift_c || !r_c || !shift_q || !r_q || !hyp || !llr) return VAEQ_ERR_NULL;
-    if (R < 0 || N < 2 * vaeq::EDGE + vaeq::N_SHIFT || N > 0x3fffffff) return VAEQ_ERR_SHAPE;
+    if (!vaeq::epi_frame_shape_ok(R, N, 0)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *tx = reinterpret_cast<const __half *>(tx_f16);
     return vaeq::dispatch_nlev(n_lev, [&](auto nl) {

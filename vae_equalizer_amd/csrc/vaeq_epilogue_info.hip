@@ -12,8 +12,9 @@
 // every hypothesis is then a selection among (axis, level in {t_I, n-1-t_I, t_Q, n-1-t_Q}).
 // Integer counts are exact; float sums run per thread in symbol order, then over the wave's lanes (DPP, fixed order), then over the four waves
 // in order: two calls give identical bits.
-// This file holds the kernel's addressing (KeepWalk, the roll and the polarisation exchange) and how a symbol's v is loaded or demapped; the
-// per-symbol body and the tail are vaeq_info.h's (info_symbol<NL, YMODE, 8>, info_finish), shared with vaeq_awgn_info.hip and vaeq_cma_info.hip.
+// This file holds the walk over a thread's symbols (KeepWalk), the accumulation and the three lines of the demapper's constants; the alignment,
+// the q-mode load and the demapper's exponent are vaeq_info.h's (InfoAlign, info_load_q, info_demap_log2), the text vaeq_epilogue_llr.hip runs,
+// and so are the per-symbol body and the tail (info_symbol<NL, YMODE, 8>, info_finish), shared with vaeq_awgn_info.hip and vaeq_cma_info.hip.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -40,15 +41,13 @@ __global__ __launch_bounds__(EPI_NT) void dp_epilogue_info_kernel(int N, int bat
 {
     __shared__ InfoShared<8, INFO_WAVES> sh;
     const int run = blockIdx.x, p = blockIdx.y, tid = threadIdx.x;
-    // the alignment the epilogue found (11 <= n, |shift| <= 10, and the window ends 11 + max|shift| before the row does)
-    const int s0 = info_clamp_shift(shift[run * 2 + 0]), s1 = info_clamp_shift(shift[run * 2 + 1]);
-    const int r = rflag[run] & 1, ms = max(abs(s0), abs(s1));
-    const int sp = (p - r) & 1, sft = p ? s1 : s0;             // roll(r, 0): row p comes from row p - r; roll(-shift): out[n] = in[n + shift]
+    const InfoAlign al(shift, rflag, run);
+    const int sp = al.sp(p), sft = al.sft(p);
     const __half *txI = txg + ((size_t)run * 4 + p * 2) * N, *txQ = txI + N;
     const float *src = YMODE ? y + ((size_t)run * 4 + sp * 2) * N : q + ((size_t)run * 4 + sp * 2) * NL * N;
     float amp[NL], pen[NL];
     float i2v = 0.f;
-    if constexpr (YMODE) {
+    if constexpr (YMODE) {                                     // info_demap_setup's lines (vaeq_info.h says why they stand here)
         const float nusc = nu_sc[run];
         i2v = 0.5f / var[run * 2 + sp];                        // the demapper of the RECEIVED polarisation made this row's q
 #pragma unroll
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(EPI_NT) void dp_epilogue_info_kernel(int N, int bat
 #pragma unroll
     for (int i = 0; i < 8; i++) se[i] = be[i] = 0;
 
-    KeepWalk kw(tid, N, batch_len, s0, ms);
+    KeepWalk kw(tid, N, batch_len, al.s0, al.ms);
     for (int n = tid; n < N; n += EPI_NT, kw.next()) {
         const int m = n + sft;
         if (!kw.keep(n) || m < 0 || m >= N) continue;
@@ -71,12 +70,8 @@ __global__ __launch_bounds__(EPI_NT) void dp_epilogue_info_kernel(int N, int bat
         float v[2][NL];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
-            if constexpr (YMODE) {
-                info_demap_log2<NL>(src[(size_t)c * N + m], amp, pen, i2v, v[c]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < NL; i++) v[c][i] = src[(size_t)(c * NL + i) * N + m];
-            }
+            if constexpr (YMODE) info_demap_log2<NL>(src[(size_t)c * N + m], amp, pen, i2v, v[c]);
+            else info_load_q<NL>(src, N, m, c, v[c]);
         }
         info_symbol<NL, YMODE, 8>(v, txi, txq, fs, se, be);
     }
@@ -93,7 +88,7 @@ extern "C" int vaeq_dp_epilogue_info(int32_t R, int64_t N, int32_t n_lev, int32_
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if ((q != nullptr) == (y != nullptr)) return VAEQ_ERR_NULL;                                  // exactly one source of posteriors
     if (!tx_f16 || !amp || !P || !shift || !rflag || !info || !counts || (y && (!var || !nu_sc))) return VAEQ_ERR_NULL;
-    if (R < 0 || N < 2 * vaeq::EDGE + vaeq::N_SHIFT || N > 0x3fffffff || batch_len < 0 || (batch_len > 0 && N % batch_len)) return VAEQ_ERR_SHAPE;
+    if (!vaeq::epi_frame_shape_ok(R, N, batch_len)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __half *tx = reinterpret_cast<const __half *>(tx_f16);
     return vaeq::dispatch_nlev(n_lev, [&](auto nl) {

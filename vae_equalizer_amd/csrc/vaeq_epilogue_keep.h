@@ -1,12 +1,20 @@
 // vaeq_epilogue_keep.h -- which symbols of a frame the per-frame epilogues keep: the per-minibatch cut and the frame-edge slice of
 // func_VAELE_DP_MQAM_shaping.py:73-79 (batch_len > 0) resp. func_VAEflex_DP_MQAM_shaping.py:72-84 (batch_len = 0) as index arithmetic.
-// Shared by vaeq_epilogue.hip (SER) and vaeq_epilogue_info.hip (GMI / achievable rate / BER): both see exactly the same window.
+// Shared by vaeq_epilogue.hip (SER), vaeq_epilogue_info.hip (GMI / achievable rate / BER) and vaeq_epilogue_llr.hip: all see exactly the same window.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace vaeq {
 
 constexpr int EPI_NT = 256, N_SHIFT = 21, HALF_SHIFT = 10, N_CUT = 10, EDGE = 11;
+
+// the frames the information-rate and LLR entry points of the DP and CMA epilogues take: long enough for both edges and the shift search, indices
+// in int32, and whole minibatches where there is a per-minibatch cut (the CMA frames have none: batch_len = 0)
+inline bool epi_frame_shape_ok(int32_t R, int64_t N, int32_t batch_len)
+{
+    return R >= 0 && N >= 2 * EDGE + N_SHIFT && N <= 0x3fffffff && batch_len >= 0 && (batch_len == 0 || N % batch_len == 0);
+}
 
 // symbols kept of every minibatch by the reference's slice [: batch_len - shift[0] - 10] (:73-77), with Python's slice semantics: an end past the
 // minibatch keeps all of it, an end of 0 keeps nothing, and a NEGATIVE end e (batch_len < shift[0] + 10, so only for batch_len < 20) counts from the

@@ -7,7 +7,8 @@
 // workgroup, tiles on grid.x and (run, polarisation) on grid.y -- 15 runs of 10 000 symbols are 1200 workgroups, as 8192 runs are 655 360.
 // A wave reads 64 consecutive floats of every row it needs (q-mode: 2 n_lev rows of q; y-mode: the two equalised samples, demapped again in
 // the log domain) and writes 64 consecutive floats of each of the 2 b planes.  No LDS, no reduction, no atomics: two calls give identical bits.
-// This file holds the addressing and how a symbol's v is loaded or demapped; the per-symbol body is vaeq_llr.h's.
+// This file holds the tiling, the erasures and the plane stores; the alignment, the q-mode load and the demapper are the text
+// dp_epilogue_info_kernel runs (vaeq_info.h: InfoAlign, info_load_q, info_demap_setup / info_demap_log2), the per-symbol body is vaeq_llr.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,30 +35,23 @@ __global__ __launch_bounds__(LLR_NT) void dp_epilogue_llr_kernel(long long R2, i
     for (long long rp = blockIdx.y; rp < R2; rp += gridDim.y) {      // (run, polarisation) pairs past the grid's y limit
         const size_t run = (size_t)(rp >> 1);
         const int p = (int)(rp & 1);
-        // the alignment the epilogue found, as dp_epilogue_info_kernel reads it
-        const int s0 = info_clamp_shift(shift[run * 2 + 0]), s1 = info_clamp_shift(shift[run * 2 + 1]);
-        const int r = rflag[run] & 1, ms = max(abs(s0), abs(s1));
-        const int sp = (p - r) & 1, sft = p ? s1 : s0;         // roll(r, 0): row p comes from row p - r; roll(-shift): out[n] = in[n + shift]
-        const int m = n + sft;
+        const InfoAlign al(shift, rflag, run);
+        const int sp = al.sp(p), m = n + al.sft(p);
         float out[2 * NB];
 #pragma unroll
         for (int i = 0; i < 2 * NB; i++) out[i] = 0.f;         // an erasure
-        if (epi_keep(n, N, batch_len, s0, ms) && m >= 0 && m < N) {
+        if (epi_keep(n, N, batch_len, al.s0, al.ms) && m >= 0 && m < N) {
             float v[2][NL];
             if constexpr (YMODE) {
                 const float *src = y + (run * 4 + sp * 2) * N;
-                const float nusc = nu_sc[run], i2v = 0.5f / var[run * 2 + sp];   // the demapper of the RECEIVED polarisation made this row's q
                 float amp[NL], pen[NL];
-#pragma unroll
-                for (int i = 0; i < NL; i++) { amp[i] = amp_g[i]; pen[i] = nusc * (amp[i] * amp[i]); }
+                const float i2v = info_demap_setup<NL>(amp_g, nu_sc, var, run, sp, amp, pen);   // the demapper of the RECEIVED polarisation made this row's q
 #pragma unroll
                 for (int c = 0; c < 2; c++) info_demap_log2<NL>(src[(size_t)c * N + m], amp, pen, i2v, v[c]);
             } else {
                 const float *src = q + (run * 4 + sp * 2) * NL * N;
 #pragma unroll
-                for (int c = 0; c < 2; c++)
-#pragma unroll
-                    for (int i = 0; i < NL; i++) v[c][i] = src[(size_t)(c * NL + i) * N + m];
+                for (int c = 0; c < 2; c++) info_load_q<NL>(src, N, m, c, v[c]);
             }
             llr_symbol<NL, YMODE>(v, hyp[rp] & 7, out);
         }
@@ -76,7 +70,7 @@ extern "C" int vaeq_dp_epilogue_llr(int32_t R, int64_t N, int32_t n_lev, int32_t
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if ((q != nullptr) == (y != nullptr)) return VAEQ_ERR_NULL;                                  // exactly one source of posteriors
     if (!amp || !shift || !rflag || !hyp || !llr || (y && (!var || !nu_sc))) return VAEQ_ERR_NULL;
-    if (R < 0 || N < 2 * vaeq::EDGE + vaeq::N_SHIFT || N > 0x3fffffff || batch_len < 0 || (batch_len > 0 && N % batch_len)) return VAEQ_ERR_SHAPE;
+    if (!vaeq::epi_frame_shape_ok(R, N, batch_len)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t R2 = 2 * (int64_t)R;
     const dim3 grid((unsigned)((N + vaeq::LLR_NT - 1) / vaeq::LLR_NT), (unsigned)(R2 < vaeq::LLR_GRID_Y ? R2 : vaeq::LLR_GRID_Y));

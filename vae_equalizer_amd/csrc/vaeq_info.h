@@ -1,8 +1,13 @@
-// vaeq_info.h -- what the three information-rate kernels share (vaeq_epilogue_info.hip: a DP frame; vaeq_awgn_info.hip: an AWGN validation frame;
-// vaeq_cma_info.hip: a frame of the constant-modulus DP baselines), which is the definition of their figures: the level of a TX sample and the
-// clamp of a shift, the per-symbol body info_symbol (argmax, bit-wise sets, the terms of every hypothesis, their accumulation) and the tail
-// info_finish (wave and workgroup sums, the winning hypothesis, the entropy, the K == 0 rule, the 3 + 4 outputs).  A kernel keeps its addressing,
-// its pre-pass, its early-out and the one or two lines that form v, the posteriors (q-mode) or their unnormalised log2 (y-mode) of one symbol.
+// vaeq_info.h -- what the information-rate kernels and their LLR siblings share (vaeq_epilogue_info / _llr.hip: a DP frame; vaeq_awgn_info /
+// _llr.hip: an AWGN validation frame; vaeq_cma_info / _llr.hip: a frame of the constant-modulus DP baselines; vaeq_awgn_track_info / _llr.hip: a
+// soft sequence of the AWGN baselines).  An LLR kernel reports the LLRs of the posteriors whose GMI its sibling reports only if both see the same
+// symbols and the same floats, so everything that decides either is written once, here: the clamp of a shift, the DP alignment (InfoAlign), the
+// CMA frame with its radius walk and two-stage addressing (CmaFrame, cma_radius_factor), the q-mode load and both demappers' exponents
+// (info_load_q, info_demap_setup / info_demap_log2, info_awgn_log2); vaeq_awgn_eval.h holds the AWGN family's window and pre-passes.  The
+// information-rate kernels' own definition follows: the level of a TX sample, the per-symbol body info_symbol (argmax, bit-wise sets, the terms
+// of every hypothesis, their accumulation) and the tail info_finish (wave and workgroup sums, the winning hypothesis, the entropy, the K == 0
+// rule, the 3 + 4 outputs); vaeq_llr.h holds the LLR body.
+// A kernel keeps its launch shape, its early-out or plane stores and what is truly its own (KeepWalk, the tail calls, the split grid).
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -38,8 +43,36 @@ __device__ __forceinline__ int info_tx_level(__half tx)                     // t
 }
 // an alignment clamped to what the epilogues can find, so that a kept symbol's partner n + shift never leaves the row
 __device__ __forceinline__ int info_clamp_shift(int s) { return min(max(s, -HALF_SHIFT), HALF_SHIFT); }
-// y-mode of the DP soft demapper: log2 of the unnormalised posterior of sample yv (soft_demap<NLEV>'s exponent, vaeq_common.h), pen[i] = nu_sc a_i^2,
-// i2v = 1 / (2 var)
+// the alignment a DP epilogue found for a run (11 <= n, |shift| <= 10, and the window ends 11 + max|shift| before the row does)
+struct InfoAlign {
+    int s0, s1, r, ms;
+    template <class Run>                      // (an int in the one kernel, a size_t in the other: the index arithmetic stays the caller's)
+    __device__ __forceinline__ InfoAlign(const int32_t *__restrict__ shift, const int32_t *__restrict__ rflag, Run run)
+        : s0(info_clamp_shift(shift[run * 2 + 0])), s1(info_clamp_shift(shift[run * 2 + 1])), r(rflag[run] & 1), ms(max(abs(s0), abs(s1))) {}
+    __device__ __forceinline__ int sp(int p) const { return (p - r) & 1; }   // roll(r, 0): row p comes from row p - r
+    __device__ __forceinline__ int sft(int p) const { return p ? s1 : s0; }  // roll(-shift): out[n] = in[n + shift]
+};
+
+// q-mode: the stored posteriors of axis c of sample m, src = the 2 NL rows [axis][level][N] of the received polarisation
+template <int NL>
+__device__ __forceinline__ void info_load_q(const float *__restrict__ src, int N, int m, int c, float (&v)[NL])
+{
+#pragma unroll
+    for (int i = 0; i < NL; i++) v[i] = src[(size_t)(c * NL + i) * N + m];
+}
+// y-mode of the DP soft demapper: the constants of run `run` whose posteriors polarisation `row` of var made -- amp[i], pen[i] = nu_sc a_i^2 and,
+// returned, i2v = 1 / (2 var) ...  (dp_epilogue_info_kernel alone states these three lines itself: called from there, whatever the order of the
+// loads and the type of run, the function moved that kernel's y-mode schedule and cost it 2.3 %)
+template <int NL>
+__device__ __forceinline__ float info_demap_setup(const float *__restrict__ amp_g, const float *__restrict__ nu_sc, const float *__restrict__ var,
+                                                  size_t run, int row, float (&amp)[NL], float (&pen)[NL])
+{
+    const float nusc = nu_sc[run];
+#pragma unroll
+    for (int i = 0; i < NL; i++) { amp[i] = amp_g[i]; pen[i] = nusc * (amp[i] * amp[i]); }
+    return 0.5f / var[run * 2 + row];
+}
+// ... and log2 of the unnormalised posterior of sample yv (soft_demap<NLEV>'s exponent, vaeq_common.h)
 template <int NL>
 __device__ __forceinline__ void info_demap_log2(float yv, const float (&amp)[NL], const float (&pen)[NL], float i2v, float (&v)[NL])
 {
@@ -48,6 +81,80 @@ __device__ __forceinline__ void info_demap_log2(float yv, const float (&amp)[NL]
         const float dd = yv - amp[i];
         v[i] = -(dd * dd * i2v + pen[i]) * 1.4426950408889634f;
     }
+}
+// y-mode of the AWGN reference's own demapper (func_VAELE_MQAM_shaping.py:229: -(y - a_i)^2 / var per axis, no 1/2, no prior term): log2 of the
+// unnormalised posterior of the scaled sample yv, ivl = log2 e / var
+constexpr float INFO_LOG2E = 1.4426950408889634f;
+template <int NL>
+__device__ __forceinline__ void info_awgn_log2(float yv, const float (&amp)[NL], float ivl, float (&v)[NL])
+{
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        const float dd = yv - amp[i];
+        v[i] = -(dd * dd) * ivl;
+    }
+}
+
+// One frame of the constant-modulus DP baselines as vaeq_cma_epilogue aligned it, rebuilt from the raw y and the four alignment outputs:
+//   stage c:  ya[p'][c][m] = y[(p' - r_c) & 1][c][(m + shift_c[p']) mod N],   W_c = [EDGE, endc)
+//   stage q:  kept symbol n in [EDGE, endq) of output polarisation p reads ya[p' = (p - r_q) & 1][:, m = n + shift_q[p]]
+// Both alignments are clamped to what the epilogue can find: with 11 <= n and a window that ends 11 + max|shift| before the row does, n + shift
+// stays inside [1, N - 1) in either stage; only the stage-c roll of a sample outside W_c can wrap around the frame.
+struct CmaFrame {
+    int N, c0, c1, q0, q1, rc, rq, endc, endq;
+    const float *yr;                          // y[run]: [2][2][N]
+    const __half *txr;                        // tx[run]: [2][2][N]
+    __device__ __forceinline__ CmaFrame(int run, int N_, const float *__restrict__ y, const __half *__restrict__ txg,
+                                        const int32_t *__restrict__ shift_c, const int32_t *__restrict__ r_c,
+                                        const int32_t *__restrict__ shift_q, const int32_t *__restrict__ r_q)
+        : N(N_), c0(info_clamp_shift(shift_c[run * 2 + 0])), c1(info_clamp_shift(shift_c[run * 2 + 1])),
+          q0(info_clamp_shift(shift_q[run * 2 + 0])), q1(info_clamp_shift(shift_q[run * 2 + 1])), rc(r_c[run] & 1), rq(r_q[run] & 1),
+          endc(N_ - EDGE - max(abs(c0), abs(c1))), endq(N_ - EDGE - max(abs(q0), abs(q1))), yr(y + (size_t)run * 4 * N_),
+          txr(txg + (size_t)run * 4 * N_) {}
+    __device__ __forceinline__ bool kept(int n) const { return n >= EDGE && n < endq; }
+    // the source of output polarisation p: pp, the stage-c aligned row it comes from (whose demapper made its posteriors), and that row's I row in y
+    __device__ __forceinline__ int aligned_row(int p) const { return (p - rq) & 1; }
+    __device__ __forceinline__ const float *y_row(int p) const { return yr + (size_t)(((aligned_row(p) - rc) & 1) * 2) * N; }
+    // kept symbol n of output polarisation p -> its index ms in y_row(p), and g = fac exactly where its stage-c aligned index lies in W_c, else 1
+    __device__ __forceinline__ int source(int p, int n, float fac, float &g) const
+    {
+        const int m = n + (p ? q1 : q0);                       // index in the stage-c aligned sequence, 1 <= m < N - 1
+        int ms = m + (aligned_row(p) ? c1 : c0);               // index in y: -9 <= ms < N + 9, one wrap at most (N >= 43)
+        if (ms >= N) ms -= N;
+        if (ms < 0) ms += N;
+        g = (m >= EDGE && m < endc) ? fac : 1.0f;
+        return ms;
+    }
+};
+
+// fac = sum_{p', m in W_c} |tx[p'][:, m]| / sum_{p', m in W_c} |ya[p'][:, m]|, the mean radius of TX over that of the stage-c aligned output, both
+// polarisations (shared_funcs.py:242): per thread at stride EPI_NT, over the wave's lanes (DPP, fixed order), over the WAVES waves in order.  It
+// multiplies every sample of W_c, so both kernels of the pair -- and on a split grid both workgroups of a run -- form it here, the same float.
+// rad: [WAVES][2] floats of LDS.  Returns fac in every thread; degenerate: sum |ya| == 0, no radius, no normalisation -- the run keeps nothing.
+template <int WAVES>
+__device__ __forceinline__ float cma_radius_factor(const CmaFrame &f, float (*rad)[2], int tid, bool &degenerate)
+{
+    const int N = f.N;
+    float st = 0.f, sy = 0.f;
+    for (int n = tid; n < N; n += EPI_NT) {
+        if (n < EDGE || n >= f.endc) continue;
+#pragma unroll
+        for (int pp = 0; pp < 2; pp++) {
+            const int sp = (pp - f.rc) & 1, m = n + (pp ? f.c1 : f.c0);                          // 1 <= m < N - 1
+            const float ti = __half2float(f.txr[(size_t)(pp * 2 + 0) * N + n]), tq = __half2float(f.txr[(size_t)(pp * 2 + 1) * N + n]);
+            const float yi = f.yr[(size_t)(sp * 2 + 0) * N + m], yq = f.yr[(size_t)(sp * 2 + 1) * N + m];
+            st += sqrtf(fmaf(ti, ti, tq * tq));
+            sy += sqrtf(fmaf(yi, yi, yq * yq));
+        }
+    }
+    st = wave_sum_dpp(st);
+    sy = wave_sum_dpp(sy);
+    if ((tid & 63) == 0) { rad[tid >> 6][0] = st; rad[tid >> 6][1] = sy; }
+    __syncthreads();
+    st = sy = 0.f;
+    for (int k = 0; k < WAVES; k++) { st += rad[k][0]; sy += rad[k][1]; }
+    degenerate = sy == 0.f;
+    return st / sy;
 }
 
 // One kept symbol, all NH hypotheses.  v[c][i]: axis c, level i -- q-mode the posterior q, y-mode its unnormalised log2; txI / txQ: the transmitted

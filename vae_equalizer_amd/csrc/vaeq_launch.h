@@ -25,6 +25,15 @@ inline bool loss_shape_ok(int64_t B, int64_t sps, int64_t M)
     return B > 0 && fir_shape_ok(sps, M) && B * sps - 2 * (M / 2) > 0 && B > 2 * (M / 2);
 }
 
+// a batch of AWGN validation frames of N symbols (vaeq_awgn_info, vaeq_awgn_llr): indices in int32 with room for a shift
+inline bool awgn_frame_shape_ok(int32_t R, int64_t N) { return R >= 0 && N >= 1 && N <= 0x3fffffff; }
+
+// ... and of soft sequences of Nz samples against Nd TX symbols (vaeq_awgn_track_info, vaeq_awgn_track_llr): the LMMSE output is one sample longer
+inline bool track_shape_ok(int32_t R, int64_t Nz, int64_t Nd, int32_t edge, int32_t interleaved)
+{
+    return awgn_frame_shape_ok(R, Nz) && Nd >= 1 && (Nz == Nd || Nz == Nd + 1) && edge >= 0 && (interleaved == 0 || interleaved == 1);
+}
+
 // f(std::integral_constant<int, n_lev>{}) for the three supported level counts (4-/16-/64-QAM), VAEQ_ERR_SHAPE otherwise; the result has f's type
 // (int for a launch, int64_t for an occupancy query)
 template <class F>

@@ -1,11 +1,15 @@
-// vaeq_llr.h -- the per-symbol body of the two LLR kernels (vaeq_epilogue_llr.hip: a DP frame; vaeq_awgn_llr.hip: an AWGN validation frame): the
+// vaeq_llr.h -- the per-symbol body of the four LLR kernels (vaeq_epilogue_llr.hip: a DP frame; vaeq_awgn_llr.hip: an AWGN validation frame;
+// vaeq_cma_llr.hip: a frame of the constant-modulus DP baselines; vaeq_awgn_track_llr.hip: a soft sequence of the AWGN baselines): the
 // a-posteriori log-likelihood ratio of every label bit of one received symbol, and which of them is which transmitted bit under a hypothesis.
+// What decides v -- window, alignment, pre-pass, load, demapper -- is vaeq_info.h's and vaeq_awgn_eval.h's, the text the information-rate
+// siblings run.
 //
 // Level i of an axis carries the label g(i) = i ^ (i >> 1) (info_gray), b = log2 n_lev bits, bit b-1 the top one.  For a received axis c
 //     lam[c][k] = ln 2 (L[c][k][0] - L[c][k][1])      nats, positive = bit 0, priors included
-// with L[c][k][s] the log2 of the posterior mass of the levels whose label bit k is s -- vaeq_info.h's L of info_symbol, restated here because
-// reshaping that body costs the information-rate kernels 1-2 %; tests/test_epilogue_llr_gpu.py and
-// tests/test_awgn_llr_gpu.py pin the restatement to the original through the GMI, which is an exact function of the LLRs.
+// with L[c][k][s] the log2 of the posterior mass of the levels whose label bit k is s -- vaeq_info.h's L of info_symbol.  These set sums are the
+// one thing the pairs still state twice: with both bodies on one function every bit stayed, but the information-rate kernels' y-mode ran 0.4-3 %
+// slower and one launch left the parent's range.  tests/test_llr_bits_gpu.py and tests/test_info_bits_gpu.py pin each copy's
+// bits, and the LLR tests pin one to the other through the GMI, which is an exact function of the LLRs.
 //   q-mode: info_log2 of the two set sums, added in ascending i; an exact 0 costs 126 bit, so every LLR is finite.
 //   y-mode: v is the unnormalised log2 posterior; each set is a log-sum-exp around its own maximum, so no set underflows.
 // Hypothesis h = 4 flip + rot (rot: 0, pi, pi/2, 3 pi/2, as in info_symbol) says where the transmitted axes are found:

@@ -50,6 +50,65 @@ def _f16(data):
     return data.to(torch.float16).contiguous()
 
 
+def _posterior_source(who, q, y, amp_levels, lead, data):
+    """What the information-rate and LLR functions of a DP frame (lead = (2,)) and of an AWGN validation frame (lead = ()) take: exactly one of
+    q[R,*lead,2n,N] and y[R,*lead,2,N], and data[R,*lead,2,N] where the function reads it (None otherwise) ->
+    (dev, R, N, n, amp[n], q or None, y or None, data fp16 or None), contiguous."""
+    if (q is None) == (y is None):
+        raise ValueError(f"{who} takes exactly one of q and y")
+    src = q if y is None else y
+    dev, R, N = src.device, src.shape[0], src.shape[-1]
+    amp = _amp(amp_levels, dev)
+    n = amp.numel()
+    if tuple(src.shape) != (R, *lead, 2 * n if y is None else 2, N) or (data is not None and tuple(data.shape) != (R, *lead, 2, N)):
+        raise ValueError(f"expected q{[R, *lead, 2 * n, N]} or y{[R, *lead, 2, N]} and data{[R, *lead, 2, N]}, got {tuple(src.shape)}"
+                         + ("" if data is None else f", {tuple(data.shape)}"))
+    src = src.contiguous()
+    return dev, R, N, n, amp, (src if y is None else None), (src if y is not None else None), None if data is None else _f16(data)
+
+
+def _dp_frame(who, q, y, data, amp_levels, nu_sc, var, shift, r):
+    """The arguments dp_epilogue_info and dp_epilogue_llr share -> (dev, R, N, n, amp, q, y, data, var[R,2], nu_sc[R] (None in q-mode),
+    shift[R,2] i32, r[R] i32)."""
+    dev, R, N, n, amp, q, y, data = _posterior_source(who, q, y, amp_levels, (2,), data)
+    var_t, nu_t = (None, None) if y is None else _var_nu(var, nu_sc, R, dev)
+    return dev, R, N, n, amp, q, y, data, var_t, nu_t, _i32(shift, (R, 2), dev), _i32(r, R, dev)
+
+
+def _awgn_frame(who, q, y, data, amp_levels, amp_mean, var, shift):
+    """The arguments awgn_info and awgn_llr share -> (dev, R, N, n, amp, q, y, data, amp_mean[R], var[R] (None in q-mode), shift[R] i32)."""
+    dev, R, N, n, amp, q, y, data = _posterior_source(who, q, y, amp_levels, (), data)
+    am_t, var_t = (None, None) if y is None else (_f32(amp_mean, dev).expand(R).contiguous(), _f32(var, dev).expand(R).contiguous())
+    return dev, R, N, n, amp, q, y, data, am_t, var_t, _i32(shift, R, dev)
+
+
+def _cma_frame(y, data, amp_levels, nu_sc, var, shift_c, r_c, shift_q, r_q):
+    """The arguments cma_epilogue_info and cma_epilogue_llr share -> (dev, R, N, n, amp, y, data fp16, var[R,2], nu_sc[R], and the four alignment
+    outputs as int32: shift_c[R,2], r_c[R], shift_q[R,2], r_q[R])."""
+    dev, R, N = y.device, y.shape[0], y.shape[-1]
+    amp = _amp(amp_levels, dev)
+    if tuple(y.shape) != (R, 2, 2, N) or tuple(data.shape) != (R, 2, 2, N):
+        raise ValueError(f"expected y[R,2,2,N] and data[R,2,2,N], got {tuple(y.shape)}, {tuple(data.shape)}")
+    var_t, nu_t = _var_nu(var, nu_sc, R, dev)
+    return (dev, R, N, amp.numel(), amp, y.contiguous(), _f16(data), var_t, nu_t,
+            _i32(shift_c, (R, 2), dev), _i32(r_c, R, dev), _i32(shift_q, (R, 2), dev), _i32(r_q, R, dev))
+
+
+def _track(z, data, amp_levels, var, shift):
+    """The arguments awgn_track_info and awgn_track_llr share: z float [R,2,Nz] (planar) or complex [R,Nz] (interleaved: the layout follows from
+    the dtype), data[R,2,Nd] -> (dev, R, Nz, Nd, n, interleaved, amp, z float32, data fp16, var[R], shift[R] i32)."""
+    dev, R = z.device, z.shape[0]
+    amp = _amp(amp_levels, dev)
+    interleaved = z.is_complex()
+    if interleaved:
+        z = torch.view_as_real(z.to(torch.complex64).contiguous())
+    Nz, Nd = (z.shape[1] if interleaved else z.shape[-1]), data.shape[-1]
+    if tuple(z.shape) != ((R, Nz, 2) if interleaved else (R, 2, Nz)) or tuple(data.shape) != (R, 2, Nd):
+        raise ValueError(f"expected z[R,2,Nz] float or z[R,Nz] complex and data[R,2,Nd], got {tuple(z.shape)}, {tuple(data.shape)}")
+    return (dev, R, Nz, Nd, amp.numel(), interleaved, amp, z.float().contiguous(), _f16(data), _f32(var, dev).expand(R).contiguous(),
+            _i32(shift, R, dev))
+
+
 def _alignment_out(R, dev):
     """What an epilogue launch writes: SER[R,4] f32, shift[R,2,2] i32 and the exchange flags [R,2] i32 (stage q, then stage c)."""
     e = lambda *s, dtype=torch.int32: torch.empty(R, *s, dtype=dtype, device=dev)
@@ -527,23 +586,12 @@ def dp_epilogue_info(q=None, y=None, data=None, amp_levels=None, P=None, nu_sc=N
     data[R,2,2,N] fp16, P[R,n] (or [n]) the per-axis pmf, shift[R,2] / r[R] = dp_epilogue's shift_q / r_q ->
     dict(AIR[R,2], GMI[R,2], NGMI[R,2], BER[R,2] f32 (NaN where nothing is kept); kept, sym_err, bit_err, hyp [R,2] int64).
     AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
-    if (q is None) == (y is None):
-        raise ValueError("dp_epilogue_info takes exactly one of q and y")
-    src = q if y is None else y
-    dev, R, N = src.device, src.shape[0], src.shape[-1]
-    amp = _amp(amp_levels, dev)
-    n = amp.numel()
+    dev, R, N, n, amp, q, y, data, var_t, nu_t, shift, r = _dp_frame("dp_epilogue_info", q, y, data, amp_levels, nu_sc, var, shift, r)
     P = _pmf(P, R, n, dev)
-    var_t = nu_t = None
-    if y is not None:
-        var_t, nu_t = _var_nu(var, nu_sc, R, dev)
-    src = src.contiguous()
-    data = _f16(data)
-    shift, r = _i32(shift, (R, 2), dev), _i32(r, R, dev)
     info = torch.empty(R, 2, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(R, 2, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_dp_epilogue_info(R, N, n, int(batch_len or 0), nat.ptr(src if y is None else None), nat.ptr(src if y is not None else None),
+        nat.check(nat.lib().vaeq_dp_epilogue_info(R, N, n, int(batch_len or 0), nat.ptr(q), nat.ptr(y),
                                                   nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(P), nat.ptr(var_t), nat.ptr(nu_t),
                                                   nat.ptr(shift, torch.int32), nat.ptr(r, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32),
                                                   nat.current_stream(dev)), "vaeq_dp_epilogue_info")
@@ -557,26 +605,12 @@ def awgn_info(q=None, y=None, data=None, amp_levels=None, P=None, amp_mean=None,
     P[R,n] (or [n]) the per-axis pmf, shift[R] ->
     dict(AIR[R], GMI[R], NGMI[R], BER[R] f32 (NaN where nothing is kept); kept, sym_err, bit_err, hyp [R] int64).
     AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
-    if (q is None) == (y is None):
-        raise ValueError("awgn_info takes exactly one of q and y")
-    src = q if y is None else y
-    dev, R, N = src.device, src.shape[0], src.shape[-1]
-    amp = _amp(amp_levels, dev)
-    n = amp.numel()
-    if tuple(src.shape) != (R, 2 * n if y is None else 2, N) or tuple(data.shape) != (R, 2, N):
-        raise ValueError(f"expected q[R,{2 * n},N] or y[R,2,N] and data[R,2,N], got {tuple(src.shape)}, {tuple(data.shape)}")
+    dev, R, N, n, amp, q, y, data, am_t, var_t, shift = _awgn_frame("awgn_info", q, y, data, amp_levels, amp_mean, var, shift)
     P = _pmf(P, R, n, dev)
-    am_t = var_t = None
-    if y is not None:
-        am_t = _f32(amp_mean, dev).expand(R).contiguous()
-        var_t = _f32(var, dev).expand(R).contiguous()
-    src = src.contiguous()
-    data = _f16(data)
-    shift = _i32(shift, R, dev)
     info = torch.empty(R, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(R, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_awgn_info(R, N, n, nat.ptr(src if y is None else None), nat.ptr(src if y is not None else None),
+        nat.check(nat.lib().vaeq_awgn_info(R, N, n, nat.ptr(q), nat.ptr(y),
                                            nat.ptr(data, torch.float16), nat.ptr(amp), nat.ptr(P), nat.ptr(am_t), nat.ptr(var_t),
                                            nat.ptr(shift, torch.int32), nat.ptr(info), nat.ptr(counts, torch.int32), nat.current_stream(dev)),
                   "vaeq_awgn_info")
@@ -589,22 +623,11 @@ def dp_epilogue_llr(q=None, y=None, amp_levels=None, nu_sc=None, var=None, shift
     r_q, hyp[R,2] = dp_epilogue_info's hyp on the same alignment -> llr[R,2,2b,N] f32 in nats, positive = bit 0, b = log2 n: plane a b + k of
     polarisation p at TX index n is bit k (b-1 = the top bit of the Gray label i ^ (i >> 1)) of TX axis a (0 = I, 1 = Q), aligned with
     label_bits(data, n); the symbols dp_epilogue_info does not keep are erasures, +0.0."""
-    if (q is None) == (y is None):
-        raise ValueError("dp_epilogue_llr takes exactly one of q and y")
-    src = q if y is None else y
-    dev, R, N = src.device, src.shape[0], src.shape[-1]
-    amp = _amp(amp_levels, dev)
-    n = amp.numel()
-    if tuple(src.shape) != (R, 2, 2 * n if y is None else 2, N):
-        raise ValueError(f"expected q[R,2,{2 * n},N] or y[R,2,2,N], got {tuple(src.shape)}")
-    var_t = nu_t = None
-    if y is not None:
-        var_t, nu_t = _var_nu(var, nu_sc, R, dev)
-    src = src.contiguous()
-    shift, r, hyp = _i32(shift, (R, 2), dev), _i32(r, R, dev), _i32(hyp, (R, 2), dev)
+    dev, R, N, n, amp, q, y, _, var_t, nu_t, shift, r = _dp_frame("dp_epilogue_llr", q, y, None, amp_levels, nu_sc, var, shift, r)
+    hyp = _i32(hyp, (R, 2), dev)
     llr = torch.empty(R, 2, 2 * (n.bit_length() - 1), N, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_dp_epilogue_llr(R, N, n, int(batch_len or 0), nat.ptr(src if y is None else None), nat.ptr(src if y is not None else None),
+        nat.check(nat.lib().vaeq_dp_epilogue_llr(R, N, n, int(batch_len or 0), nat.ptr(q), nat.ptr(y),
                                                  nat.ptr(amp), nat.ptr(var_t), nat.ptr(nu_t), nat.ptr(shift, torch.int32), nat.ptr(r, torch.int32),
                                                  nat.ptr(hyp, torch.int32), nat.ptr(llr), nat.current_stream(dev)), "vaeq_dp_epilogue_llr")
     return llr
@@ -615,23 +638,11 @@ def awgn_llr(q=None, y=None, amp_levels=None, amp_mean=None, var=None, shift=Non
     y[R,2,N] (the validation's un-normalised output; the VAE-LE demapper's posteriors are recomputed from amp_mean[R] / var[R] as awgn_info
     does), shift[R], hyp[R] = awgn_info's hyp on the same shift -> llr[R,2b,N] f32 in nats, positive = bit 0: plane a b + k at TX index n is bit
     k of TX axis a, aligned with label_bits(data, n); everything outside TX indices [11, N - 11 - shift) is an erasure, +0.0."""
-    if (q is None) == (y is None):
-        raise ValueError("awgn_llr takes exactly one of q and y")
-    src = q if y is None else y
-    dev, R, N = src.device, src.shape[0], src.shape[-1]
-    amp = _amp(amp_levels, dev)
-    n = amp.numel()
-    if tuple(src.shape) != (R, 2 * n if y is None else 2, N):
-        raise ValueError(f"expected q[R,{2 * n},N] or y[R,2,N], got {tuple(src.shape)}")
-    am_t = var_t = None
-    if y is not None:
-        am_t = _f32(amp_mean, dev).expand(R).contiguous()
-        var_t = _f32(var, dev).expand(R).contiguous()
-    src = src.contiguous()
-    shift, hyp = _i32(shift, R, dev), _i32(hyp, R, dev)
+    dev, R, N, n, amp, q, y, _, am_t, var_t, shift = _awgn_frame("awgn_llr", q, y, None, amp_levels, amp_mean, var, shift)
+    hyp = _i32(hyp, R, dev)
     llr = torch.empty(R, 2 * (n.bit_length() - 1), N, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_awgn_llr(R, N, n, nat.ptr(src if y is None else None), nat.ptr(src if y is not None else None), nat.ptr(amp),
+        nat.check(nat.lib().vaeq_awgn_llr(R, N, n, nat.ptr(q), nat.ptr(y), nat.ptr(amp),
                                           nat.ptr(am_t), nat.ptr(var_t), nat.ptr(shift, torch.int32), nat.ptr(hyp, torch.int32), nat.ptr(llr),
                                           nat.current_stream(dev)), "vaeq_awgn_llr")
     return llr
@@ -749,16 +760,8 @@ def cma_epilogue_info(y, data, amp_levels, P, nu_sc, var, shift_c, r_c, shift_q,
     whose kept window carries the mean-radius normalisation, recomputed in the log domain (neither that sequence nor q exists in memory) ->
     dict(AIR[R,2], GMI[R,2], NGMI[R,2], BER[R,2] f32 (NaN for a run without a normalisation); kept, sym_err, bit_err, hyp [R,2] int64).
     AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
-    dev, R, N = y.device, y.shape[0], y.shape[-1]
-    amp = _amp(amp_levels, dev)
-    n = amp.numel()
-    if tuple(y.shape) != (R, 2, 2, N) or tuple(data.shape) != (R, 2, 2, N):
-        raise ValueError(f"expected y[R,2,2,N] and data[R,2,2,N], got {tuple(y.shape)}, {tuple(data.shape)}")
+    dev, R, N, n, amp, y, data, var_t, nu_t, sc, rc, sq, rq = _cma_frame(y, data, amp_levels, nu_sc, var, shift_c, r_c, shift_q, r_q)
     P = _pmf(P, R, n, dev)
-    var_t, nu_t = _var_nu(var, nu_sc, R, dev)
-    y = y.contiguous()
-    data = _f16(data)
-    sc, rc, sq, rq = _i32(shift_c, (R, 2), dev), _i32(r_c, R, dev), _i32(shift_q, (R, 2), dev), _i32(r_q, R, dev)
     info = torch.empty(R, 2, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(R, 2, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -775,15 +778,7 @@ def cma_epilogue_llr(y, data, amp_levels, nu_sc, var, shift_c, r_c, shift_q, r_q
     cma_epilogue_info got them, hyp[R,2] = that call's hyp -> llr[R,2,2b,N] f32 in nats, positive = bit 0, b = log2 n: plane a b + k of output
     polarisation p at TX index n is bit k of TX axis a, aligned with label_bits(data, n).  The posteriors are cma_epilogue_info's; the symbols
     it does not keep are erasures, +0.0, and a run without a normalisation is all zeros."""
-    dev, R, N = y.device, y.shape[0], y.shape[-1]
-    amp = _amp(amp_levels, dev)
-    n = amp.numel()
-    if tuple(y.shape) != (R, 2, 2, N) or tuple(data.shape) != (R, 2, 2, N):
-        raise ValueError(f"expected y[R,2,2,N] and data[R,2,2,N], got {tuple(y.shape)}, {tuple(data.shape)}")
-    var_t, nu_t = _var_nu(var, nu_sc, R, dev)
-    y = y.contiguous()
-    data = _f16(data)
-    sc, rc, sq, rq = _i32(shift_c, (R, 2), dev), _i32(r_c, R, dev), _i32(shift_q, (R, 2), dev), _i32(r_q, R, dev)
+    dev, R, N, n, amp, y, data, var_t, nu_t, sc, rc, sq, rq = _cma_frame(y, data, amp_levels, nu_sc, var, shift_c, r_c, shift_q, r_q)
     hyp = _i32(hyp, (R, 2), dev)
     llr = torch.empty(R, 2, 2 * (n.bit_length() - 1), N, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -979,20 +974,8 @@ def awgn_track_info(z, data, amp_levels, P, var, shift, edge=11):
     (10^(-SNR/10) in the host layers), shift[R] the validator's ->
     dict(AIR[R], GMI[R], NGMI[R], BER[R] f32 (NaN where nothing is kept or z is zero); kept, sym_err, bit_err, hyp [R] int64).
     AIR and GMI in bit per 2-D symbol; NGMI = 1 - (2 H - GMI) / (2 log2 n)."""
-    dev, R = z.device, z.shape[0]
-    amp = _amp(amp_levels, dev)
-    n = amp.numel()
-    interleaved = z.is_complex()
-    if interleaved:
-        z = torch.view_as_real(z.to(torch.complex64).contiguous())
-    Nz, Nd = (z.shape[1] if interleaved else z.shape[-1]), data.shape[-1]
-    if tuple(z.shape) != ((R, Nz, 2) if interleaved else (R, 2, Nz)) or tuple(data.shape) != (R, 2, Nd):
-        raise ValueError(f"expected z[R,2,Nz] float or z[R,Nz] complex and data[R,2,Nd], got {tuple(z.shape)}, {tuple(data.shape)}")
+    dev, R, Nz, Nd, n, interleaved, amp, z, data, var_t, shift = _track(z, data, amp_levels, var, shift)
     P = _pmf(P, R, n, dev)
-    var_t = _f32(var, dev).expand(R).contiguous()
-    z = z.float().contiguous()
-    data = _f16(data)
-    shift = _i32(shift, R, dev)
     info = torch.empty(R, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(R, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -1008,19 +991,8 @@ def awgn_track_llr(z, data, amp_levels, var, shift, hyp, edge=11):
     for the normalisation only), hyp[R] = that call's hyp -> llr[R,2b,Nd] f32 in nats, positive = bit 0: plane a b + k at TX index edge + j,
     j < Nd - 2 edge - shift, is bit k of TX axis a of sample edge + shift + j, aligned with label_bits(data, n); everything else is an erasure,
     +0.0, and a run whose window is empty or whose slice is zero is all zeros."""
-    dev, R = z.device, z.shape[0]
-    amp = _amp(amp_levels, dev)
-    n = amp.numel()
-    interleaved = z.is_complex()
-    if interleaved:
-        z = torch.view_as_real(z.to(torch.complex64).contiguous())
-    Nz, Nd = (z.shape[1] if interleaved else z.shape[-1]), data.shape[-1]
-    if tuple(z.shape) != ((R, Nz, 2) if interleaved else (R, 2, Nz)) or tuple(data.shape) != (R, 2, Nd):
-        raise ValueError(f"expected z[R,2,Nz] float or z[R,Nz] complex and data[R,2,Nd], got {tuple(z.shape)}, {tuple(data.shape)}")
-    var_t = _f32(var, dev).expand(R).contiguous()
-    z = z.float().contiguous()
-    data = _f16(data)
-    shift, hyp = _i32(shift, R, dev), _i32(hyp, R, dev)
+    dev, R, Nz, Nd, n, interleaved, amp, z, data, var_t, shift = _track(z, data, amp_levels, var, shift)
+    hyp = _i32(hyp, R, dev)
     llr = torch.empty(R, 2 * (n.bit_length() - 1), Nd, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         nat.check(nat.lib().vaeq_awgn_track_llr(R, Nz, Nd, n, int(edge), int(interleaved), nat.ptr(z), nat.ptr(data, torch.float16), nat.ptr(amp),
