@@ -671,6 +671,20 @@ int vaeq_ldpc_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int
                      const float *llr, const int8_t *bits, float alpha, int32_t max_iter, int32_t *out, float *post, void *stream);
 int64_t vaeq_ldpc_lds_bytes(int32_t mb, int32_t nb, int32_t Z);
 
+/* vaeq_ldpc_decode behind a symbol interleaver over groups of `depth` codewords, so that a burst of bad symbols (the DFE's error propagation,
+ * a tracking transient at the head of a frame) is shared among the codewords of a group and does not fall on one of them.
+ * S = ceil(n / w) symbols per codeword: codewords are symbol-aligned here, not bit-packed.  Group k holds the codewords k depth ..
+ * min((k + 1) depth, C) - 1: D_k of them, depth except in a ragged last group.  Its base is symbol t0 + k depth S, and bit j of the codeword
+ * with local index d of group k is symbol base + (j / w) D_k + d, plane j % w.  When n % w != 0, the planes >= n - (S - 1) w of a codeword's
+ * last symbol belong to no codeword: they are never loaded into L and never counted in pre_err or erased.  depth == 1: symbol-aligned contiguous
+ * codewords; depth == C: symbol u of codeword c is symbol t0 + u C + c, every codeword spread over the whole used part of the frame.
+ * Everything else -- the code, the tensors, the algorithm and its float32 operation order, out[R][C][5] and post[R][C][n] in codeword order,
+ * the state in LDS -- is vaeq_ldpc_decode's.  The refusals are vaeq_ldpc_decode's too, in its order and all before any HIP call, but for:
+ * depth < 1 or depth > C is VAEQ_ERR_SHAPE, and the fit rule is t0 + C S > N is VAEQ_ERR_SHAPE. */
+int vaeq_ldpc_decode_il(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t mb, int32_t nb, int32_t Z,
+                        const int32_t *shifts_host, const float *llr, const int8_t *bits, float alpha, int32_t max_iter, int32_t *out, float *post,
+                        void *stream);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

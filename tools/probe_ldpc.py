@@ -2,7 +2,10 @@
 """Time vaeq_ldpc_decode (GPU) at the size of a sweep: --runs runs x the codewords of one --symbols-symbol DP 64-QAM frame (w = 12 planes) under
 array_code(4, 24, 211) (n = 5064, 20 256 edges), at three noise levels that take about 1, about 5 and all 20 iterations.
 
-    python tools/probe_ldpc.py [--runs 8192] [--symbols 10000] [--sigmas 0.3,0.53,0.8] [--rounds 5] [--out profiles/ldpc/probe.txt]
+    python tools/probe_ldpc.py [--runs 8192] [--symbols 10000] [--sigmas 0.3,0.53,0.8] [--rounds 5] [--depth D] [--out profiles/ldpc/probe.txt]
+
+--depth D times vaeq_ldpc_decode_il instead: the same decoder behind the symbol interleaver over groups of D codewords (codewords of whole symbols:
+23 of 422 symbols in the default frame, as many as the contiguous form packs into it).
 
 The LLRs are synthetic, generated on the device from a seed: random TX bits, llr = 2 y / sigma^2 of y = (1 - 2 b) + sigma noise (the inputs of
 tests/_ref_ldpc.py).  Per level, after a warm-up call, --rounds calls between device events (host wrapper + kernel): median / min / max, codewords/s
@@ -36,17 +39,20 @@ def main():
     ap.add_argument("--sigmas", default="0.3,0.53,0.8")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--max-iter", type=int, default=20)
+    ap.add_argument("--depth", type=int, default=None)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ldpc", "probe.txt"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
     code = engine.array_code(4, 24, 211)
     w, R, N = 12, a.runs, a.symbols
-    C_ = N * w // code.n
+    C_ = N * w // code.n if a.depth is None else N // -(-code.n // w)
+    kw = dict(max_iter=a.max_iter) if a.depth is None else dict(max_iter=a.max_iter, depth=a.depth)
+    entry = "vaeq_ldpc_decode" if a.depth is None else f"vaeq_ldpc_decode_il at depth {a.depth}"
     edges = int((code.shifts >= 0).sum()) * code.Z
     lds = int(nat.lib().vaeq_ldpc_lds_bytes(code.mb, code.nb, code.Z)) + STATIC_LDS
     waves = (code.Z + 63) // 64
-    lines = [f"# vaeq_ldpc_decode: {R} runs x {C_} codewords of array_code(4, 24, 211), n = {code.n}, {edges} edges, w = {w}, {N} symbols, "
+    lines = [f"# {entry}: {R} runs x {C_} codewords of array_code(4, 24, 211), n = {code.n}, {edges} edges, w = {w}, {N} symbols, "
              f"max_iter {a.max_iter}, alpha 0.75; {torch.cuda.get_device_name(dev)}",
              f"# workgroup: {waves * 64} threads, {lds} B of LDS -> {min(LDS_PER_CU // lds, WAVES_PER_CU // waves)} workgroups per CU "
              f"(LDS allows {LDS_PER_CU // lds}, the 32 waves of a CU {WAVES_PER_CU // waves})"]
@@ -56,13 +62,13 @@ def main():
         g.manual_seed(1 + k)
         bits = torch.randint(0, 2, (R, w, N), dtype=torch.int8, device=dev, generator=g)
         llr.normal_(generator=g).mul_(sigma).add_(1.0).sub_(bits, alpha=2.0).mul_(2.0 / sigma ** 2)
-        res = engine.ldpc_decode(llr, bits, code, max_iter=a.max_iter)                # warm-up; its figures are the level's
+        res = engine.ldpc_decode(llr, bits, code, **kw)                               # warm-up; its figures are the level's
         torch.cuda.synchronize()
         times = []
         for _ in range(a.rounds):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            engine.ldpc_decode(llr, bits, code, max_iter=a.max_iter)
+            engine.ldpc_decode(llr, bits, code, **kw)
             e1.record()
             e1.synchronize()
             times.append(e0.elapsed_time(e1))

@@ -68,6 +68,7 @@ n1 = (lmmse_filter_order - 1) // 2 + 1
 N_SHIFT_LMMSE, N_SHIFT_DFE = 21, 24                    # find_shift_symb lags (:280, :292)
 
 info_metrics = False    # True: main() also returns the info dicts of both curves (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp)
+fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None): main() also returns engine.ldpc_decode's figures of both curves' LLRs
 base_seed = None        # int -> reproducible frames (the reference's stream under the same seed); None = like the reference
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
 
@@ -181,7 +182,7 @@ def _filters(h, SNR):
 
 
 def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.0270955, *, seed=None, generator=None, device=None,
-                  verbose=False, C=None, W=None, want_info=False, want_llr=False):
+                  verbose=False, C=None, W=None, want_info=False, want_llr=False, fec=None):
     """The script's loop nest (:264-296) for a channel (h_orig: symbol-spaced taps, default h_1) and a modulation, all frames at once:
     R = len(SNRs) * num_epochs frames, one generator call, ONE LMMSE evaluation launch and ONE DFE launch.
 
@@ -196,9 +197,15 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
     awgn_track_info on them (want_info's call, when that is on), and engine.label_bits of the TX data.  All frames go through one launch, so
     all of them are returned; the two dicts share one bits tensor: num_snr x num_epochs x 2b x N_valid x (2 x 4 + 1) bytes (64-QAM, 15 SNRs x
     10 epochs x 10 000 symbols: 81 MB).
-    Every other output is the same with and without it."""
+    Every other output is the same with and without it.
+    With fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) also fec_mmse and fec_dfe ON THE DEVICE: engine.ldpc_decode's
+    figures of those LLRs (computed for it; llr_* itself is returned only with want_llr), all num_snr x num_epochs frames as the run axis of one
+    call per curve: the counters [num_snr, num_epochs, C], the rates [num_snr, num_epochs].  A bad fec dict is a ValueError before anything is
+    allocated or launched."""
     from .dp_runs import default_device, fresh_seed, resolve_generator
-    from .engine import awgn_dfe, awgn_dfe_soft, awgn_lmmse_eval, awgn_track_info, awgn_track_llr, label_bits
+    from .engine import awgn_dfe, awgn_dfe_soft, awgn_lmmse_eval, awgn_track_info, awgn_track_llr, check_fec, fec_figures, label_bits
+    check_fec(fec)
+    need_llr = want_llr or fec is not None
     device = default_device() if device is None else torch.device(device)
     h = channel_taps(CHANNELS["h1"] if h_orig is None else np.asarray(h_orig), sps)
     q = qam_constants(mod)
@@ -222,21 +229,25 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
                                              fresh_seed() if seed is None else seed, 0)
     else:
         raise ValueError(f"unknown generator {generator!r}")
-    ser_m, sh_m, dec_m, out_m = awgn_lmmse_eval(rx, lm, data, amps, N_SHIFT_LMMSE, N_cut, want_out=want_info or want_llr)
-    r = awgn_dfe(rx, ff, fb, dec_m, amps, data, N_SHIFT_DFE, N_cut, C=C, W=W, want_ff=want_info or want_llr)
+    ser_m, sh_m, dec_m, out_m = awgn_lmmse_eval(rx, lm, data, amps, N_SHIFT_LMMSE, N_cut, want_out=want_info or need_llr)
+    r = awgn_dfe(rx, ff, fb, dec_m, amps, data, N_SHIFT_DFE, N_cut, C=C, W=W, want_ff=want_info or need_llr)
     info = {}
-    if want_info or want_llr:
+    if want_info or need_llr:
         P = ch.pcs_probabilities(amps, nu)
         var = [10 ** (-SNRs[k // E] / 10) for k in range(R)]
         on_grid = lambda d: {k: v.cpu().reshape(S, E) for k, v in d.items()}  # noqa: E731
-        bits = label_bits(data, len(amps)).reshape(S, E, -1, data.shape[-1]) if want_llr else None
+        bits = label_bits(data, len(amps)).reshape(S, E, -1, data.shape[-1]) if need_llr else None
         for key, z, sh in (("mmse", out_m, sh_m), ("dfe", awgn_dfe_soft(r["ff"], fb, r["dec"], amps), r["shift"])):
             fig = awgn_track_info(z, data, amps, P, var, sh, N_cut + 11)
             if want_info:
                 info["info_" + key] = on_grid(fig)
-            if want_llr:                                                        # the same track, shift, edge and var as fig, under its hypothesis
+            if need_llr:                                                        # the same track, shift, edge and var as fig, under its hypothesis
                 llr = awgn_track_llr(z, data, amps, var, sh, fig["hyp"], N_cut + 11)
-                info["llr_" + key] = dict(llr=llr.reshape(S, E, *llr.shape[1:]), bits=bits, hyp=fig["hyp"].reshape(S, E))
+                if want_llr:
+                    info["llr_" + key] = dict(llr=llr.reshape(S, E, *llr.shape[1:]), bits=bits, hyp=fig["hyp"].reshape(S, E))
+                if fec is not None:
+                    info["fec_" + key] = {k: v.reshape(S, E, *v.shape[1:])
+                                          for k, v in fec_figures(dict(llr=llr, bits=bits.reshape(R, *bits.shape[2:])), fec).items()}
     out = dict(SER_mmse=ser_m.cpu().reshape(S, E), SER_dfe=r["ser"].cpu().reshape(S, E), shift_mmse=sh_m.cpu().numpy().reshape(S, E),
                shift_dfe=r["shift"].cpu().numpy().reshape(S, E), repairs=r["repairs"].cpu().numpy().reshape(S, E), C=r["C"], W=r["W"])
     out.update(info)
@@ -249,13 +260,15 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
 
 def main():
     """The reference's sweep (:264-296) with the module's constants -> (SER_mmse, SER_dfe), each [num_snr, num_epochs] (CPU float32); with
-    info_metrics (SER_mmse, SER_dfe, info_mmse, info_dfe), the two dicts as run_dfe_batch's."""
+    info_metrics (SER_mmse, SER_dfe, info_mmse, info_dfe), the two dicts as run_dfe_batch's; with fec_metrics additionally fec_mmse and fec_dfe,
+    run_dfe_batch's (on the device), at the end."""
     from .dp_runs import default_device
     device = default_device()
     print("We are using the following device for learning:", device)
     r = run_dfe_batch(SNR_vec, num_epochs, N_valid, mod, h_channel_orig, nu, seed=base_seed, generator=generator, device=device,
-                      verbose=True, want_info=info_metrics)
-    return (r["SER_mmse"], r["SER_dfe"], r["info_mmse"], r["info_dfe"]) if info_metrics else (r["SER_mmse"], r["SER_dfe"])
+                      verbose=True, want_info=info_metrics, fec=fec_metrics)
+    out = (r["SER_mmse"], r["SER_dfe"], r["info_mmse"], r["info_dfe"]) if info_metrics else (r["SER_mmse"], r["SER_dfe"])
+    return out if fec_metrics is None else out + (r["fec_mmse"], r["fec_dfe"])
 
 
 if __name__ == "__main__":

@@ -41,6 +41,7 @@ N_frame_max = 10000
 savePATH = ""
 base_seed = None    # int -> reproducible runs (run i of the flattened sweep uses base_seed + 1000*i); None = like the reference
 info_metrics = False  # True (every loss_type): the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), shaped like SER with a leading axis of 2
+fec_metrics = None  # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) (every loss_type): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords) of the last frame's LLRs, each shaped like SER without its first and last axes
 generator = None    # None: "hip" (on-device channel simulator) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set; or force "numpy" / "hip" / "torch"
 
 
@@ -77,6 +78,8 @@ def main():
     key = lambda i: (points[i][1]["M"], points[i][1]["batch_len"], points[i][1]["flex_step"], points[i][1]["symb_rate"])
     shapes = sorted({key(i) for i in mine})
     n_col = 16 if info_metrics else 8                      # with info_metrics: + GMI[2] | NGMI[2] | AIR[2] | BER[2]
+    c_fec, n_fec = n_col, 0 if fec_metrics is None else len(sweep.FEC_KEYS)
+    n_col += n_fec                                         # with fec_metrics: + BER_post | FER | BER_pre_fec | fec_iters (broadcast)
     local = torch.zeros(len(mine), n_col, num_frames, dtype=torch.float32)
     for (M, batch_len, fs, rate) in shapes:
         sel = [k for k, i in enumerate(mine) if key(i) == (M, batch_len, fs, rate)]
@@ -87,11 +90,11 @@ def main():
             from .cma_runs import run_cma_batch
             r = run_cma_batch(runs, loss_type, mod, sps, M, batch_len, N_frame_max, num_frames, fs, channel, tau_cd, tau_pmd, phiIQ, N_lrhalf,
                               device=device, generator=generator if generator in (None, "numpy", "hip") else "hip", verbose=False,
-                              want_info=info_metrics)
+                              want_info=info_metrics, fec=fec_metrics)
         elif loss_type in ('VAE', 'VAEflex'):
             r = run_dp_batch(runs, mod, sps, M, batch_len, N_frame_max, num_frames, fs, channel, tau_cd, tau_pmd, phiIQ, N_lrhalf,
                              flex=(loss_type == 'VAEflex'), device=device, generator=generator, verbose=False,
-                             want_info=info_metrics)
+                             want_info=info_metrics, fec=fec_metrics)
         else:
             raise NameError(f"loss_type {loss_type!r}: the reference leaves `process` undefined (:56-65)")
         local[sel, 0:4] = r["SER"]
@@ -102,6 +105,8 @@ def main():
                 raise ValueError(f"the result of loss_type {loss_type!r} carries no 'info'")
             for j, k in enumerate(INFO_KEYS):
                 local[sel, 8 + 2 * j:10 + 2 * j] = r["info"][k]
+        if n_fec:
+            local[sel, c_fec:] = sweep.fec_values(r["fec"]).unsqueeze(-1).expand(-1, -1, num_frames)
     rows = sweep.gather_rows(local, len(points), rank, world)
     if rank != 0:
         return None
@@ -119,6 +124,11 @@ def main():
             for k, (idx, _) in enumerate(points):
                 arr[(slice(None),) + idx] = rows[k, 8 + 2 * j:10 + 2 * j]
             save_dict[name_k] = arr.numpy()
+    for j, name_k in enumerate(sweep.FEC_KEYS[:n_fec]):
+        arr = torch.empty(*shape_tail, dtype=torch.float32)
+        for k, (idx, _) in enumerate(points):
+            arr[idx] = rows[k, c_fec + j, 0]
+        save_dict[name_k] = arr.numpy()
     io.savemat(name, {'dict': save_dict})
     return name, save_dict
 

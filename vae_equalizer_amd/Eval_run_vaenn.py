@@ -24,6 +24,7 @@ savePATH = ""
 base_seed = None        # int -> reproducible runs; None = like the reference
 info_metrics = False    # True: the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), each shaped like SER
 generator = "hip"       # "hip": on-device channel model; "numpy": host restatement per run
+fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords) of the last validation's LLRs, each shaped like SER without its last axis
 INFO_KEYS = ("GMI", "NGMI", "AIR", "BER")
 
 
@@ -39,25 +40,29 @@ def main():
     from . import sweep
     from .func_VAENN_MQAM import run_vaenn_batch
 
+    keys, n_fec = INFO_KEYS if info_metrics else (), 0 if fec_metrics is None else len(sweep.FEC_KEYS)
     name = save_dict = None
     for j, net_type in enumerate(net_type_vec):
         def run_batch(shape, pts, seeds, device, seed):
             M, k1, k2, batch_len = shape
             runs = [dict(SNR=p["SNR"], lr_optim=p["lr"], seed=s) for p, s in zip(pts, seeds)]
             r = run_vaenn_batch(runs, mod, sps, M, k1, k2, batch_len, N_valid, train_len, num_epochs, epe, channel, device=device,
-                                generator=generator, seed=seed, net_type=net_type, want_info=info_metrics)
+                                generator=generator, seed=seed, net_type=net_type, want_info=info_metrics, fec=fec_metrics)
+            if fec_metrics is not None:
+                return sweep.fec_rows(r, keys)                                        # per run: SER | keys | BER_post | FER | BER_pre_fec | fec_iters
             return sweep.info_rows(r, INFO_KEYS) if info_metrics else r           # per run: SER | GMI | NGMI | AIR | BER
 
         n_eval = num_epochs // epe
         out = sweep.run_sharded(list(sweep_points()), lambda p: (p["M"], p["k1"], p["k2"], p["batch_len"]), run_batch, base_seed,
                                 (len(SNR_vec), len(k2_vec), len(k1_vec), len(M_vec), len(lr_optim_vec), len(batch_len_vec), iter),
-                                (1 + len(INFO_KEYS), n_eval) if info_metrics else (n_eval,),
+                                (1 + len(keys) + n_fec, n_eval) if keys or n_fec else (n_eval,),
                                 batch_offset=1000 * net_type_vec.index(net_type), announce=j == 0)
         if out is None:
             continue
         name = f"{savePATH}SERvsSNR_{net_type}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
         save_dict = {'SER': out[0].numpy(), 'SNR': SNR_vec, 'k2': k2_vec, 'k1': k1_vec, 'M': M_vec, 'lr': lr_optim_vec, 'N_train': batch_len_vec}
-        save_dict.update({k: arr.numpy() for k, arr in zip(INFO_KEYS, out[1:])})
+        save_dict.update({k: arr.numpy() for k, arr in zip(keys, out[1:])})
+        save_dict.update({k: arr[..., -1].numpy() for k, arr in zip(sweep.FEC_KEYS[:n_fec], out[1 + len(keys):])})
         io.savemat(name, {'dict': save_dict})
     return (name, save_dict) if sweep.dist_info()[0] == 0 else None
 

@@ -111,7 +111,7 @@ EXPORTS = ["vaeq_dp_train", "vaeq_dp_step_debug", "vaeq_dp_lds_bytes", "vaeq_dp_
            "vaeq_dp_forward_bwd_x", "vaeq_dp_loss_bwd_x", "vaeq_awgn_forward_bwd_x", "vaeq_awgn_loss_bwd_x", "vaeq_nn_enc_backward_x",
            "vaeq_dp_epilogue_info", "vaeq_awgn_info", "vaeq_awgn_validate_short", "vaeq_cma_epilogue_info",
            "vaeq_awgn_track_info", "vaeq_awgn_dfe_soft", "vaeq_dp_epilogue_llr", "vaeq_awgn_llr",
-           "vaeq_cma_epilogue_llr", "vaeq_awgn_track_llr", "vaeq_ldpc_decode", "vaeq_ldpc_lds_bytes"]
+           "vaeq_cma_epilogue_llr", "vaeq_awgn_track_llr", "vaeq_ldpc_decode", "vaeq_ldpc_lds_bytes", "vaeq_ldpc_decode_il"]
 
 
 def lib():
@@ -170,6 +170,9 @@ def lib():
         L.vaeq_ldpc_decode.restype = C.c_int
         L.vaeq_ldpc_decode.argtypes = ([C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p] * 3
                                        + [C.c_float, C.c_int32] + [C.c_void_p] * 3)
+        L.vaeq_ldpc_decode_il.restype = C.c_int
+        L.vaeq_ldpc_decode_il.argtypes = ([C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 3
+                                          + [C.c_float, C.c_int32] + [C.c_void_p] * 3)
         L.vaeq_ldpc_lds_bytes.restype = C.c_int64
         L.vaeq_ldpc_lds_bytes.argtypes = [C.c_int32] * 3
         L.vaeq_awgn_track_info.restype = C.c_int

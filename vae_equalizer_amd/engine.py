@@ -695,27 +695,37 @@ def array_code(mb, nb, Z):
     return LdpcCode(np.outer(np.arange(mb), np.arange(nb)) % Z, Z)
 
 
-def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=0.75, want_post=False):
+def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=0.75, want_post=False, depth=None):
     """Post-FEC figures of per-bit LLRs on the device (vaeq_ldpc_decode): layered normalized min-sum towards the syndrome of the TX bits (no
     encoder).  llr f32 and bits int8 of one shape, [R,2,2b,N] (dp_epilogue_llr / cma_epilogue_llr with label_bits) or [R,w,N] (awgn_llr,
     awgn_track_llr); bit j of codeword c of a run is global bit c n + j, at symbol t0 + (c n + j) // w in plane (c n + j) % w.  codewords: per
     run, default the most that fit behind t0.  -> dict(iters, ok, bit_err, pre_err, erased [R,C] int64; BER_post[R], BER_pre[R], FER[R] f32
-    (FER: the share of codewords with bit_err > 0); post[R,C,n] f32, the final LLRs in codeword order, if want_post)."""
+    (FER: the share of codewords with bit_err > 0); post[R,C,n] f32, the final LLRs in codeword order, if want_post).
+    depth: an int puts a symbol interleaver over groups of `depth` codewords in front of the decoder (vaeq_ldpc_decode_il): codewords of
+    S = ceil(n / w) whole symbols, symbol u of the codeword with local index d of a group of D at symbol base + u D + d; codewords then defaults
+    to (N - t0) // S.  None: the contiguous bit-packed codewords above."""
     if llr.shape != bits.shape or llr.dim() not in (3, 4):
         raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
     dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
     llr = llr.reshape(R, -1, N).contiguous()
     bits = bits.reshape(R, -1, N).contiguous()
     w, n = llr.shape[1], code.n
-    C_ = int(codewords) if codewords is not None else ((N - int(t0)) * w // n if n > 0 else 0)
+    if depth is None:
+        fit = (N - int(t0)) * w // n if n > 0 else 0
+    else:
+        fit = (N - int(t0)) // -(-n // w) if n > 0 and w > 0 else 0
+    C_ = int(codewords) if codewords is not None else fit
     if codewords is None and C_ < 1:
         raise ValueError(f"no codeword of {n} bits fits into {N - int(t0)} symbols of {w} bits")
     out = torch.empty(R, max(C_, 0), 5, dtype=torch.int32, device=dev)
     post = torch.empty(R, max(C_, 0), n, dtype=torch.float32, device=dev) if want_post else None
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_ldpc_decode(R, C_, N, w, int(t0), code.mb, code.nb, code.Z, code.shifts.ctypes.data_as(C.c_void_p), nat.ptr(llr),
-                                             nat.ptr(bits, torch.int8), float(alpha), int(max_iter), nat.ptr(out, torch.int32), nat.ptr(post),
-                                             nat.current_stream(dev)), "vaeq_ldpc_decode")
+        tail = (code.mb, code.nb, code.Z, code.shifts.ctypes.data_as(C.c_void_p), nat.ptr(llr), nat.ptr(bits, torch.int8), float(alpha),
+                int(max_iter), nat.ptr(out, torch.int32), nat.ptr(post), nat.current_stream(dev))
+        if depth is None:
+            nat.check(nat.lib().vaeq_ldpc_decode(R, C_, N, w, int(t0), *tail), "vaeq_ldpc_decode")
+        else:
+            nat.check(nat.lib().vaeq_ldpc_decode_il(R, C_, N, w, int(t0), int(depth), *tail), "vaeq_ldpc_decode_il")
     o = out.long()
     tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)   # a tensor divisor: a true division, not a product with 1 / tot
     ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
@@ -726,12 +736,19 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=0.75, 
     return ret
 
 
+FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth")
+
+
+def check_fec(fec):
+    """ValueError for a fec= dict that fec_figures would refuse (None passes): for a runner to call before it allocates or launches anything."""
+    if fec is not None and (set(fec) - set(FEC_KEYS) or "code" not in fec):
+        raise ValueError(f"fec takes {', '.join(FEC_KEYS)}; got {sorted(fec)}")
+
+
 def fec_figures(llr, fec):
-    """run_dp_batch / run_cma_batch's fec= : ldpc_decode of an "llr" dict (llr, bits) under fec = dict(code, t0, max_iter, alpha; all but code
+    """The batch runners' fec= : ldpc_decode of an "llr" dict (llr, bits) under fec = dict(code, t0, max_iter, alpha, depth; all but code
     optional)."""
-    unknown = set(fec) - {"code", "t0", "max_iter", "alpha"}
-    if unknown or "code" not in fec:
-        raise ValueError(f"fec takes code, t0, max_iter, alpha; got {sorted(fec)}")
+    check_fec(fec)
     return ldpc_decode(llr["llr"], llr["bits"], fec["code"], **{k: v for k, v in fec.items() if k != "code"})
 
 

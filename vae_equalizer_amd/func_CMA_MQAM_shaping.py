@@ -9,7 +9,7 @@ import torch
 from . import channel as ch
 from .awgn_runs import check_generator, first_run, run_awgn_epochs
 from .dp_runs import default_device, resolve_generator
-from .engine import awgn_cma, awgn_cma_validate, awgn_track_info
+from .engine import awgn_cma, awgn_cma_validate, awgn_track_info, awgn_track_llr, check_fec, label_bits
 from .func_VAELE_MQAM_shaping import SER_symb, awgn_batch_tables, awgn_tables  # noqa: F401  (SER_symb: identical text in both reference modules)
 
 rcfir, rrcfir = ch.rcfir, ch.rrcfir
@@ -89,7 +89,7 @@ def cma_validate_torch(rx, h, data, amp_levels, sps=2, n_shift=N_SHIFT):
 
 
 def run_awgn_cma_batch(runs, mod, sps, M_est, N_valid, N_train, num_epochs, epe, channel, device=None, verbose=False, generator=None,
-                       seed=None, want_info=False):
+                       seed=None, want_info=False, want_llr=False, fec=None):
     """R AWGN constant-modulus runs at once: ``runs`` = list of dict(SNR, nu, lr_optim, seed).  Per epoch ONE training launch (every run's
     per-symbol chain on its own wave) and, on evaluated epochs, ONE fused validation launch (:213-232).
 
@@ -98,8 +98,13 @@ def run_awgn_cma_batch(runs, mod, sps, M_est, N_valid, N_train, num_epochs, epe,
                "hip"   = the on-device generator (vaeq_gen_awgn), Philox streams keyed by ``seed``, the draw counter and the run index.
     Returns SER_valid[R, num_epochs // epe] (CPU float32); with want_info (SER_valid, info), info = dict(AIR, GMI, NGMI, BER f32; kept, sym_err,
     bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: engine.awgn_track_info on the CPE output and the shift of every validation launch,
-    demapped at var = 10^(-SNR/10), the VAE-LE's of the same sweep point (func_VAELE_MQAM_shaping.py:272)."""
+    demapped at var = 10^(-SNR/10), the VAE-LE's of the same sweep point (func_VAELE_MQAM_shaping.py:272).
+    want_llr / fec: (SER_valid, info or None, extras), for the LAST evaluated validation only and on the device: with want_llr extras["llr"] =
+    dict(llr[R,2b,N_valid] f32 = engine.awgn_track_llr on that validation's CPE output and shift, at the var and edge 11 of the info call and
+    under its hyp, bits int8 = engine.label_bits of its TX data, hyp[R]); with fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75,
+    depth=None) extras["fec"] = engine.ldpc_decode's figures of those LLRs.  Both off: no output changes."""
     device = default_device() if device is None else torch.device(device)
+    check_fec(fec)
     R = len(runs)
     generator = check_generator(resolve_generator(generator, any(r.get("seed") is not None for r in runs)))
     tabs, gen_args, host, seeded = awgn_batch_tables(runs, mod, sps, channel)
@@ -109,13 +114,16 @@ def run_awgn_cma_batch(runs, mod, sps, M_est, N_valid, N_train, num_epochs, epe,
     h[:, 0, M_est // 2] = 1.0                                                    # :245-246
     lr = torch.tensor([r["lr_optim"] for r in runs], dtype=torch.float32, device=device)
 
-    def validate(draw, N):                                                       # :222-232
+    def validate(draw, N, soft=False):                                           # :222-232
         rxv, datav = draw(N)
-        ser, sh, yv = awgn_cma_validate(rxv, h, datav, amp, sps, N_SHIFT, want_cpe=want_info)
-        return ser, sh, awgn_track_info(yv, datav, amp, gen_args[1], var, sh, 11) if want_info else None
+        ser, sh, yv = awgn_cma_validate(rxv, h, datav, amp, sps, N_SHIFT, want_cpe=want_info or soft)
+        if not soft:
+            return ser, sh, awgn_track_info(yv, datav, amp, gen_args[1], var, sh, 11) if want_info else None
+        info = awgn_track_info(yv, datav, amp, gen_args[1], var, sh, 11)
+        return ser, sh, info, dict(llr=awgn_track_llr(yv, datav, amp, var, sh, info["hyp"], 11), bits=label_bits(datav, amp.numel()), hyp=info["hyp"])
 
     return run_awgn_epochs(R, device, num_epochs, epe, N_train, N_valid, lambda rx: awgn_cma(rx, h, lr, sps, update=True)[0], validate,   # :218-220
-                           generator, seed, gen_args, host, seeded, verbose, want_info)
+                           generator, seed, gen_args, host, seeded, verbose, want_info, want_llr, fec)
 
 
 def processing(mod, sps, SNR, nu, M_est, lr_optim, N_valid, N_train, num_epochs, epe, channel, *, seed=None, device=None, verbose=True,

@@ -6,7 +6,7 @@ import torch
 from . import channel as ch
 from .awgn_runs import check_generator, first_run, run_awgn_epochs
 from .dp_runs import default_device, resolve_generator
-from .engine import INFO_FLOAT as INFO_FIGURES, INFO_INT as INFO_COUNTS, AWGNEngine  # noqa: F401  (the keys of engine.awgn_info, under this module's names)
+from .engine import INFO_FLOAT as INFO_FIGURES, INFO_INT as INFO_COUNTS, AWGNEngine, check_fec, label_bits  # noqa: F401  (the keys of engine.awgn_info, under this module's names)
 from .shared_funcs import _CHANNELS, qam_tables
 
 
@@ -121,7 +121,7 @@ def awgn_batch_tables(runs, mod, sps, channel):
 
 
 def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epochs, epe, channel, device=None, verbose=False,
-                   generator=None, seed=None, want_info=False):
+                   generator=None, seed=None, want_info=False, want_llr=False, fec=None):
     """R AWGN VAE-LE runs at once: ``runs`` = list of dict(SNR, nu, lr_optim, seed).  Per epoch ONE training launch and, on evaluated
     epochs, ONE fused validation launch (forward + find_shift + SER_q, vaeq_awgn_validate) for all runs (:291-322).
 
@@ -129,8 +129,13 @@ def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epoch
                "numpy" = the bit-faithful host channel model per run (seeded like tools/capture_golden.py when the run has a seed);
                "hip"   = the on-device generator (vaeq_gen_awgn), Philox streams keyed by ``seed``, the draw counter and the run index.
     Returns SER_valid[R, num_epochs // epe] (CPU float32); with want_info (SER_valid, info), info = dict(AIR, GMI, NGMI, BER f32; kept, sym_err,
-    bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: engine.awgn_info in y-mode on the y and the shift of every validation launch."""
+    bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: engine.awgn_info in y-mode on the y and the shift of every validation launch.
+    want_llr / fec: (SER_valid, info or None, extras), for the LAST evaluated validation only and on the device: with want_llr extras["llr"] =
+    dict(llr[R,2b,N_valid] f32 = AWGNEngine.llr on that validation's y and shift under the hyp of AWGNEngine.info on them, bits int8 =
+    engine.label_bits of its TX data, hyp[R]); with fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) extras["fec"] =
+    engine.ldpc_decode's figures of those LLRs.  Both off: no output changes."""
     device = default_device() if device is None else torch.device(device)
+    check_fec(fec)
     R = len(runs)
     generator = check_generator(resolve_generator(generator, any(r.get("seed") is not None for r in runs)))
     tabs, gen_args, host, seeded = awgn_batch_tables(runs, mod, sps, channel)
@@ -139,7 +144,7 @@ def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epoch
     lr = np.array([r["lr_optim"] for r in runs], dtype=np.float32)
     steps = N_train // batch_len                                                 # :297 (the remainder is dropped)
 
-    def validate(draw, N):                                                       # :308-318
+    def validate(draw, N, soft=False):                                           # :308-318
         if generator == "hip" and ch.awgn_clean_supported(sps, M_est):           # the validation frame is read once: its noise goes on while it is read
             frame = draw(N, clean=True)
             ser, sh, yv = eng.validate_clean(frame, 21)
@@ -147,10 +152,13 @@ def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epoch
         else:
             rxv, datav = draw(N)
             ser, sh, yv = eng.validate(rxv, datav, 21)
-        return ser, sh, eng.info(yv, datav, sh) if want_info else None
+        if not soft:
+            return ser, sh, eng.info(yv, datav, sh) if want_info else None
+        info = eng.info(yv, datav, sh)
+        return ser, sh, info, dict(llr=eng.llr(yv, sh, info["hyp"]), bits=label_bits(datav, amp.numel()), hyp=info["hyp"])
 
     return run_awgn_epochs(R, device, num_epochs, epe, N_train, N_valid, lambda rx: eng.train(rx, batch_len, steps, lr)["loss"][:, -1], validate,
-                           generator, seed, gen_args, host, seeded, verbose, want_info)
+                           generator, seed, gen_args, host, seeded, verbose, want_info, want_llr, fec)
 
 
 def processing(mod, sps, SNR, nu, M_est, lr_optim, batch_len, N_valid, N_train, num_epochs, epe, channel, *, seed=None,

@@ -14,7 +14,7 @@ from torch import nn
 from . import channel as ch
 from .awgn_runs import check_generator, first_run, run_awgn_epochs
 from .dp_runs import default_device
-from .engine import NNEngine
+from .engine import NNEngine, check_fec, label_bits
 from .func_VAELE_MQAM_shaping import SER_q, SER_symb, find_shift  # noqa: F401  (identical helpers in both reference files)
 from .shared_funcs import _CHANNELS, _LEVELS
 
@@ -139,7 +139,7 @@ def theta_to_net(theta, net, bn=None):
 
 
 def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_valid, N_train, num_epochs, epe, channel, device=None,
-                    verbose=False, generator="hip", seed=0, theta0=None, net_type="Net", want_info=False):
+                    verbose=False, generator="hip", seed=0, theta0=None, net_type="Net", want_info=False, want_llr=False, fec=None):
     """R VAE-NN runs at once: ``runs`` = list of dict(SNR, lr_optim, seed).  Per epoch one generator call, ONE training launch
     (N_train // batch_len minibatches) and, on evaluated epochs, one fused validation launch for all runs (:266-301).
 
@@ -148,13 +148,18 @@ def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_vali
     theta0: optional [R, NP] initial parameters (default: Xavier / PyTorch-default initialisation drawn on the device).
     Returns SER_valid[R, num_epochs // epe] (CPU float32); with want_info (SER_valid, info), info = dict(AIR, GMI, NGMI, BER f32; kept, sym_err,
     bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: NNEngine.info (eval forward, then engine.awgn_info in q-mode, uniform pmf) on the
-    frame and the shift of every validation launch."""
+    frame and the shift of every validation launch.
+    want_llr / fec: (SER_valid, info or None, extras), for the LAST evaluated validation only and on the device: with want_llr extras["llr"] =
+    dict(llr[R,2b,N_valid] f32 = NNEngine.llr on that validation's frame and shift under the hyp of NNEngine.info on them, bits int8 =
+    engine.label_bits of its TX data, hyp[R]); with fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) extras["fec"] =
+    engine.ldpc_decode's figures of those LLRs.  Both off: no output changes."""
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
     t = vaenn_tables(mod, channel, sps)
     if net_type not in ("Net", "Net_BN"):
         raise UnboundLocalError(f"unknown net_type {net_type!r} (the reference leaves `net` unbound, :239-243)")
     check_generator(generator)
+    check_fec(fec)
     eng = NNEngine(R, M_est, kernel_1, kernel_2, t["amps"], device, sps, batch_norm=(net_type == "Net_BN"))
     if theta0 is None:
         gen = torch.Generator(device=device)
@@ -168,15 +173,18 @@ def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_vali
     rngs = [np.random.RandomState(r["seed"]) if r.get("seed") is not None else None for r in runs]
     steps = N_train // batch_len
 
-    def validate(draw, N):
+    def validate(draw, N, soft=False):
         rxv, datav = draw(N)
         ser, sh = eng.validate(rxv, datav, 21)
-        return ser, sh, eng.info(rxv, datav, sh) if want_info else None
+        if not soft:
+            return ser, sh, eng.info(rxv, datav, sh) if want_info else None
+        info = eng.info(rxv, datav, sh)
+        return ser, sh, info, dict(llr=eng.llr(rxv, sh, info["hyp"]), bits=label_bits(datav, t["n"]), hyp=info["hyp"])
 
     return run_awgn_epochs(R, device, num_epochs, epe, N_train, N_valid, lambda rx: eng.train(rx, batch_len, steps, lr)["loss"][:, -1], validate,
                            generator, seed, (t["amps"], np.full(t["n"], 1.0 / t["n"]), snr, t["h_channel"], sps),
                            lambda N, i: generate_data(N, t["M_channel"], t["constellation"], runs[i]["SNR"], t["h_channel"], sps, "cpu", rngs[i]),
-                           all(g is not None for g in rngs), verbose, want_info, sigma_fixed=np.sqrt(0.5) / 10 ** (snr / 20))
+                           all(g is not None for g in rngs), verbose, want_info, want_llr, fec, sigma_fixed=np.sqrt(0.5) / 10 ** (snr / 20))
 
 
 def processing(mod, sps, SNR, M_est, kernel_1, kernel_2, lr_optim, batch_len, N_valid, N_train, num_epochs, epe, channel, net_type, *,

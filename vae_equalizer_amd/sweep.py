@@ -116,3 +116,19 @@ def run_sharded(points, shape_key, run_batch, base_seed, result_shape, row_shape
 def info_rows(r, keys):
     """A runner's (SER, info) -> rows [R, 1 + len(keys), n_eval]: per run SER, then info[k] for k in keys."""
     return torch.stack([r[0]] + [r[1][k] for k in keys], dim=1)
+
+
+FEC_KEYS = ("BER_post", "FER", "BER_pre_fec", "fec_iters")
+
+
+def fec_values(fec):
+    """engine.fec_figures' dict -> [R, 4] float32 on the CPU, in FEC_KEYS order: BER_post, FER, BER_pre and the mean over the codewords of iters."""
+    return torch.stack([fec["BER_post"], fec["FER"], fec["BER_pre"], fec["iters"].double().mean(1).float()], dim=1).cpu()
+
+
+def fec_rows(r, keys):
+    """An AWGN runner's (SER, info or None, extras) under fec= -> rows [R, 1 + len(keys) + 4, n_eval] through info_rows: SER, info[k] for k in keys,
+    then the four FEC_KEYS figures of the last evaluated validation, each repeated along n_eval (a row has one length)."""
+    v = fec_values(r[2]["fec"])
+    cols = dict(r[1] or {}, **{k: v[:, j:j + 1].expand(-1, r[0].shape[1]) for j, k in enumerate(FEC_KEYS)})
+    return info_rows((r[0], cols), tuple(keys) + FEC_KEYS)
