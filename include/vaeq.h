@@ -685,6 +685,39 @@ int vaeq_ldpc_decode_il(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, 
                         const int32_t *shifts_host, const float *llr, const int8_t *bits, float alpha, int32_t max_iter, int32_t *out, float *post,
                         void *stream);
 
+/* The fixed-point decoder: vaeq_ldpc_decode's layered min-sum with q-bit channel LLRs, q-bit check messages and saturating a-posteriori values,
+ * as a hardware decoder holds them.  Float32 normalized min-sum is positively homogeneous: a common factor on every LLR changes no decision and
+ * no counter, so vaeq_ldpc_decode cannot show whether an equalizer's noise-variance estimate (the scale of its LLRs) is any good.  Here the
+ * scale decides what is clipped and what rounds to an erasure.
+ * The code table, the tensors llr[R][w][N] / bits[R][w][N], coset decoding towards the syndrome of the TX bits, the layer order, the edge order
+ * (ascending block column), the test before the first and after every full iteration, and out[R][C][5] are vaeq_ldpc_decode's.  depth == 0 is
+ * vaeq_ldpc_decode's bit-packed contiguous mapping with its fit rule, depth >= 1 vaeq_ldpc_decode_il's symbol interleaver with its fit rule.
+ * Everything behind the quantiser is integer arithmetic, fixed here so that an integer model reproduces every bit:
+ *   constants  Cmax = Mmax = 2^(qbits-1) - 1, Lmax = 2^(abits-1) - 1.
+ *   quantiser  (the only float operations, each rounded on its own)  x = llr * scale in float32; a NaN x becomes +0; x = min(max(x, -Cmax), Cmax);
+ *              Q = rint(x), ties to even, as an integer.
+ *   counters   pre_err counts (llr < 0) != bit on the RAW float input (vaeq_ldpc_decode's pre_err of the same tensors; a NaN is bit 0);
+ *              erased counts Q == 0: what the quantiser erased, not only exact zeros.
+ *   start      L[v] = Q[v]; every check's (m1, m2, idx, signs) = (0, 0, 0, 0).  Negative means < 0: integer 0 is bit 0.
+ *   f          f(m) = max(((num m + 4) >> 3) - beta, 0): num = 6, beta = 0 is alpha = 0.75 rounded half up; num = 8, beta = 1 plain offset min-sum.
+ *   layer      for check i with edges e:  r_e = +-f(m2 if e == idx else m1) of the stored state, negative iff bit e of signs;
+ *              t_e = L[v_e] - r_e, exact (|t_e| <= Lmax + Mmax fits 16 bits because abits <= 15);  a_e = min(|t_e|, Mmax);
+ *              m1, m2 = the smallest and second smallest a_e, idx = the FIRST edge that attains m1 after the clamp (ties are the common case);
+ *              s_e = (t_e < 0), S = xor_e s_e xor sigma_i;  r'_e = +-f(m2 if e == idx else m1) of the NEW state, negative iff S xor s_e;
+ *              L[v_e] = min(max(t_e + r'_e, -Lmax), Lmax).
+ * post[R][C][n] int16 (nullable): the final L in codeword order; post_err counts L < 0 against the TX bits.
+ * One workgroup per codeword as in vaeq_ldpc_decode, the state in LDS: vaeq_ldpc_q_lds_bytes(mb, nb, Z) = 2 n (L as int16, padded to a word)
+ * + n (the TX bits as bytes, padded to a word) + 8 m (one dword m1 | m2 << 8 | idx << 16 | sigma << 24 and one dword of signs per check), at most
+ * 64 KiB; VAEQ_ERR_SHAPE from that call outside the ranges of mb, nb and Z.  Integers and a fixed order: two calls give identical bits.
+ * Refusals, all before any HIP call and in vaeq_ldpc_decode's order: R == 0 is VAEQ_OK (its pointers may be NULL); a NULL shifts_host, llr, bits
+ * or out is VAEQ_ERR_NULL, before any shape rule; then VAEQ_ERR_SHAPE for vaeq_ldpc_decode's shape rules with this state size and the fit rule of
+ * the depth, and for qbits outside 2 .. 8, abits outside qbits .. 15, a scale that is not finite or <= 0, num outside 1 .. 8, beta outside
+ * 0 .. 127, depth < 0 or depth > C, and last the table's rules. */
+int vaeq_ldpc_decode_q(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t mb, int32_t nb, int32_t Z,
+                       const int32_t *shifts_host, const float *llr, const int8_t *bits, int32_t qbits, int32_t abits, float scale, int32_t num,
+                       int32_t beta, int32_t max_iter, int32_t *out, int16_t *post, void *stream);
+int64_t vaeq_ldpc_q_lds_bytes(int32_t mb, int32_t nb, int32_t Z);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

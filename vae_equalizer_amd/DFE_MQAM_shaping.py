@@ -68,7 +68,7 @@ n1 = (lmmse_filter_order - 1) // 2 + 1
 N_SHIFT_LMMSE, N_SHIFT_DFE = 21, 24                    # find_shift_symb lags (:280, :292)
 
 info_metrics = False    # True: main() also returns the info dicts of both curves (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp)
-fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None): main() also returns engine.ldpc_decode's figures of both curves' LLRs
+fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None; quant=dict(bits=5) decodes in fixed point and takes no alpha): main() also returns engine.ldpc_decode's figures of both curves' LLRs
 base_seed = None        # int -> reproducible frames (the reference's stream under the same seed); None = like the reference
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
 
@@ -200,8 +200,8 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
     Every other output is the same with and without it.
     With fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) also fec_mmse and fec_dfe ON THE DEVICE: engine.ldpc_decode's
     figures of those LLRs (computed for it; llr_* itself is returned only with want_llr), all num_snr x num_epochs frames as the run axis of one
-    call per curve: the counters [num_snr, num_epochs, C], the rates [num_snr, num_epochs].  A bad fec dict is a ValueError before anything is
-    allocated or launched."""
+    call per curve: the counters [num_snr, num_epochs, C], the rates [num_snr, num_epochs].  A quant=dict(bits, scale=None, app_bits=None, num=6, beta=0) in fec decodes in
+    fixed point (vaeq_ldpc_decode_q; no alpha then).  A bad fec dict is a ValueError before anything is allocated or launched."""
     from .dp_runs import default_device, fresh_seed, resolve_generator
     from .engine import awgn_dfe, awgn_dfe_soft, awgn_lmmse_eval, awgn_track_info, awgn_track_llr, check_fec, fec_figures, label_bits
     check_fec(fec)
@@ -246,7 +246,7 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
                 if want_llr:
                     info["llr_" + key] = dict(llr=llr.reshape(S, E, *llr.shape[1:]), bits=bits, hyp=fig["hyp"].reshape(S, E))
                 if fec is not None:
-                    info["fec_" + key] = {k: v.reshape(S, E, *v.shape[1:])
+                    info["fec_" + key] = {k: v.reshape(S, E, *v.shape[1:]) if torch.is_tensor(v) else v   # ("quant": the resolved dict)
                                           for k, v in fec_figures(dict(llr=llr, bits=bits.reshape(R, *bits.shape[2:])), fec).items()}
     out = dict(SER_mmse=ser_m.cpu().reshape(S, E), SER_dfe=r["ser"].cpu().reshape(S, E), shift_mmse=sh_m.cpu().numpy().reshape(S, E),
                shift_dfe=r["shift"].cpu().numpy().reshape(S, E), repairs=r["repairs"].cpu().numpy().reshape(S, E), C=r["C"], W=r["W"])

@@ -15,7 +15,7 @@ from . import channel as ch
 from . import epilogue as epi
 from . import shared_funcs as sfun
 from .dp_runs import INFO_FLOAT, INFO_INT, DPRun, _host_pool, check_one_symb_rate, default_device, fresh_seed, resolve_generator  # noqa: F401
-from .engine import cma, cpe, fec_figures, soft_demap
+from .engine import check_fec, cma, cpe, fec_figures, soft_demap
 
 N_CUT = 10   # symbols cut at both frame ends before the phase estimation (func_CMA_DP_MQAM_shaping.py:26,39)
 
@@ -75,7 +75,10 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
                under the winning hypothesis of one cma_epilogue_info call (want_info's, when that is on), and engine.label_bits of the cut TX
                reference.  Every other output is the same with and without it.
     fec:       dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75): also engine.ldpc_decode's figures of the LAST frame's LLRs (the pass
-               want_llr runs; "llr" itself is returned only with want_llr) under "fec", on the device.  None: no output changes."""
+               want_llr runs; "llr" itself is returned only with want_llr) under "fec", on the device.  None: no output changes.
+               quant=dict(bits, scale=None, app_bits=None, num=6, beta=0) in it decodes in fixed point (vaeq_ldpc_decode_q: what the scale of
+               the LLRs costs after FEC; no alpha then).  A bad fec dict is a ValueError before anything is allocated or launched."""
+    check_fec(fec)
     if mode not in ("CMA", "CMAbatch", "CMAflex"):
         raise ValueError(f"unknown CMA variant {mode!r}")
     device = default_device() if device is None else torch.device(device)

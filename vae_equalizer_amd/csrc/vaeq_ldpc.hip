@@ -4,6 +4,7 @@
 // the sweep's random symbols, so the decoder works towards their syndrome (coset decoding).  Two entry points, one kernel: vaeq_ldpc_decode maps
 // bit-packed contiguous codewords onto the frame, vaeq_ldpc_decode_il puts a symbol interleaver over groups of `depth` codewords in front; the
 // choice is a template argument of the kernel and touches its input gather alone.
+// The envelope, the table and its packer, the edge walker and the gather are in vaeq_ldpc.h, shared with the fixed-point decoder (vaeq_ldpc_q.hip).
 //
 // One codeword per workgroup, one thread per check of the layer in flight (Z checks, blockDim = Z rounded up to whole waves).  The whole state
 // lives in LDS: L[n] f32, the TX bits [n] as bytes, and per check the compressed message (m1, m2, idx | sigma << 8, signs), 16 bytes, as four
@@ -21,53 +22,11 @@
 
 #include "vaeq.h"
 #include "vaeq_launch.h"
+#include "vaeq_ldpc.h"
 
 namespace vaeq {
 
-constexpr int LDPC_MB = 8, LDPC_NB = 64, LDPC_ROW = 32, LDPC_Z = 512, LDPC_ITER = 100, LDPC_W = 64;
-constexpr int64_t LDPC_STATE_MAX = 64 * 1024;
-
-// Row l: edges e < wt[l] in ascending block column, two per dword, edge e in bits 16 (e & 1) .. of dword e / 2 as column << 9 | shift.
-struct ldpc_table {
-    uint4 row[LDPC_MB][LDPC_ROW / 8];
-    uint64_t wt;                                               // byte l: the edges of row l
-};
-static_assert(sizeof(ldpc_table) <= 1024, "the table travels in the kernel arguments");
-
 inline int64_t ldpc_state_bytes(int64_t mb, int64_t nb, int64_t Z) { return 4 * nb * Z + ((nb * Z + 3) & ~(int64_t)3) + 16 * mb * Z; }
-
-// A loaded value stays where it is: without this the backend sinks each read into the branch that uses it, and every read waits alone.
-__device__ __forceinline__ void ldpc_pin(float &x) { asm volatile("" : "+v"(x)); }
-__device__ __forceinline__ void ldpc_pin(uint32_t &x) { asm volatile("" : "+v"(x)); }
-
-// f(e, valid, v, x) for the edges of check i of a layer, eight at a time: v the variable of edge e, x = ld(v), all eight reads in flight
-// before the first use.  The four groups are unrolled, so e is a constant in f and arrays indexed by it stay in registers.  The last group of a
-// row may hold edges past wt (valid = false, wave-uniform): their table entry is 0, so they read variable i, an address inside L, and f must
-// leave no trace of them.
-template <class LD, class F>
-__device__ __forceinline__ void ldpc_edges(const uint4 *row, int wt, int Z, int i, LD &&ld, F &&f)
-{
-#pragma unroll
-    for (int g = 0; g < LDPC_ROW / 8; g++) {
-        if (8 * g >= wt) break;
-        const uint4 pk = row[g];
-        const uint32_t d[4] = {pk.x, pk.y, pk.z, pk.w};
-        int v[8];
-        decltype(ld(0)) x[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t h = (d[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-            const uint32_t j = (uint32_t)i + (h & 511u);       // (i + s) mod Z: j - Z wraps past j exactly when j < Z
-            v[k] = (int)((h >> 9) * (uint32_t)Z + min(j, j - (uint32_t)Z));
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) x[k] = ld(v[k]);
-#pragma unroll
-        for (int k = 0; k < 8; k++) ldpc_pin(x[k]);
-#pragma unroll
-        for (int k = 0; k < 8; k++) f(8 * g + k, 8 * g + k < wt, v[k], x[k]);
-    }
-}
 
 // x with its sign flipped when bit e of sg is set (an exact negation, of zero too)
 __device__ __forceinline__ float ldpc_signed(float x, uint32_t sg, int e) { return __uint_as_float(__float_as_uint(x) ^ ((sg >> e) << 31)); }
@@ -91,54 +50,15 @@ __global__ __launch_bounds__(LDPC_Z) void ldpc_decode_kernel(const ldpc_table ta
     mb = min(mb, LDPC_MB);
     max_iter = min(max_iter, LDPC_ITER);
 
-    // Contiguous: bit j of this codeword is global bit g = cw n + j of the run: symbol t0 + g / w, plane g % w.  Consecutive lanes on consecutive
-    // symbols of one plane.  Interleaved: symbol u of the codeword is symbol base + u D + d of the frame, its plane p is bit u w + p; consecutive
-    // lanes on consecutive u, D symbols apart -- the D workgroups of a group have adjacent block indices and read the same lines between them,
-    // and L2 hides it: +0.36 ms on 6.68 ms where the call is almost all gather (lanes on consecutive frame symbols, each keeping its
-    // own residue, run the loop body D times as often and take 28.6 ms).
-    const long long g0 = (long long)cw * n;
-    long long first, j_lo;                                     // the frame's symbol and the codeword's bit (of plane 0) at s = 0
-    int nsym, step;
-    if constexpr (IL) {
-        const int S = (n + w - 1) / w, k0 = cw / depth * depth;
-        step = min(depth, C - k0);
-        first = t0 + (long long)k0 * S + (cw - k0);
-        j_lo = 0;
-        nsym = S;
-    } else {
-        const long long s_lo = g0 / w;
-        step = 1;
-        first = t0 + s_lo;
-        j_lo = s_lo * w - g0;
-        nsym = (int)((g0 + n - 1) / w - s_lo) + 1;
-    }
+    const ldpc_window win = ldpc_window_of<IL>(cw, C, w, t0, depth, n);
     if (tid < 3) cnt[tid] = 0;
     int pre = 0, era = 0;
-    for (int s = tid; s < nsym; s += NT) {                     // four planes of a symbol at a time, their loads in flight together
-        const size_t sym = (size_t)first + (size_t)s * (size_t)step;
-        for (int p0 = 0; p0 < w; p0 += 4) {
-            float x[4];
-            uint32_t b[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const size_t at = (run * (size_t)w + min(p0 + k, w - 1)) * (size_t)N + sym;
-                x[k] = llr[at];
-                b[k] = (uint32_t)bits[at] & 1u;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) { ldpc_pin(x[k]); ldpc_pin(b[k]); }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const long long j = j_lo + (long long)s * w + (p0 + k);
-                if (p0 + k < w && j >= 0 && j < n) {
-                    L[j] = x[k];
-                    B[j] = (uint8_t)b[k];
-                    pre += (uint32_t)(x[k] < 0.f) != b[k];
-                    era += x[k] == 0.f;
-                }
-            }
-        }
-    }
+    ldpc_gather(win, run, N, w, n, tid, NT, llr, bits, [&](long long j, float x, uint32_t b) {
+        L[j] = x;
+        B[j] = (uint8_t)b;
+        pre += (uint32_t)(x < 0.f) != b;
+        era += x == 0.f;
+    });
     __syncthreads();
     if (pre) atomicAdd(&cnt[1], pre);
     if (era) atomicAdd(&cnt[2], era);
@@ -229,35 +149,6 @@ __global__ __launch_bounds__(LDPC_Z) void ldpc_decode_kernel(const ldpc_table ta
     }
 }
 
-// shifts[mb][nb] -> the kernel's table; false when the table leaves the envelope
-static bool ldpc_pack(int mb, int nb, int Z, const int32_t *shifts, ldpc_table *tab)
-{
-    uint32_t d[LDPC_MB][LDPC_ROW / 2] = {};
-    tab->wt = 0;
-    for (int l = 0; l < mb; l++) {
-        int wt = 0;
-        for (int c = 0; c < nb; c++) {
-            const int32_t s = shifts[l * nb + c];
-            if (s < -1 || s >= Z) return false;
-            if (s < 0) continue;
-            if (wt == LDPC_ROW) return false;
-            d[l][wt >> 1] |= ((uint32_t)c << 9 | (uint32_t)s) << (16 * (wt & 1));
-            wt++;
-        }
-        if (wt < 2) return false;
-        tab->wt |= (uint64_t)wt << (8 * l);
-    }
-    for (int l = 0; l < LDPC_MB; l++) {
-        for (int k = 0; k < LDPC_ROW / 8; k++) tab->row[l][k] = make_uint4(d[l][4 * k], d[l][4 * k + 1], d[l][4 * k + 2], d[l][4 * k + 3]);
-    }
-    return true;
-}
-
-static bool ldpc_dims_ok(int64_t mb, int64_t nb, int64_t Z)
-{
-    return mb >= 1 && mb <= LDPC_MB && nb >= 2 && nb <= LDPC_NB && Z >= 2 && Z <= LDPC_Z;
-}
-
 }  // namespace vaeq
 
 extern "C" int64_t vaeq_ldpc_lds_bytes(int32_t mb, int32_t nb, int32_t Z)
@@ -274,12 +165,8 @@ static int ldpc_decode_any(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t
 {
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!shifts_host || !llr || !bits || !out) return VAEQ_ERR_NULL;
-    if (R < 0 || C < 1 || N < 1 || N > 0x3fffffff || w < 1 || w > LDPC_W || t0 < 0 || t0 > N || max_iter < 1 || max_iter > LDPC_ITER ||
-        !ldpc_dims_ok(mb, nb, Z) || (il && (depth < 1 || depth > C)))
-        return VAEQ_ERR_SHAPE;
-    const int64_t n = (int64_t)nb * Z, lds = ldpc_state_bytes(mb, nb, Z);
-    const bool fits = il ? t0 + (int64_t)C * ((n + w - 1) / w) <= N : t0 * w + (int64_t)C * n <= N * w;
-    if (lds > LDPC_STATE_MAX || !fits || (int64_t)R * C > 0x7fffffff) return VAEQ_ERR_SHAPE;
+    const int64_t lds = ldpc_state_bytes(mb, nb, Z);
+    if (!ldpc_shape_ok(R, C, N, w, t0, depth, mb, nb, Z, max_iter, lds, il)) return VAEQ_ERR_SHAPE;
     ldpc_table tab;
     if (!ldpc_pack(mb, nb, Z, shifts_host, &tab)) return VAEQ_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

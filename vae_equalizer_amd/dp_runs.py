@@ -15,7 +15,7 @@ import torch
 
 from . import channel as ch
 from . import shared_funcs as sfun
-from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info, dp_epilogue_llr, fec_figures, label_bits  # noqa: F401
+from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info, dp_epilogue_llr, check_fec, fec_figures, label_bits  # noqa: F401
 
 
 @dataclass
@@ -125,7 +125,10 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
                and engine.label_bits of the frame's TX reference.  Every other output is the same with and without it.
     fec:       dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75): also engine.ldpc_decode's figures of the LAST frame's LLRs (the pass
                want_llr runs; "llr" itself is returned only with want_llr) under "fec", on the device.  None: no output changes.
+               quant=dict(bits, scale=None, app_bits=None, num=6, beta=0) in it decodes in fixed point (vaeq_ldpc_decode_q: what the scale of
+               the LLRs costs after FEC; no alpha then).  A bad fec dict is a ValueError before anything is allocated or launched.
     """
+    check_fec(fec)
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
     generator = resolve_generator(generator, any(r.seed is not None for r in runs))
@@ -274,7 +277,8 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
         main.wait_stream(s_epi)
         main.wait_stream(s_gen)
         for t in (*state.get("llr", {}).values(), *state.get("fec", {}).values()):   # made on s_epi, used by the caller on main from here on
-            t.record_stream(main)
+            if torch.is_tensor(t):                                                # (fec["quant"] is the resolved dict of a fixed-point decode)
+                t.record_stream(main)
     else:
         for frame in range(num_frames):
             rx, data = make_frame(frame)

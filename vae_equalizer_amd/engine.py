@@ -695,15 +695,44 @@ def array_code(mb, nb, Z):
     return LdpcCode(np.outer(np.arange(mb), np.arange(nb)) % Z, Z)
 
 
-def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=0.75, want_post=False, depth=None):
+QUANT_KEYS = ("bits", "scale", "app_bits", "num", "beta")
+
+
+def resolve_quant(quant):
+    """ldpc_decode's quant= dict(bits, scale=None, app_bits=None, num=6, beta=0) with its defaults filled in: app_bits = bits + 2 and
+    scale = 2 ** (bits - 5), a clip near +-16 nats at every width and one nat per step at 5 bits.  ValueError for an unknown key, a missing or
+    non-integer bits; the ranges are vaeq_ldpc_decode_q's to refuse."""
+    import numbers
+    if not isinstance(quant, dict) or set(quant) - set(QUANT_KEYS) or "bits" not in quant:
+        raise ValueError(f"quant takes a dict of {', '.join(QUANT_KEYS)} with bits in it; got {sorted(quant) if isinstance(quant, dict) else quant!r}")
+    bits = quant["bits"]
+    if not isinstance(bits, numbers.Integral) or isinstance(bits, bool):
+        raise ValueError(f"quant['bits'] is an integer number of bits, got {bits!r}")
+    bits = int(bits)
+    scale, app = quant.get("scale"), quant.get("app_bits")
+    return dict(bits=bits, scale=2.0 ** (bits - 5) if scale is None else float(scale), app_bits=bits + 2 if app is None else int(app),
+                num=int(quant.get("num", 6)), beta=int(quant.get("beta", 0)))
+
+
+def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, want_post=False, depth=None, quant=None):
     """Post-FEC figures of per-bit LLRs on the device (vaeq_ldpc_decode): layered normalized min-sum towards the syndrome of the TX bits (no
     encoder).  llr f32 and bits int8 of one shape, [R,2,2b,N] (dp_epilogue_llr / cma_epilogue_llr with label_bits) or [R,w,N] (awgn_llr,
     awgn_track_llr); bit j of codeword c of a run is global bit c n + j, at symbol t0 + (c n + j) // w in plane (c n + j) % w.  codewords: per
     run, default the most that fit behind t0.  -> dict(iters, ok, bit_err, pre_err, erased [R,C] int64; BER_post[R], BER_pre[R], FER[R] f32
-    (FER: the share of codewords with bit_err > 0); post[R,C,n] f32, the final LLRs in codeword order, if want_post).
+    (FER: the share of codewords with bit_err > 0); post[R,C,n] f32, the final LLRs in codeword order, if want_post).  alpha defaults to 0.75.
     depth: an int puts a symbol interleaver over groups of `depth` codewords in front of the decoder (vaeq_ldpc_decode_il): codewords of
     S = ceil(n / w) whole symbols, symbol u of the codeword with local index d of a group of D at symbol base + u D + d; codewords then defaults
-    to (N - t0) // S.  None: the contiguous bit-packed codewords above."""
+    to (N - t0) // S.  None: the contiguous bit-packed codewords above.
+    quant: dict(bits, scale=None, app_bits=None, num=6, beta=0) decodes in fixed point instead (vaeq_ldpc_decode_q): LLRs quantised to `bits`
+    bits as rint(llr * scale) (default scale 2 ** (bits - 5)), `bits`-bit check messages, a-posteriori values saturating at app_bits (default
+    bits + 2) bits, messages normalised as max(((num m + 4) >> 3) - beta, 0).  Unlike the float decoder this one sees the scale of the LLRs: what
+    a wrong noise variance costs after FEC.  alpha has no meaning there and is a ValueError if passed.  The same dict comes back, post int16,
+    erased counting what the quantiser rounded to zero, and the resolved dict under "quant"."""
+    if quant is not None:
+        if alpha is not None:
+            raise ValueError("alpha belongs to the float decoder; the fixed-point one is normalised by quant['num'] and quant['beta']")
+        quant = resolve_quant(quant)
+    alpha = 0.75 if alpha is None else alpha
     if llr.shape != bits.shape or llr.dim() not in (3, 4):
         raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
     dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
@@ -718,14 +747,17 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=0.75, 
     if codewords is None and C_ < 1:
         raise ValueError(f"no codeword of {n} bits fits into {N - int(t0)} symbols of {w} bits")
     out = torch.empty(R, max(C_, 0), 5, dtype=torch.int32, device=dev)
-    post = torch.empty(R, max(C_, 0), n, dtype=torch.float32, device=dev) if want_post else None
+    post = torch.empty(R, max(C_, 0), n, dtype=torch.float32 if quant is None else torch.int16, device=dev) if want_post else None
     with torch.cuda.device(dev):
-        tail = (code.mb, code.nb, code.Z, code.shifts.ctypes.data_as(C.c_void_p), nat.ptr(llr), nat.ptr(bits, torch.int8), float(alpha),
-                int(max_iter), nat.ptr(out, torch.int32), nat.ptr(post), nat.current_stream(dev))
-        if depth is None:
-            nat.check(nat.lib().vaeq_ldpc_decode(R, C_, N, w, int(t0), *tail), "vaeq_ldpc_decode")
+        head = (code.mb, code.nb, code.Z, code.shifts.ctypes.data_as(C.c_void_p), nat.ptr(llr), nat.ptr(bits, torch.int8))
+        tail = (int(max_iter), nat.ptr(out, torch.int32), nat.ptr(post, torch.float32 if quant is None else torch.int16), nat.current_stream(dev))
+        if quant is not None:
+            nat.check(nat.lib().vaeq_ldpc_decode_q(R, C_, N, w, int(t0), 0 if depth is None else int(depth), *head, quant["bits"], quant["app_bits"],
+                                                   quant["scale"], quant["num"], quant["beta"], *tail), "vaeq_ldpc_decode_q")
+        elif depth is None:
+            nat.check(nat.lib().vaeq_ldpc_decode(R, C_, N, w, int(t0), *head, float(alpha), *tail), "vaeq_ldpc_decode")
         else:
-            nat.check(nat.lib().vaeq_ldpc_decode_il(R, C_, N, w, int(t0), int(depth), *tail), "vaeq_ldpc_decode_il")
+            nat.check(nat.lib().vaeq_ldpc_decode_il(R, C_, N, w, int(t0), int(depth), *head, float(alpha), *tail), "vaeq_ldpc_decode_il")
     o = out.long()
     tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)   # a tensor divisor: a true division, not a product with 1 / tot
     ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
@@ -733,21 +765,27 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=0.75, 
                FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float())
     if want_post:
         ret["post"] = post
+    if quant is not None:
+        ret["quant"] = quant
     return ret
 
 
-FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth")
+FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant")
 
 
 def check_fec(fec):
     """ValueError for a fec= dict that fec_figures would refuse (None passes): for a runner to call before it allocates or launches anything."""
     if fec is not None and (set(fec) - set(FEC_KEYS) or "code" not in fec):
         raise ValueError(f"fec takes {', '.join(FEC_KEYS)}; got {sorted(fec)}")
+    if fec is not None and fec.get("quant") is not None:
+        resolve_quant(fec["quant"])
+        if fec.get("alpha") is not None:
+            raise ValueError("fec takes alpha for the float decoder or quant for the fixed-point one, not both")
 
 
 def fec_figures(llr, fec):
-    """The batch runners' fec= : ldpc_decode of an "llr" dict (llr, bits) under fec = dict(code, t0, max_iter, alpha, depth; all but code
-    optional)."""
+    """The batch runners' fec= : ldpc_decode of an "llr" dict (llr, bits) under fec = dict(code, t0, max_iter, alpha, depth, quant; all but code
+    optional; quant = dict(bits, ...) decodes in fixed point, vaeq_ldpc_decode_q)."""
     check_fec(fec)
     return ldpc_decode(llr["llr"], llr["bits"], fec["code"], **{k: v for k, v in fec.items() if k != "code"})
 

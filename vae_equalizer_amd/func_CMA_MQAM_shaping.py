@@ -102,7 +102,7 @@ def run_awgn_cma_batch(runs, mod, sps, M_est, N_valid, N_train, num_epochs, epe,
     want_llr / fec: (SER_valid, info or None, extras), for the LAST evaluated validation only and on the device: with want_llr extras["llr"] =
     dict(llr[R,2b,N_valid] f32 = engine.awgn_track_llr on that validation's CPE output and shift, at the var and edge 11 of the info call and
     under its hyp, bits int8 = engine.label_bits of its TX data, hyp[R]); with fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75,
-    depth=None) extras["fec"] = engine.ldpc_decode's figures of those LLRs.  Both off: no output changes."""
+    depth=None) extras["fec"] = engine.ldpc_decode's figures of those LLRs. A quant=dict(bits, ...) in fec decodes in fixed point (vaeq_ldpc_decode_q).  Both off: no output changes."""
     device = default_device() if device is None else torch.device(device)
     check_fec(fec)
     R = len(runs)

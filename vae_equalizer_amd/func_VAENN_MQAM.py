@@ -152,7 +152,7 @@ def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_vali
     want_llr / fec: (SER_valid, info or None, extras), for the LAST evaluated validation only and on the device: with want_llr extras["llr"] =
     dict(llr[R,2b,N_valid] f32 = NNEngine.llr on that validation's frame and shift under the hyp of NNEngine.info on them, bits int8 =
     engine.label_bits of its TX data, hyp[R]); with fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) extras["fec"] =
-    engine.ldpc_decode's figures of those LLRs.  Both off: no output changes."""
+    engine.ldpc_decode's figures of those LLRs. A quant=dict(bits, ...) in fec decodes in fixed point (vaeq_ldpc_decode_q).  Both off: no output changes."""
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
     t = vaenn_tables(mod, channel, sps)
