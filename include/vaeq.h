@@ -718,6 +718,38 @@ int vaeq_ldpc_decode_q(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, i
                        int32_t beta, int32_t max_iter, int32_t *out, int16_t *post, void *stream);
 int64_t vaeq_ldpc_q_lds_bytes(int32_t mb, int32_t nb, int32_t Z);
 
+/* The outer code behind the LDPC decoders: a bounded-distance hard-decision decoder of a shortened binary BCH code over the payload bits of
+ * `post`, so that the figure an optical-FEC comparison is judged by -- errors after the outer code -- is counted on the device.  As with the inner
+ * code there is no encoder: the result depends on the error pattern alone.
+ * The code: narrow-sense primitive binary BCH over GF(2^m), m in 4 .. 13, designed correction t in 1 .. 16, shortened to n_o bits.  alpha is the
+ * root of the primitive polynomial (bit masks, m = 4 .. 13) 0x13, 0x25, 0x43, 0x89, 0x11D, 0x211, 0x409, 0x805, 0x1053, 0x201B.  Position p of a
+ * codeword belongs to alpha^p; shortening keeps the positions 0 .. n_o - 1.  parity(m, t) = the size of the union of the cyclotomic cosets of
+ * 1 .. 2t modulo 2^m - 1, and parity < n_o <= 2^m - 1.
+ * The payload: the first K bits of every LDPC codeword of n bits, 1 <= K <= n.  A run's payload stream has C K bits, stream bit u = c K + i is bit
+ * i of LDPC codeword c.  C_o outer codewords per run, C_o n_o <= C K; stream bits past C_o n_o belong to no outer codeword.  spread == 0:
+ * position p of outer codeword a is stream bit a n_o + p.  spread == 1: stream bit p C_o + a, a bit interleaver over all outer codewords of the
+ * run, which turns one failed LDPC codeword into a few errors in each outer codeword.
+ * The received bit is post[r][c][i] < 0 (a float NaN and +-0 are bit 0, as in the decoders); post[R][C][n] is float32 (post_i16 == 0) or int16
+ * (post_i16 == 1), the `post` output of the three LDPC calls.  The transmitted bit is bits[r][plane][symbol] of the demappers' [R][w][N] tensor
+ * under the LDPC decoder's own map of codeword c, bit i: depth == 0 vaeq_ldpc_decode's bit-packed map, depth >= 1 vaeq_ldpc_decode_il's;
+ * t0, w, N, n and C as in those calls.  e = received xor transmitted is the error pattern of an outer codeword.
+ * The rule, stated without an algorithm:  S_j = xor over the positions p with e_p = 1 of alpha^(j p), j = 1 .. 2t.
+ *   status 0   every S_j is zero; nothing is flipped.
+ *   status 1   there is a set of at most t positions, all below n_o, whose S_1 .. S_2t equal those of e.  That set is unique; it is flipped.
+ *   status 2   otherwise; nothing is flipped.
+ * (With an error locator Lambda of degree L: status 1 iff L <= t, Lambda has exactly L roots alpha^(-p), and all of them have p < n_o.)
+ * out[R][C_o][4] int32 = status, pre_err (the weight of e), post_err (the weight after the flips), nflip.  loc[R][C_o][t] int16 (nullable): the
+ * flipped positions ascending, padded with -1.  A miscorrection is status 1 with post_err > 0, an undetected error status 0 with pre_err > 0.
+ * Workgroups of four waves, the exp / log tables of GF(2^m) in LDS (2^(m+2) bytes), one wave per outer codeword.  Integers only: two calls give
+ * identical bits.
+ * Refusals, all before any HIP call: R == 0 is VAEQ_OK (its pointers may be NULL); a NULL post, bits or out is VAEQ_ERR_NULL, before any shape
+ * rule; then VAEQ_ERR_SHAPE for the tensor rules of the LDPC calls (R < 0, C < 1, R C > 0x7fffffff, N < 1, N > 0x3fffffff, w outside 1 .. 64,
+ * t0 < 0, t0 > N), depth outside 0 .. C, n outside 2 .. 32768 and that depth's fit rule (t0 w + C n > N w, or t0 + C ceil(n / w) > N); then
+ * VAEQ_ERR_SHAPE for K outside 1 .. n, m outside 4 .. 13, t outside 1 .. 16, n_o outside parity + 1 .. 2^m - 1, spread outside 0 .. 1, post_i16
+ * outside 0 .. 1, C_o < 1 and R C_o > 0x7fffffff; last VAEQ_ERR_SHAPE for C_o n_o > C K. */
+int vaeq_bch_outer(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t n, int32_t K, int32_t m, int32_t t, int32_t n_o,
+                   int32_t C_o, int32_t spread, const void *post, int32_t post_i16, const int8_t *bits, int32_t *out, int16_t *loc, void *stream);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

@@ -68,7 +68,7 @@ n1 = (lmmse_filter_order - 1) // 2 + 1
 N_SHIFT_LMMSE, N_SHIFT_DFE = 21, 24                    # find_shift_symb lags (:280, :292)
 
 info_metrics = False    # True: main() also returns the info dicts of both curves (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp)
-fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None; quant=dict(bits=5) decodes in fixed point and takes no alpha): main() also returns engine.ldpc_decode's figures of both curves' LLRs
+fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=engine.BchCode, ...) puts engine.bch_outer behind it, and the .mat also gains BER_outer and FER_outer): main() also returns engine.ldpc_decode's figures of both curves' LLRs
 base_seed = None        # int -> reproducible frames (the reference's stream under the same seed); None = like the reference
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
 
@@ -237,6 +237,12 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
         var = [10 ** (-SNRs[k // E] / 10) for k in range(R)]
         on_grid = lambda d: {k: v.cpu().reshape(S, E) for k, v in d.items()}  # noqa: E731
         bits = label_bits(data, len(amps)).reshape(S, E, -1, data.shape[-1]) if need_llr else None
+
+        def on_se(v):                                                           # fec_figures' [R, ...] tensors on the (SNR, epoch) grid; "outer" is a dict of them, "quant" the resolved dict
+            if torch.is_tensor(v):
+                return v.reshape(S, E, *v.shape[1:])
+            return {k: on_se(x) for k, x in v.items()} if isinstance(v, dict) else v
+
         for key, z, sh in (("mmse", out_m, sh_m), ("dfe", awgn_dfe_soft(r["ff"], fb, r["dec"], amps), r["shift"])):
             fig = awgn_track_info(z, data, amps, P, var, sh, N_cut + 11)
             if want_info:
@@ -246,8 +252,7 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
                 if want_llr:
                     info["llr_" + key] = dict(llr=llr.reshape(S, E, *llr.shape[1:]), bits=bits, hyp=fig["hyp"].reshape(S, E))
                 if fec is not None:
-                    info["fec_" + key] = {k: v.reshape(S, E, *v.shape[1:]) if torch.is_tensor(v) else v   # ("quant": the resolved dict)
-                                          for k, v in fec_figures(dict(llr=llr, bits=bits.reshape(R, *bits.shape[2:])), fec).items()}
+                    info["fec_" + key] = on_se(fec_figures(dict(llr=llr, bits=bits.reshape(R, *bits.shape[2:])), fec))
     out = dict(SER_mmse=ser_m.cpu().reshape(S, E), SER_dfe=r["ser"].cpu().reshape(S, E), shift_mmse=sh_m.cpu().numpy().reshape(S, E),
                shift_dfe=r["shift"].cpu().numpy().reshape(S, E), repairs=r["repairs"].cpu().numpy().reshape(S, E), C=r["C"], W=r["W"])
     out.update(info)

@@ -41,7 +41,7 @@ N_frame_max = 10000
 savePATH = ""
 base_seed = None    # int -> reproducible runs (run i of the flattened sweep uses base_seed + 1000*i); None = like the reference
 info_metrics = False  # True (every loss_type): the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), shaped like SER with a leading axis of 2
-fec_metrics = None  # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None; quant=dict(bits=5) decodes in fixed point and takes no alpha) (every loss_type): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords) of the last frame's LLRs, each shaped like SER without its first and last axes
+fec_metrics = None  # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=engine.BchCode, ...) puts engine.bch_outer behind it, and the .mat also gains BER_outer and FER_outer) (every loss_type): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords) of the last frame's LLRs, each shaped like SER without its first and last axes
 generator = None    # None: "hip" (on-device channel simulator) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set; or force "numpy" / "hip" / "torch"
 
 
@@ -78,8 +78,8 @@ def main():
     key = lambda i: (points[i][1]["M"], points[i][1]["batch_len"], points[i][1]["flex_step"], points[i][1]["symb_rate"])
     shapes = sorted({key(i) for i in mine})
     n_col = 16 if info_metrics else 8                      # with info_metrics: + GMI[2] | NGMI[2] | AIR[2] | BER[2]
-    c_fec, n_fec = n_col, 0 if fec_metrics is None else len(sweep.FEC_KEYS)
-    n_col += n_fec                                         # with fec_metrics: + BER_post | FER | BER_pre_fec | fec_iters (broadcast)
+    c_fec, n_fec = n_col, len(sweep.fec_keys(fec_metrics))
+    n_col += n_fec                                         # with fec_metrics: + BER_post | FER | BER_pre_fec | fec_iters (| BER_outer | FER_outer with an outer code) (broadcast)
     local = torch.zeros(len(mine), n_col, num_frames, dtype=torch.float32)
     for (M, batch_len, fs, rate) in shapes:
         sel = [k for k, i in enumerate(mine) if key(i) == (M, batch_len, fs, rate)]
@@ -124,7 +124,7 @@ def main():
             for k, (idx, _) in enumerate(points):
                 arr[(slice(None),) + idx] = rows[k, 8 + 2 * j:10 + 2 * j]
             save_dict[name_k] = arr.numpy()
-    for j, name_k in enumerate(sweep.FEC_KEYS[:n_fec]):
+    for j, name_k in enumerate(sweep.fec_keys(fec_metrics)):
         arr = torch.empty(*shape_tail, dtype=torch.float32)
         for k, (idx, _) in enumerate(points):
             arr[idx] = rows[k, c_fec + j, 0]

@@ -23,7 +23,7 @@ savePATH = ""
 base_seed = None        # int -> reproducible runs; None = like the reference
 info_metrics = False    # True: the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), each shaped like SER
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
-fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None; quant=dict(bits=5) decodes in fixed point and takes no alpha): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords) of the last validation's LLRs, each shaped like SER without its last axis
+fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=engine.BchCode, ...) puts engine.bch_outer behind it, and the .mat also gains BER_outer and FER_outer): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords) of the last validation's LLRs, each shaped like SER without its last axis
 INFO_KEYS = ("GMI", "NGMI", "AIR", "BER")
 
 
@@ -38,7 +38,7 @@ def main():
     from . import sweep
     from .func_VAELE_MQAM_shaping import run_awgn_batch
 
-    keys, n_fec = INFO_KEYS if info_metrics else (), 0 if fec_metrics is None else len(sweep.FEC_KEYS)
+    keys, n_fec = INFO_KEYS if info_metrics else (), len(sweep.fec_keys(fec_metrics))
 
     def run_batch(shape, pts, seeds, device, seed):
         M, N_train = shape
@@ -46,7 +46,7 @@ def main():
         r = run_awgn_batch(runs, mod, sps, M, N_train, N_valid, train_len, num_epochs, epe, channel, device=device, generator=generator, seed=seed,
                            want_info=info_metrics, fec=fec_metrics)
         if fec_metrics is not None:
-            return sweep.fec_rows(r, keys)                                        # per run: SER | keys | BER_post | FER | BER_pre_fec | fec_iters
+            return sweep.fec_rows(r, keys)                                        # per run: SER | keys | BER_post | FER | BER_pre_fec | fec_iters (| BER_outer | FER_outer)
         return sweep.info_rows(r, INFO_KEYS) if info_metrics else r               # per run: SER | GMI | NGMI | AIR | BER
 
     n_eval = num_epochs // epe
@@ -59,7 +59,7 @@ def main():
     name = f"{savePATH}SERvsSNR_VAELE_shaping_{nu}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
     save_dict = {'SER': out[0].numpy(), 'SNR': SNR_vec, 'M': M_vec, 'lr': lr_optim_vec, 'N_train': N_train_vec, 'nu': nu_vec}
     save_dict.update({k: arr.numpy() for k, arr in zip(keys, out[1:])})
-    save_dict.update({k: arr[..., -1].numpy() for k, arr in zip(sweep.FEC_KEYS[:n_fec], out[1 + len(keys):])})
+    save_dict.update({k: arr[..., -1].numpy() for k, arr in zip(sweep.fec_keys(fec_metrics), out[1 + len(keys):])})
     io.savemat(name, {'dict': save_dict})
     return name, save_dict
 

@@ -24,7 +24,7 @@ savePATH = ""
 base_seed = None        # int -> reproducible runs; None = like the reference
 info_metrics = False    # True: the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), each shaped like SER
 generator = "hip"       # "hip": on-device channel model; "numpy": host restatement per run
-fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None; quant=dict(bits=5) decodes in fixed point and takes no alpha): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords) of the last validation's LLRs, each shaped like SER without its last axis
+fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=engine.BchCode, ...) puts engine.bch_outer behind it, and the .mat also gains BER_outer and FER_outer): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords) of the last validation's LLRs, each shaped like SER without its last axis
 INFO_KEYS = ("GMI", "NGMI", "AIR", "BER")
 
 
@@ -40,7 +40,7 @@ def main():
     from . import sweep
     from .func_VAENN_MQAM import run_vaenn_batch
 
-    keys, n_fec = INFO_KEYS if info_metrics else (), 0 if fec_metrics is None else len(sweep.FEC_KEYS)
+    keys, n_fec = INFO_KEYS if info_metrics else (), len(sweep.fec_keys(fec_metrics))
     name = save_dict = None
     for j, net_type in enumerate(net_type_vec):
         def run_batch(shape, pts, seeds, device, seed):
@@ -49,7 +49,7 @@ def main():
             r = run_vaenn_batch(runs, mod, sps, M, k1, k2, batch_len, N_valid, train_len, num_epochs, epe, channel, device=device,
                                 generator=generator, seed=seed, net_type=net_type, want_info=info_metrics, fec=fec_metrics)
             if fec_metrics is not None:
-                return sweep.fec_rows(r, keys)                                        # per run: SER | keys | BER_post | FER | BER_pre_fec | fec_iters
+                return sweep.fec_rows(r, keys)                                        # per run: SER | keys | BER_post | FER | BER_pre_fec | fec_iters (| BER_outer | FER_outer)
             return sweep.info_rows(r, INFO_KEYS) if info_metrics else r           # per run: SER | GMI | NGMI | AIR | BER
 
         n_eval = num_epochs // epe
@@ -62,7 +62,7 @@ def main():
         name = f"{savePATH}SERvsSNR_{net_type}_{channel}_{mod}_{sps}_{N_valid}_{epe}_{train_len}_{datetime.today().strftime('%y%m%d%H%M%S')}.mat"
         save_dict = {'SER': out[0].numpy(), 'SNR': SNR_vec, 'k2': k2_vec, 'k1': k1_vec, 'M': M_vec, 'lr': lr_optim_vec, 'N_train': batch_len_vec}
         save_dict.update({k: arr.numpy() for k, arr in zip(keys, out[1:])})
-        save_dict.update({k: arr[..., -1].numpy() for k, arr in zip(sweep.FEC_KEYS[:n_fec], out[1 + len(keys):])})
+        save_dict.update({k: arr[..., -1].numpy() for k, arr in zip(sweep.fec_keys(fec_metrics), out[1 + len(keys):])})
         io.savemat(name, {'dict': save_dict})
     return (name, save_dict) if sweep.dist_info()[0] == 0 else None
 

@@ -113,6 +113,23 @@ __device__ __forceinline__ void ldpc_gather(const ldpc_window win, size_t run, l
     }
 }
 
+// The same map for one bit (vaeq_bch.hip, which visits the payload bits of a codeword in its own order): where bit j of codeword cw lies in a
+// run's [w][N] tensors, as ldpc_window_of and ldpc_gather above walk it.  I, the type of every index and of the result: uint32_t where C n < 2^31
+// and w N < 2^32 (no 64-bit multiply per bit), else uint64_t.
+template <bool IL, class I>
+__device__ __forceinline__ I ldpc_bit_at(I cw, uint32_t j, int C, int w, long long N, long long t0, int depth, int n)
+{
+    if constexpr (IL) {
+        const uint32_t S = ((uint32_t)n + (uint32_t)w - 1u) / (uint32_t)w, u = j / (uint32_t)w;
+        const I k0 = cw / (I)depth * (I)depth;
+        const I D = (I)C - k0 < (I)depth ? (I)C - k0 : (I)depth;
+        return (I)(j - u * (uint32_t)w) * (I)N + (I)t0 + k0 * (I)S + (I)u * D + (cw - k0);
+    } else {
+        const I g = cw * (I)n + (I)j, s = g / (I)w;
+        return (g - s * (I)w) * (I)N + (I)t0 + s;
+    }
+}
+
 // shifts[mb][nb] -> the kernel's table; false when the table leaves the envelope
 static inline bool ldpc_pack(int mb, int nb, int Z, const int32_t *shifts, ldpc_table *tab)
 {

@@ -714,7 +714,14 @@ def resolve_quant(quant):
                 num=int(quant.get("num", 6)), beta=int(quant.get("beta", 0)))
 
 
-def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, want_post=False, depth=None, quant=None):
+def _ldpc_fit(N, w, n, t0, depth):
+    """The most codewords of n bits that fit behind t0 into N symbols of w bits: bit-packed (depth None) or in whole symbols."""
+    if depth is None:
+        return (N - int(t0)) * w // n if n > 0 else 0
+    return (N - int(t0)) // -(-n // w) if n > 0 and w > 0 else 0
+
+
+def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, want_post=False, depth=None, quant=None, outer=None):
     """Post-FEC figures of per-bit LLRs on the device (vaeq_ldpc_decode): layered normalized min-sum towards the syndrome of the TX bits (no
     encoder).  llr f32 and bits int8 of one shape, [R,2,2b,N] (dp_epilogue_llr / cma_epilogue_llr with label_bits) or [R,w,N] (awgn_llr,
     awgn_track_llr); bit j of codeword c of a run is global bit c n + j, at symbol t0 + (c n + j) // w in plane (c n + j) % w.  codewords: per
@@ -727,7 +734,12 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, 
     bits as rint(llr * scale) (default scale 2 ** (bits - 5)), `bits`-bit check messages, a-posteriori values saturating at app_bits (default
     bits + 2) bits, messages normalised as max(((num m + 4) >> 3) - beta, 0).  Unlike the float decoder this one sees the scale of the LLRs: what
     a wrong noise variance costs after FEC.  alpha has no meaning there and is a ValueError if passed.  The same dict comes back, post int16,
-    erased counting what the quantiser rounded to zero, and the resolved dict under "quant"."""
+    erased counting what the quantiser rounded to zero, and the resolved dict under "quant".
+    outer: dict(code=BchCode, payload=None, spread=True, codewords=None) puts a hard-decision outer decoder behind this one: bch_outer on the
+    final LLRs (kept on the device, returned only with want_post), its dict under "outer".  payload defaults to (nb - mb) Z, the first bits of
+    every codeword."""
+    if outer is not None:
+        outer = resolve_outer(outer, code)
     if quant is not None:
         if alpha is not None:
             raise ValueError("alpha belongs to the float decoder; the fixed-point one is normalised by quant['num'] and quant['beta']")
@@ -739,15 +751,11 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, 
     llr = llr.reshape(R, -1, N).contiguous()
     bits = bits.reshape(R, -1, N).contiguous()
     w, n = llr.shape[1], code.n
-    if depth is None:
-        fit = (N - int(t0)) * w // n if n > 0 else 0
-    else:
-        fit = (N - int(t0)) // -(-n // w) if n > 0 and w > 0 else 0
-    C_ = int(codewords) if codewords is not None else fit
+    C_ = int(codewords) if codewords is not None else _ldpc_fit(N, w, n, t0, depth)
     if codewords is None and C_ < 1:
         raise ValueError(f"no codeword of {n} bits fits into {N - int(t0)} symbols of {w} bits")
     out = torch.empty(R, max(C_, 0), 5, dtype=torch.int32, device=dev)
-    post = torch.empty(R, max(C_, 0), n, dtype=torch.float32 if quant is None else torch.int16, device=dev) if want_post else None
+    post = torch.empty(R, max(C_, 0), n, dtype=torch.float32 if quant is None else torch.int16, device=dev) if want_post or outer is not None else None
     with torch.cuda.device(dev):
         head = (code.mb, code.nb, code.Z, code.shifts.ctypes.data_as(C.c_void_p), nat.ptr(llr), nat.ptr(bits, torch.int8))
         tail = (int(max_iter), nat.ptr(out, torch.int32), nat.ptr(post, torch.float32 if quant is None else torch.int16), nat.current_stream(dev))
@@ -767,10 +775,100 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, 
         ret["post"] = post
     if quant is not None:
         ret["quant"] = quant
+    if outer is not None:
+        ret["outer"] = bch_outer(post, bits, outer["code"], n, t0=t0, depth=depth, payload=outer["payload"], spread=outer["spread"],
+                                 codewords=outer["codewords"])
     return ret
 
 
-FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant")
+class BchCode:
+    """A narrow-sense primitive binary BCH code over GF(2^m) with designed correction t, shortened to n bits (default 2^m - 1), for bch_outer:
+    .m, .t, .n, .parity (the size of the union of the cyclotomic cosets of 1 .. 2t modulo 2^m - 1), .k = n - parity, .rate = k / n.  ValueError
+    outside vaeq_bch_outer's envelope: m in 4 .. 13, t in 1 .. 16, parity < n <= 2^m - 1."""
+
+    def __init__(self, m, t, n=None):
+        import numbers
+        if any(not isinstance(x, numbers.Integral) or isinstance(x, bool) for x in (m, t) + (() if n is None else (n,))):
+            raise ValueError(f"BchCode takes integers, got m={m!r}, t={t!r}, n={n!r}")
+        self.m, self.t = int(m), int(t)
+        if not 4 <= self.m <= 13 or not 1 <= self.t <= 16:
+            raise ValueError(f"BchCode: m in 4 .. 13 and t in 1 .. 16, got m={m}, t={t}")
+        q = (1 << self.m) - 1
+        seen = set()
+        for j in range(1, 2 * self.t + 1):
+            x = j % q
+            while x not in seen:
+                seen.add(x)
+                x = 2 * x % q
+        self.parity = len(seen)
+        self.n = q if n is None else int(n)
+        if not self.parity < self.n <= q:
+            raise ValueError(f"BchCode({m}, {t}): {self.parity} parity bits need {self.parity} < n <= {q}, got n={self.n}")
+        self.k = self.n - self.parity
+        self.rate = self.k / self.n
+
+
+OUTER_KEYS = ("code", "payload", "spread", "codewords")
+OUTER_POST_BYTES = 256 << 20                               # fec_figures with an outer code: the most bytes of `post` alive at a time
+
+
+def resolve_outer(outer, code=None):
+    """ldpc_decode's outer= dict(code, payload=None, spread=True, codewords=None) with its defaults filled in; code: the LdpcCode in front, whose
+    (nb - mb) Z is the default payload.  ValueError for an unknown key, a missing code or one that is no BchCode, a payload outside 1 .. n."""
+    if not isinstance(outer, dict) or set(outer) - set(OUTER_KEYS) or not isinstance(outer.get("code"), BchCode):
+        raise ValueError(f"outer takes a dict of {', '.join(OUTER_KEYS)} with a BchCode under code; got {sorted(outer) if isinstance(outer, dict) else outer!r}")
+    payload = outer.get("payload")
+    if payload is None and code is not None:
+        payload = (code.nb - code.mb) * code.Z
+    if payload is not None and (int(payload) < 1 or (code is not None and int(payload) > code.n)):
+        raise ValueError(f"outer['payload'] = {payload}: the first 1 .. n bits of a codeword")
+    return dict(code=outer["code"], payload=None if payload is None else int(payload), spread=bool(outer.get("spread", True)),
+                codewords=outer.get("codewords"))
+
+
+def bch_outer(post, bits, code, n, t0=0, depth=None, payload=None, spread=True, codewords=None, want_loc=False):
+    """The hard-decision outer decoder behind ldpc_decode (vaeq_bch_outer): bounded-distance decoding of the BchCode `code` over the payload
+    bits of post[R, C, n] (float32 or int16: ldpc_decode's post; a negative value is bit 1) against the TX bits `bits` ([R,2,2b,N] or [R,w,N],
+    as for ldpc_decode, with its t0 and depth).  No encoder: the figures depend on the error pattern alone.  payload: the first K bits of every
+    LDPC codeword are payload (default n: all of them; ldpc_decode's outer= defaults to (nb - mb) Z); the run's stream of C K bits holds
+    `codewords` outer codewords (default C K // code.n; ValueError if none fits), bit-interleaved over the run if spread (position p of outer
+    codeword a is stream bit p C_o + a) and back to back otherwise.
+    -> dict(status, pre_err, bit_err, nflip [R,C_o] int64: status 0 = zero syndromes, 1 = corrected nflip <= t positions, 2 = detected and left
+    alone; BER_outer[R], BER_in[R] f32 over the C_o n_o bits, FER_outer[R] the share of outer codewords with bit_err > 0; miscorrected[R]
+    (status 1 with bit_err > 0) and undetected[R] (status 0 with pre_err > 0) int64; loc[R,C_o,t] int16, the flipped positions ascending and
+    padded with -1, if want_loc)."""
+    if not isinstance(code, BchCode):
+        raise ValueError(f"bch_outer takes a BchCode, got {code!r}")
+    if post.dim() != 3 or post.shape[2] != int(n) or post.dtype not in (torch.float32, torch.int16) or bits.dim() not in (3, 4) or bits.shape[0] != post.shape[0]:
+        raise ValueError(f"expected post[R,C,{n}] float32 or int16 and bits[R,2,2b,N] or [R,w,N], got {tuple(post.shape)} {post.dtype}, {tuple(bits.shape)}")
+    dev, R, C_, N = post.device, post.shape[0], post.shape[1], bits.shape[-1]
+    post = post.contiguous()
+    w = bits.shape[1] * (bits.shape[2] if bits.dim() == 4 else 1)
+    bits = bits.reshape(R, w, N).contiguous()                  # (an empty batch leaves a -1 ambiguous)
+    K = int(n) if payload is None else int(payload)
+    if not 1 <= K <= int(n):
+        raise ValueError(f"payload = {K}: the first 1 .. {n} bits of a codeword")
+    Co = C_ * K // code.n if codewords is None else int(codewords)
+    if codewords is None and Co < 1:
+        raise ValueError(f"no outer codeword of {code.n} bits fits into the {C_} x {K} payload bits of a run")
+    out = torch.empty(R, max(Co, 0), 4, dtype=torch.int32, device=dev)
+    loc = torch.empty(R, max(Co, 0), code.t, dtype=torch.int16, device=dev) if want_loc else None
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_bch_outer(R, C_, N, w, int(t0), 0 if depth is None else int(depth), int(n), K, code.m, code.t, code.n, Co,
+                                           int(bool(spread)), nat.ptr(post, post.dtype), int(post.dtype == torch.int16), nat.ptr(bits, torch.int8),
+                                           nat.ptr(out, torch.int32), nat.ptr(loc, torch.int16), nat.current_stream(dev)), "vaeq_bch_outer")
+    o = out.long()
+    tot = torch.full((R,), float(max(Co * code.n, 1)), dtype=torch.float64, device=dev)
+    ret = dict(status=o[..., 0], pre_err=o[..., 1], bit_err=o[..., 2], nflip=o[..., 3],
+               BER_outer=(o[..., 2].sum(1).double() / tot).float(), BER_in=(o[..., 1].sum(1).double() / tot).float(),
+               FER_outer=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(Co, 1)))).float(),
+               miscorrected=((o[..., 0] == 1) & (o[..., 2] > 0)).sum(1), undetected=((o[..., 0] == 0) & (o[..., 1] > 0)).sum(1))
+    if want_loc:
+        ret["loc"] = loc
+    return ret
+
+
+FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant", "outer")
 
 
 def check_fec(fec):
@@ -781,13 +879,33 @@ def check_fec(fec):
         resolve_quant(fec["quant"])
         if fec.get("alpha") is not None:
             raise ValueError("fec takes alpha for the float decoder or quant for the fixed-point one, not both")
+    if fec is not None and fec.get("outer") is not None:
+        resolve_outer(fec["outer"], fec["code"])
+
+
+def _cat_figures(parts):
+    """The dicts of the chunks of a batch as one: tensors joined along the runs, nested dicts likewise, anything else (the resolved quant) once."""
+    first = parts[0]
+    return {k: torch.cat([p[k] for p in parts]) if torch.is_tensor(v) else _cat_figures([p[k] for p in parts]) if k == "outer" else v
+            for k, v in first.items()}
 
 
 def fec_figures(llr, fec):
-    """The batch runners' fec= : ldpc_decode of an "llr" dict (llr, bits) under fec = dict(code, t0, max_iter, alpha, depth, quant; all but code
-    optional; quant = dict(bits, ...) decodes in fixed point, vaeq_ldpc_decode_q)."""
+    """The batch runners' fec= : ldpc_decode of an "llr" dict (llr, bits) under fec = dict(code, t0, max_iter, alpha, depth, quant, outer; all but
+    code optional; quant = dict(bits, ...) decodes in fixed point, vaeq_ldpc_decode_q; outer = dict(code=BchCode, ...) adds bch_outer's figures
+    under "outer").  With an outer code the runs are walked in chunks whose `post` stays within OUTER_POST_BYTES; codewords are independent, so
+    the figures are those of one call."""
     check_fec(fec)
-    return ldpc_decode(llr["llr"], llr["bits"], fec["code"], **{k: v for k, v in fec.items() if k != "code"})
+    kw = {k: v for k, v in fec.items() if k != "code"}
+    L, B = llr["llr"], llr["bits"]
+    if fec.get("outer") is None or L.shape[0] == 0:
+        return ldpc_decode(L, B, fec["code"], **kw)
+    R, N, n = L.shape[0], L.shape[-1], fec["code"].n
+    w = L.numel() // max(R * N, 1)
+    C_ = int(kw["codewords"]) if kw.get("codewords") is not None else _ldpc_fit(N, w, n, kw.get("t0", 0), kw.get("depth"))
+    per_run = max(C_, 1) * n * (4 if fec.get("quant") is None else 2)
+    step = max(1, int(OUTER_POST_BYTES) // per_run)
+    return _cat_figures([ldpc_decode(L[r:r + step], B[r:r + step], fec["code"], **kw) for r in range(0, R, step)])
 
 
 def cma_epilogue(y, data, amp_levels, nu_sc, var):

@@ -119,16 +119,30 @@ def info_rows(r, keys):
 
 
 FEC_KEYS = ("BER_post", "FER", "BER_pre_fec", "fec_iters")
+FEC_OUTER_KEYS = ("BER_outer", "FER_outer")                # the two rows behind them when fec_metrics carries an outer code
+
+
+def fec_keys(fec_metrics):
+    """The keys a sweep script's .mat gains under its fec_metrics: none, FEC_KEYS, or FEC_KEYS + FEC_OUTER_KEYS with an outer code."""
+    if fec_metrics is None:
+        return ()
+    return FEC_KEYS + (FEC_OUTER_KEYS if fec_metrics.get("outer") is not None else ())
 
 
 def fec_values(fec):
-    """engine.fec_figures' dict -> [R, 4] float32 on the CPU, in FEC_KEYS order: BER_post, FER, BER_pre and the mean over the codewords of iters."""
-    return torch.stack([fec["BER_post"], fec["FER"], fec["BER_pre"], fec["iters"].double().mean(1).float()], dim=1).cpu()
+    """engine.fec_figures' dict -> [R, 4] float32 on the CPU, in FEC_KEYS order: BER_post, FER, BER_pre and the mean over the codewords of iters;
+    [R, 6] with an outer code: then BER_outer and FER_outer, in FEC_OUTER_KEYS order."""
+    cols = [fec["BER_post"], fec["FER"], fec["BER_pre"], fec["iters"].double().mean(1).float()]
+    if "outer" in fec:
+        cols += [fec["outer"]["BER_outer"], fec["outer"]["FER_outer"]]
+    return torch.stack(cols, dim=1).cpu()
 
 
 def fec_rows(r, keys):
     """An AWGN runner's (SER, info or None, extras) under fec= -> rows [R, 1 + len(keys) + 4, n_eval] through info_rows: SER, info[k] for k in keys,
-    then the four FEC_KEYS figures of the last evaluated validation, each repeated along n_eval (a row has one length)."""
+    then the four FEC_KEYS figures of the last evaluated validation (and the two FEC_OUTER_KEYS figures behind them with an outer code), each
+    repeated along n_eval (a row has one length)."""
     v = fec_values(r[2]["fec"])
-    cols = dict(r[1] or {}, **{k: v[:, j:j + 1].expand(-1, r[0].shape[1]) for j, k in enumerate(FEC_KEYS)})
-    return info_rows((r[0], cols), tuple(keys) + FEC_KEYS)
+    names = (FEC_KEYS + FEC_OUTER_KEYS)[:v.shape[1]]
+    cols = dict(r[1] or {}, **{k: v[:, j:j + 1].expand(-1, r[0].shape[1]) for j, k in enumerate(names)})
+    return info_rows((r[0], cols), tuple(keys) + names)
