@@ -5,6 +5,7 @@ For a lane -> (group, part) mapping and a part stride it counts, per loop trip, 
 64 lanes is served as two half-waves of 32; within a half-wave the lanes that name the SAME dword are one access (broadcast), different
 dwords on the same of the 64 banks serialise.  passes(read) = sum over the two half-waves of the maximum bank multiplicity.
 Usage: python tools/lds_bank_model.py [B] [M]
+       python tools/lds_bank_model.py dp_d3 | dp_tappair      (the DP wave kernel's D phase / tap-pair tap gradients at the baked B = 100)
 """
 import sys
 from collections import defaultdict
@@ -181,10 +182,71 @@ def dp_d3_model(B=100, M=25):
     return worst
 
 
+def dp_tappair_model(B=100, M=25):
+    """Tap-gradient phases (P4a dL/dh, P5 dL/dw) of the DP wave kernel at the baked B = 100 (csrc/vaeq_dp_wave_kernel.h): passes per half-wave of every
+    per-lane read of a pair of terms, for the tap-pair mapping (TapPairMap: lane = (c, half, par, slot), read tap + carried tap) and for the plain one
+    (lane = (tap, half), every operand read).  The trip index adds the same offset to every lane: one trip is the pattern of all.
+    Exit status 1 if a read of the tap-pair mapping needs more passes than the worst read of the plain mapping.    python tools/lds_bank_model.py dp_tappair"""
+    mh = M // 2
+    Mh = 2 * mh
+    Lph, Uph = wave_lph(2 * B + M - 1), B // 2 + 1
+    X, E = 0, 2 * 4 * Lph
+    U = 2 * E                                                  # gy aliases U: [o][B]
+    nh, nw = (B - mh) // 4, B // 4                             # pairs per half
+    se = ((M + 1) // 2 + 1) // 2
+    ns = se + (M // 2 + 1) // 2
+    ph = lambda c: (c & 3) * Lph + (c >> 2)
+    worst = {}
+    # tap pairs
+    dh, dw = [[] for _ in range(6)], [[] for _ in range(6)]
+    for lane in range(64):
+        ix = (lane & 31) if (lane & 31) < 2 * ns else 0
+        c, hf = int(ix >= ns), lane >> 5
+        s = ix - c * ns
+        par = int(s >= se)
+        sl = s - par * se
+        pt = hf ^ c                                            # dL/dh: chi = 1 takes the halves of the tau range the other way round (TapPairMap::part_h): with pt = hf the two chi of a half-wave collide on every e read (2 passes)
+        e = E + c * 4 * Lph + pt * nh
+        uA = U + (mh >> 1) - sl + pt * nh
+        for k, a in enumerate((e + ph(par + Mh), e + ph(par + Mh + 2), uA, uA + 2 * Uph, uA + Uph, uA + 3 * Uph)):
+            dh[k].append(a)
+        kr = 2 * (2 * sl + 1) + par
+        g = U + c * B + 2 * hf * nw
+        x = X + hf * nw
+        for k, a in enumerate((g, g + 1, x + ph(kr), x + 4 * Lph + ph(kr), x + ph(kr + 2), x + 4 * Lph + ph(kr + 2))):
+            dw[k].append(a)
+    worst["pairs dL/dh"] = [max(half_passes(a)) for a in dh]
+    worst["pairs dL/dw"] = [max(half_passes(a)) for a in dw]
+    # plain: lane = (tap tk = lane & 31 (tk >= M shadows tap 0), half)
+    dh, dw = [[] for _ in range(8)], [[] for _ in range(8)]
+    for lane in range(64):
+        tk, hf = (lane & 31) if (lane & 31) < M else 0, lane >> 5
+        par, aa = tk & 1, tk >> 1
+        npA, npB = mh - aa, mh - aa + 1
+        eA, eB = E + ph(par + Mh) + hf * nh, E + ph(par + Mh + 2) + hf * nh
+        uA, uB = U + (npA & 1) * Uph + (npA >> 1) + hf * nh, U + (npB & 1) * Uph + (npB >> 1) + hf * nh
+        for k, a in enumerate((eA, eA + 4 * Lph, uA, uA + 2 * Uph, eB, eB + 4 * Lph, uB, uB + 2 * Uph)):
+            dh[k].append(a)
+        g0 = U + 2 * hf * nw
+        xA, xB = X + ph(tk) + hf * nw, X + ph(tk + 2) + hf * nw
+        for k, a in enumerate((g0, g0 + 1, g0 + B, g0 + B + 1, xA, xA + 4 * Lph, xB, xB + 4 * Lph)):
+            dw[k].append(a)
+    worst["plain dL/dh"] = [max(half_passes(a)) for a in dh]
+    worst["plain dL/dw"] = [max(half_passes(a)) for a in dw]
+    print(f"DP wave kernel, tap gradients, B = {B}, M = {M}: Lph = {Lph}, Uph = {Uph}; LDS passes per half-wave of each per-lane read of one pair of terms:")
+    for k, v in worst.items():
+        print(f"  {k:12s} {v}   reads {len(v)}, passes {sum(v)}")
+    ok = all(max(worst["pairs " + g]) <= max(worst["plain " + g]) for g in ("dL/dh", "dL/dw"))
+    print("  the tap pairs need", "no more" if ok else "MORE", "passes per read than the plain mapping's worst read")
+    return ok
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "dp_d3":
         dp_d3_model()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "dp_tappair":
+        sys.exit(0 if dp_tappair_model() else 1)
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 350
     M = int(sys.argv[2]) if len(sys.argv) > 2 else 25
     mh = M // 2

@@ -244,6 +244,153 @@ struct D3Map {
 };
 static_assert(D3Map::exact(100, 25), "B = 100: three tau per lane must cover tau = 0..87 of both chi exactly once");
 
+// Tap-gradient phases (P4a dL/dh, P5 dL/dw) of the baked B = 100, M = 25 kernel on one wave.  In both sums a lane's two operand streams advance
+// together, so two neighbouring taps of one parity share their per-lane operands:
+//   dL/dh[chi, nu, j = 2a + par] = sum_tau e[chi, 2 tau + par] conj(U[nu, tau + mh - a]):  tap a + 1 reads at tau + 1 the U cell tap a read at tau,
+//   dL/dw[o, p, k = 2a + par]    = sum_n   gy[o, n] conj(x[p, 2n + k]):                    tap a reads at n + 1 the x cell tap a + 1 read at n.
+// A lane is (c, half, par, slot): c = chi resp. o, half = which half of the sum range, slot = the tap pair (a, a + 1) = (2 slot, 2 slot + 1) of parity
+// par -- the 13 even taps make 7 slots (the last one holds a = 12 alone), the 12 odd taps 6: 13 slots x 2 c = 26 lanes in each 32-lane half, the
+// lanes beyond shadow lane 0.  The lane keeps the accumulators [tap of the pair][nu resp. p]; per term it reads ONE cell of its own c (e resp. gy),
+// the two cells (nu resp. p = 0, 1) of the pair's READ tap (dL/dh: a, dL/dw: a + 1), and has the other tap's two cells in registers: the read tap's
+// cells of the term before (tap_pair_sum).  12 per-lane LDS reads per 32 packed FMAs instead of 16; every output's chain keeps its terms and their order.
+// The two halves meet on v_permlane32_swap over the pair: the lower half keeps tap a = 2 slot, the upper half a + 1, both nu resp. p -- that lane owns
+// those four reals, their Adam moments and the tap's write to LDS (one map for h and W: lane -> (c, j)).
+struct TapPairMap {
+    static constexpr int se(int M) { return ((M + 1) / 2 + 1) / 2; }          // slots of the even taps (a = 0 .. (M - 1) / 2)
+    static constexpr int ns(int M) { return se(M) + (M / 2 + 1) / 2; }        // ... plus those of the odd taps (a = 0 .. M / 2 - 1)
+    static constexpr bool works(int lane, int M) { return (lane & 31) < 2 * ns(M); }
+    static constexpr int idx(int lane, int M) { return works(lane, M) ? (lane & 31) : 0; }
+    static constexpr int c(int lane, int M) { return idx(lane, M) >= ns(M) ? 1 : 0; }
+    static constexpr int s(int lane, int M) { return idx(lane, M) - c(lane, M) * ns(M); }
+    static constexpr int par(int lane, int M) { return s(lane, M) >= se(M) ? 1 : 0; }
+    static constexpr int alo(int lane, int M) { return 2 * (s(lane, M) - par(lane, M) * se(M)); }      // the pair's lower tap
+    static constexpr int tap(int lane, int M, int x) { return 2 * (alo(lane, M) + x) + par(lane, M); }  // j resp. k of the pair's tap x = 0, 1
+    static constexpr int kept(int lane, int M) { return tap(lane, M, lane >> 5); }                       // the tap whose sum the lane ends up with
+    static constexpr bool owns(int lane, int M) { return works(lane, M) && kept(lane, M) < M; }
+    // which half of the sum range the lane takes.  dL/dh: chi = 1 takes them the other way round (a sum's two halves still sit 32 lanes apart and
+    // their addition commutes) -- the e rows of the two chi are a multiple of 64 banks apart, and with equal offsets the two chi of a half-wave
+    // would collide on every e read (tools/lds_bank_model.py dp_tappair: 2 passes, 1 this way); gy, x and U have no such collision
+    static constexpr int part_h(int lane, int M) { return (lane >> 5) ^ c(lane, M); }
+    static constexpr int part_w(int lane) { return lane >> 5; }
+    static constexpr int dh_pairs(int B, int M) { return (B - M / 2) / 4; }    // (tau, tau + 1) pairs per half of dL/dh; (n, n + 1) pairs per half of dL/dw:
+    static constexpr int dw_pairs(int B) { return B / 4; }                     // what uniform_parts() finds for two parts
+    // every (c, j < M, half) is summed by exactly one lane and every (c, j < M) kept by exactly one; no consumed read leaves its array: U[nu][0 .. 2 Uph - 1],
+    // e and x cells below 2 B + M - 1 (a tap past M - 1, the upper tap of the slot that holds a = 12 alone: inside the phase rows), gy[o][0 .. B - 1]
+    static constexpr bool exact(int B, int M)
+    {
+        const int mh = M / 2, Mh = 2 * mh, nm = 2 * B - Mh, T = nm / 2, Uph = B / 2 + 1, len = 2 * B + M - 1, Lph = wave_lph(len);
+        if (M > 31 || (mh & 1) || (nm & 1) || (T & 3) || (B & 3) || 2 * ns(M) > 32 || !uniform_parts(B, M, 2)) return false;
+        int sumh[2][32][2] = {}, sumw[2][32][2] = {}, own[2][32] = {};
+        for (int lane = 0; lane < 64; lane++) {
+            const int p = par(lane, M), a = alo(lane, M);
+            if (works(lane, M))
+                for (int x = 0; x < 2; x++)
+                    if (tap(lane, M, x) < M) {
+                        sumh[c(lane, M)][tap(lane, M, x)][part_h(lane, M)]++;
+                        sumw[c(lane, M)][tap(lane, M, x)][part_w(lane)]++;
+                    }
+            if (c(lane, M) != c(lane ^ 32, M) || tap(lane, M, 0) != tap(lane ^ 32, M, 0)) return false;   // the two halves of a sum: 32 lanes apart
+            if (owns(lane, M)) own[c(lane, M)][kept(lane, M)]++;
+            // dL/dh: read tap a, pairs m = ma .. ma + n - 1: e cells Mh + par + 4 m (+ 2), U cells 2 m + mh - a (+ 1); the term before the first: one cell lower
+            const int nh = dh_pairs(B, M), mah = part_h(lane, M) * nh;
+            const bool up = tap(lane, M, 1) < M;                                // the pair's upper tap exists (else its first operand is read from the read tap's cell)
+            if (2 * mah + mh - a - (up ? 1 : 0) < 0 || 2 * (mah + nh - 1) + mh - a + 1 >= 2 * Uph) return false;
+            if (Mh + p + 4 * (mah + nh - 1) + 2 >= len) return false;
+            // dL/dw: read tap k = tap(., 1), pairs m: x cells k + 4 m (+ 2), gy cells 2 m, 2 m + 1; the term before the first: x cell k + 4 ma - 2
+            const int nw = dw_pairs(B), maw = part_w(lane) * nw, k = tap(lane, M, 1);
+            if (2 * (maw + nw - 1) + 1 >= B) return false;
+            if (k + 4 * (maw + nw - 1) + 2 >= (up ? len : 4 * Lph)) return false;
+        }
+        for (int cc = 0; cc < 2; cc++)
+            for (int j = 0; j < 32; j++) {
+                if (own[cc][j] != (j < M ? 1 : 0)) return false;
+                for (int hf = 0; hf < 2; hf++)
+                    if (sumh[cc][j][hf] != (j < M ? 1 : 0) || sumw[cc][j][hf] != (j < M ? 1 : 0)) return false;
+            }
+        return true;
+    }
+};
+static_assert(TapPairMap::exact(100, 25), "B = 100: the tap pairs must sum every (c, tap, half) once, own every (c, tap) once and read inside their arrays");
+
+// One half of the tap-gradient sums of a TapPairMap lane over the N pairs m = 0 .. N - 1 of its range: for y = 0, 1 (nu resp. p)
+//   acc[0][y] = sum_m  tA_y(m) (x) sA(m)       + tB_y(m) (x) sB(m)        -- the pair's read tap,
+//   acc[1][y] = sum_m  tB_y(m - 1) (x) sA(m)   + tA_y(m) (x) sB(m)        -- its other tap, whose operands are the read tap's one term earlier,
+// with sA(m) = sA[SS m], sB(m) = sB[SS m], tA_y(m) = tA[y TN + m], tB_y(m) = tB[y TN + m] and tB_y(-1) = tC[y TN].  Every sum keeps the two
+// sub-chains of the plain loops (the first addend of each m into one, the second into the other, the first term starting the chain, the two added
+// once at the end).  A stage is two pairs: 12 LDS reads feeding 32 packed FMAs, two-deep like pipe2 (loads run one stage past the end, never consumed,
+// inside the LDS allocation).  The last two reads of a stage (tB of its second pair) are what the next stage's first FMAs (head) take from registers:
+// the stage after that loads them behind its predecessor's head, into the registers just freed -- no copies on the back edge.
+template <int N, int SS>
+__device__ __forceinline__ void tap_pair_sum(cacc (&ca)[2][2], const float2 *sA, const float2 *sB, const float2 *tA, const float2 *tB, int TN,
+                                             const float2 *tC)
+{
+    constexpr int NST = N / 2;
+    static_assert(NST >= 2, "at least two stages");
+    cacc cb[2][2];
+    auto loadM = [&](int i, v2f (&r)[12]) {
+        const int m = 2 * i;
+        r[0] = lds2(sA + SS * m); r[1] = lds2(sB + SS * m); r[2] = lds2(tA + m); r[3] = lds2(tA + TN + m); r[4] = lds2(tB + m); r[5] = lds2(tB + TN + m);
+        r[6] = lds2(sA + SS * (m + 1)); r[7] = lds2(sB + SS * (m + 1)); r[8] = lds2(tA + m + 1); r[9] = lds2(tA + TN + m + 1);
+    };
+    auto loadL = [&](int i, v2f (&r)[12]) { r[10] = lds2(tB + 2 * i + 1); r[11] = lds2(tB + TN + 2 * i + 1); };
+    auto head = [&](const v2f (&r)[12], const v2f (&p)[12], auto first) {      // p: the stage before
+        constexpr bool F = decltype(first)::value;
+        // pin: the cells used as taps stay 8-byte registers up to their use (the optimiser otherwise splits the sets that live across the loop's back edge
+        // into halves at their loads: copies behind s_waitcnt lgkmcnt(9..0) at the end of every trip, see D3Map's loop)
+        v2f q0 = p[10], q1 = p[11];
+        asm volatile("" : "+v"(q0), "+v"(q1));
+        cmacf<F>(ca[1][0], q0, r[0]); cmacf<F>(ca[1][1], q1, r[0]);
+        asm volatile("" : "+v"(ca[1][0].a), "+v"(ca[1][0].b), "+v"(ca[1][1].a), "+v"(ca[1][1].b));   // (volatile: stays in front of the loads into p[10], p[11])
+    };
+    auto rest = [&](const v2f (&r)[12]) {
+        v2f a0 = r[2], a1 = r[3], b0 = r[4], b1 = r[5];
+        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1));            // (pin: see head)
+        cmac(ca[0][0], a0, r[0]); cmac(ca[0][1], a1, r[0]); cmac(cb[0][0], b0, r[1]); cmac(cb[0][1], b1, r[1]);
+        cmac(cb[1][0], a0, r[1]); cmac(cb[1][1], a1, r[1]);
+        v2f c0 = r[8], c1 = r[9];
+        asm volatile("" : "+v"(c0), "+v"(c1) : "v"(r[10]), "v"(r[11]));        // (r[10], r[11] live on into the next stage's head: inputs only, or they are copied)
+        cmac(ca[0][0], c0, r[6]); cmac(ca[0][1], c1, r[6]); cmac(cb[0][0], r[10], r[7]); cmac(cb[0][1], r[11], r[7]);
+        cmac(ca[1][0], b0, r[6]); cmac(ca[1][1], b1, r[6]); cmac(cb[1][0], c0, r[7]); cmac(cb[1][1], c1, r[7]);
+    };
+    // the first stage starts the chains.  Which of a chain's first two products is rounded on its own is part of the pinned bits: in the plain loops the
+    // backend contracts  t0 v0 + t1 v1  of the first sub-chain as fma(t1, v1, t0 v0) and of the second as fma(t0, v0, t1 v1).  Spelled out and pinned here
+    auto rest0 = [&](const v2f (&r)[12]) {
+        cmul(ca[0][0], r[2], r[0]); cmul(ca[0][1], r[3], r[0]);
+        cmul(cb[0][0], r[10], r[7]); cmul(cb[0][1], r[11], r[7]); cmul(cb[1][0], r[8], r[7]); cmul(cb[1][1], r[9], r[7]);
+        asm volatile("" : "+v"(ca[0][0].a), "+v"(ca[0][0].b), "+v"(ca[0][1].a), "+v"(ca[0][1].b));
+        asm volatile("" : "+v"(cb[0][0].a), "+v"(cb[0][0].b), "+v"(cb[0][1].a), "+v"(cb[0][1].b));
+        asm volatile("" : "+v"(cb[1][0].a), "+v"(cb[1][0].b), "+v"(cb[1][1].a), "+v"(cb[1][1].b));
+        cmac(cb[0][0], r[4], r[1]); cmac(cb[0][1], r[5], r[1]); cmac(cb[1][0], r[2], r[1]); cmac(cb[1][1], r[3], r[1]);
+        cmac(ca[0][0], r[8], r[6]); cmac(ca[0][1], r[9], r[6]); cmac(ca[1][0], r[4], r[6]); cmac(ca[1][1], r[5], r[6]);
+    };
+    v2f A[12], B[12];
+    B[10] = lds2(tC); B[11] = lds2(tC + TN);
+    loadM(0, A); loadL(0, A); loadM(1, B);
+    head(A, B, std::true_type{}); loadL(1, B); rest0(A);
+    int i = 1;
+#pragma unroll 1
+    for (; i + 1 < NST; i += 2) {                          // B holds stage i, A[10], A[11] what is left of stage i - 1
+        loadM(i + 1, A); head(B, A, std::false_type{}); loadL(i + 1, A); rest(B);
+        loadM(i + 2, B); head(A, B, std::false_type{}); loadL(i + 2, B); rest(A);
+    }
+    constexpr bool LB = NST % 2 == 0;                      // the last stage is in B (and still to do), else in A (done)
+    v2f t[6];
+    if constexpr (N & 1) {                                 // an odd last pair: its reads go out before the last stage's FMAs
+        constexpr int m = N - 1;
+        t[0] = lds2(sA + SS * m); t[1] = lds2(sB + SS * m); t[2] = lds2(tA + m); t[3] = lds2(tA + TN + m); t[4] = lds2(tB + m); t[5] = lds2(tB + TN + m);
+    }
+    if constexpr (LB) { head(B, A, std::false_type{}); rest(B); }
+    if constexpr (N & 1) {
+        const v2f (&p)[12] = LB ? B : A;
+        cmac(ca[1][0], p[10], t[0]); cmac(ca[1][1], p[11], t[0]); cmac(ca[0][0], t[2], t[0]); cmac(ca[0][1], t[3], t[0]);
+        cmac(cb[0][0], t[4], t[1]); cmac(cb[0][1], t[5], t[1]); cmac(cb[1][0], t[2], t[1]); cmac(cb[1][1], t[3], t[1]);
+    }
+#pragma unroll
+    for (int x = 0; x < 2; x++)
+#pragma unroll
+        for (int y = 0; y < 2; y++) { ca[x][y].a += cb[x][y].a; ca[x][y].b += cb[x][y].b; }
+}
+
 // OUT: 0 = every output nullable at run time; 1 = no compact outputs (eq_out / dec_out ignored); 2 = compact outputs, q not written.
 // The specialisations only drop dead code: fewer live scalars, fewer SGPR spills in the step loop.
 // NW = wavefronts per run: 1 (B <= 128, no barriers at all) or 2 / 4 / 8 (B <= 256 / 512 / 1024): thread gl = 64 wv + lane owns the symbol pair
@@ -267,7 +414,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     constexpr bool PIPE = VAEQ_PIPE && FIXL;               // run-time layouts keep more addresses live: there one operand set,
     constexpr bool WIDE = FIXL;                            // ... 8 accumulator chains and one chi at a time in dL/dU (fits the register file)
     // B100: the baked B = 100 kernel on one wave, the shape that is measured step by step and whose bits are pinned (tests/test_dp_wave_bits_gpu.py).
-    // It alone takes four forms; every other instantiation keeps the plain one, instruction for instruction:
+    // It alone takes five forms; every other instantiation keeps the plain one, instruction for instruction:
     //  * the halves of the two tap gradients meet on v_permlane32_swap (half_sum: one swap + one add per kept value) instead of 16 ds_bpermute_b32
     //    through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms (profiles/r04/kernel_variants_ab.txt)
     //  * the next window's prefetch is issued without a branch around it (the launch's very last step fetches with every lane out of range: zeros, no
@@ -279,6 +426,10 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     //  * (M = 25) the D convolution of P3 runs three tau of one chi per lane on 60 lanes (D3Map) instead of two tau of both chi on 44: 300 instead of 416
     //    packed FMAs per lane, every output's chain of FMAs in its old order; the residual's energy sum reads e back from LDS on its old lanes
     //    (profiles/r06/kernel_variants_ab.txt)
+    //  * (M = 25) the two tap gradients run on tap-pair lanes (TapPairMap, TP below): a lane sums two neighbouring taps of one parity for one chi resp. o
+    //    and takes the second tap's operands from the registers of the first: 12 instead of 16 per-lane LDS reads per 32 packed FMAs, every output's
+    //    chain in its old order; the lane that ends up with a tap's sum owns the tap and its Adam moments
+    //    (profiles/r07/tapgrad_lds_bound.txt, profiles/r07/kernel_variants_ab.txt)
     constexpr bool B100 = BT == 100 && NW == 1;
     constexpr int QAUX = B100 ? 2 : 0;                         // cache policy of the q stores
     const int B = BT ? BT : a.B;
@@ -319,8 +470,18 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     const bool worker = tk < M, owner = worker && wv == 0;     // worker: sums a part of a tap's gradient; owner: holds the tap
     const int part = wv * 2 + half;
     const size_t gbase = (size_t)run * 8 * M;
+    // which taps a lane owns (state in / out, Adam moments, the tap's write to LDS): W[o = oc][.][k = tj] and h[chi = oc][.][j = tj].  Plain form: the
+    // lane that summed tap tk keeps half's part (oc = half, tj = tk); TP: the tap-pair lanes of TapPairMap
+    constexpr bool TP = BT == 100 && NW == 1 && M == 25;
+    int oc = half, tj = tk;
+    bool ownr = owner;
+    if constexpr (TP) {
+        oc = TapPairMap::c(lane, M);
+        tj = TapPairMap::kept(lane, M);
+        ownr = TapPairMap::owns(lane, M);
+    }
     // Adam moments of the taps this lane owns live in LDS, one 64-lane row per quantity (touched twice per step; 16 VGPRs freed):
-    // rows 0-7: m, v of W[o=half][p][k=tk] (re, im); rows 8-15: m, v of h[chi=half][nu][.][j=tk]
+    // rows 0-7: m, v of W[o=oc][p][k=tj] (re, im); rows 8-15: m, v of h[chi=oc][nu][.][j=tj]
     float *MOM = reinterpret_cast<float *>(sm + lay.MOM) + lane;
 #define mWr(p) MOM[(0 + (p)) * 64]
 #define mWi(p) MOM[(2 + (p)) * 64]
@@ -330,17 +491,17 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 #define mHi(p) MOM[(10 + (p)) * 64]
 #define vHr(p) MOM[(12 + (p)) * 64]
 #define vHi(p) MOM[(14 + (p)) * 64]
-    if (owner) {
+    if (ownr) {
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            const size_t ir = gbase + (half * 4 + p) * M + tk, ii = gbase + (half * 4 + 2 + p) * M + tk;
-            float *wq = reinterpret_cast<float *>(&Wt[p * M + tk]);
-            wq[half * 2 + 0] = a.W[ir];
-            wq[half * 2 + 1] = a.W[ii];
+            const size_t ir = gbase + (oc * 4 + p) * M + tj, ii = gbase + (oc * 4 + 2 + p) * M + tj;
+            float *wq = reinterpret_cast<float *>(&Wt[p * M + tj]);
+            wq[oc * 2 + 0] = a.W[ir];
+            wq[oc * 2 + 1] = a.W[ii];
             mWr(p) = a.adam_mW[ir]; mWi(p) = a.adam_mW[ii];
             vWr(p) = a.adam_vW[ir]; vWi(p) = a.adam_vW[ii];
-            const size_t hr = gbase + ((half * 2 + p) * 2 + 0) * M + tk, hi = hr + M;
-            Ht[(half * 2 + p) * MP + tk] = make_float2(a.h[hr], a.h[hi]);
+            const size_t hr = gbase + ((oc * 2 + p) * 2 + 0) * M + tj, hi = hr + M;
+            Ht[(oc * 2 + p) * MP + tj] = make_float2(a.h[hr], a.h[hi]);
             mHr(p) = a.adam_mh[hr]; mHi(p) = a.adam_mh[hi];
             vHr(p) = a.adam_vh[hr]; vHi(p) = a.adam_vh[hi];
         }
@@ -810,15 +971,29 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 // update after the loop starts with fewer exposed LDS round trips (wave 0 only)
                 float2 ph_h[2] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f)};
                 float ph_vs[2] = {0.f, 0.f};                   // (the moments stay in LDS until the update: this phase cannot spare eight more registers)
-                if (NW == 1 && owner) {
+                if (NW == 1 && ownr) {
 #pragma unroll
                     for (int v = 0; v < 2; v++) {
-                        ph_h[v] = Ht[(half * 2 + v) * MP + tk];
-                        ph_vs[v] = VS[v * M + tk];
+                        ph_h[v] = Ht[(oc * 2 + v) * MP + tj];
+                        ph_vs[v] = VS[v * M + tj];
                     }
                 }
                 cacc ca[2][2];
-                {
+                if constexpr (TP) {
+                    // tap pairs (TapPairMap): ca[tap of the pair][nu] of the lane's chi over its half of the tau range; read tap a = 2 slot (mh even: its U
+                    // cells tau + mh - a of even tau are the even phase), the other tap a + 1 from registers.  The pointers are derived once per STEP (see P3)
+                    static_assert(TapPairMap::exact(100, M) && UNI, "TapPairMap");
+                    int lt = lane;
+                    asm volatile("" : "+v"(lt));
+                    constexpr int NH = TapPairMap::dh_pairs(100, M);
+                    const int par = TapPairMap::par(lt, M), sl = TapPairMap::alo(lt, M) >> 1, ma = TapPairMap::part_h(lt, M) * NH;
+                    const int ceA = par + Mh, ceB = par + Mh + 2;
+                    const float2 *ec = Es + TapPairMap::c(lt, M) * 4 * Lph + ma;
+                    const float2 *uA = Us + (mh >> 1) - sl + ma, *uB = uA + Uph;
+                    const float2 *uC = TapPairMap::tap(lt, M, 1) < M ? uB - 1 : uA;   // U of tap a + 1 at the first tau (the slot of a = 12 alone has no such tap)
+                    VAEQ_XSTAMP(0);
+                    tap_pair_sum<NH, 1>(ca, ec + (ceA & 3) * Lph + (ceA >> 2), ec + (ceB & 3) * Lph + (ceB >> 2), uA, uB, 2 * Uph, uC);
+                } else {
                     // sum over tau of e[chi, 2 tau + par] conj(U[nu, tau + mh - a]); tau runs in pairs (2m, 2m+1) so that the
                     // polyphase component of every operand is a per-lane constant and only the slot advances (by one per m).
                     // Past the last valid tau the residual cells are zero (pad), so the pair loop may overrun by one.
@@ -898,8 +1073,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                     }
                 }
                 VAEQ_XSTAMP(2);
-                if (NW == 1 && owner) {
-                    const float g = half ? gC1 : gC0;
+                if (NW == 1 && ownr) {
+                    const float g = oc ? gC1 : gC0;
 #pragma unroll
                     for (int v = 0; v < 2; v++) {
                         const float2 ac = half ? acc[1][v] : acc[0][v];
@@ -990,9 +1165,9 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                     GY[v * BS + n0 + 1] = v1 ? gy[1][v] : make_float2(0.f, 0.f);
                 }
             }
-            if (owner && !a.no_update) {
-                Ht[(half * 2 + 0) * MP + tk] = hnew[0];
-                Ht[(half * 2 + 1) * MP + tk] = hnew[1];
+            if (ownr && !a.no_update) {
+                Ht[(oc * 2 + 0) * MP + tj] = hnew[0];
+                Ht[(oc * 2 + 1) * MP + tj] = hnew[1];
             }
             sync_lds<NW>();
 
@@ -1001,17 +1176,31 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             float gwr[2] = {0, 0}, gwi[2] = {0, 0};
             {
                 float pw_w[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, pw_m[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, pw_v[2][2] = {{0.f, 0.f}, {0.f, 0.f}};   // as for Adam(h)
-                if (owner) {
+                if (ownr) {
 #pragma unroll
                     for (int p = 0; p < 2; p++) {
-                        const float *wq = reinterpret_cast<const float *>(&Wt[p * M + tk]) + half * 2;
+                        const float *wq = reinterpret_cast<const float *>(&Wt[p * M + tj]) + oc * 2;
                         pw_w[p][0] = wq[0]; pw_w[p][1] = wq[1];
                         pw_m[p][0] = mWr(p); pw_m[p][1] = mWi(p);
                         pw_v[p][0] = vWr(p); pw_v[p][1] = vWi(p);
                     }
                 }
                 cacc ca[2][2];
-                {
+                if constexpr (TP) {
+                    // tap pairs (TapPairMap): read tap k + 2 = 2 (a + 1) + par, the pair's lower tap k from registers; ca[o-half order][p]: [0] = the lower
+                    // tap, which the lower half keeps
+                    int lt = lane;
+                    asm volatile("" : "+v"(lt));
+                    constexpr int NQ = TapPairMap::dw_pairs(100);
+                    const int cA = TapPairMap::tap(lt, M, 1), cB = cA + 2, ma = TapPairMap::part_w(lt) * NQ;
+                    const float2 *gA = GY + TapPairMap::c(lt, M) * BS + 2 * ma;
+                    const float2 *xA = Xs + (cA & 3) * Lph + (cA >> 2) + ma, *xB = Xs + (cB & 3) * Lph + (cB >> 2) + ma;
+                    cacc cr[2][2];                             // [0] = the read (upper) tap
+                    VAEQ_XSTAMP(4);
+                    tap_pair_sum<NQ, 2>(cr, gA, gA + 1, xA, xB, 4 * Lph, xB - 1);
+#pragma unroll
+                    for (int p = 0; p < 2; p++) { ca[0][p] = cr[1][p]; ca[1][p] = cr[0][p]; }
+                } else {
                     // sum over n of gy[o, n] conj(x[p, 2n + k]); n runs in pairs (2m, 2m+1): x phase fixed per lane, gy pair = 16 bytes
                     const int tkc = worker ? tk : 0;           // lanes beyond the M taps shadow tap 0
                     const int Be = ODDB ? B + (B & 1) : B;     // odd B: the last pair's second symbol has dL/dy = 0
@@ -1087,7 +1276,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                     sync_lds<NW>();
                 }
                 VAEQ_XSTAMP(6);
-                if (owner) {
+                if (ownr) {
 #pragma unroll
                     for (int p = 0; p < 2; p++) {
                         float2 ac = half ? acc[1][p] : acc[0][p];
@@ -1101,7 +1290,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         gwr[p] = ac.x;
                         gwi[p] = ac.y;
                         if (!a.no_update) {
-                            float *wq = reinterpret_cast<float *>(&Wt[p * M + tk]) + half * 2;
+                            float *wq = reinterpret_cast<float *>(&Wt[p * M + tj]) + oc * 2;
                             float wr = pw_w[p][0], wi = pw_w[p][1];
                             adam_update_fast(wr, pw_m[p][0], pw_v[p][0], gwr[p], ssW, bc2s);
                             adam_update_fast(wi, pw_m[p][1], pw_v[p][1], gwi[p], ssW, bc2s);
@@ -1113,13 +1302,13 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                     }
                 }
             }
-            if (a.dbg_gW && owner && f == a.n_frames - 1 && s == a.steps - 1) {
+            if (a.dbg_gW && ownr && f == a.n_frames - 1 && s == a.steps - 1) {
 #pragma unroll
                 for (int p = 0; p < 2; p++) {
-                    a.dbg_gW[gbase + (half * 4 + p) * M + tk] = gwr[p];
-                    a.dbg_gW[gbase + (half * 4 + 2 + p) * M + tk] = gwi[p];
-                    a.dbg_gh[gbase + ((half * 2 + p) * 2 + 0) * M + tk] = ghr[p];
-                    a.dbg_gh[gbase + ((half * 2 + p) * 2 + 1) * M + tk] = ghi[p];
+                    a.dbg_gW[gbase + (oc * 4 + p) * M + tj] = gwr[p];
+                    a.dbg_gW[gbase + (oc * 4 + 2 + p) * M + tj] = gwi[p];
+                    a.dbg_gh[gbase + ((oc * 2 + p) * 2 + 0) * M + tj] = ghr[p];
+                    a.dbg_gh[gbase + ((oc * 2 + p) * 2 + 1) * M + tj] = ghi[p];
                 }
             }
             sync_lds<NW>();
@@ -1135,16 +1324,16 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 #endif
 
     // ---- state out
-    if (owner && !a.no_update) {
+    if (ownr && !a.no_update) {
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            const size_t ir = gbase + (half * 4 + p) * M + tk, ii = gbase + (half * 4 + 2 + p) * M + tk;
-            const float *wq = reinterpret_cast<const float *>(&Wt[p * M + tk]) + half * 2;
+            const size_t ir = gbase + (oc * 4 + p) * M + tj, ii = gbase + (oc * 4 + 2 + p) * M + tj;
+            const float *wq = reinterpret_cast<const float *>(&Wt[p * M + tj]) + oc * 2;
             a.W[ir] = wq[0]; a.W[ii] = wq[1];
             a.adam_mW[ir] = mWr(p); a.adam_mW[ii] = mWi(p);
             a.adam_vW[ir] = vWr(p); a.adam_vW[ii] = vWi(p);
-            const size_t hr = gbase + ((half * 2 + p) * 2 + 0) * M + tk, hi = hr + M;
-            const float2 hh = Ht[(half * 2 + p) * MP + tk];
+            const size_t hr = gbase + ((oc * 2 + p) * 2 + 0) * M + tj, hi = hr + M;
+            const float2 hh = Ht[(oc * 2 + p) * MP + tj];
             a.h[hr] = hh.x; a.h[hi] = hh.y;
             a.adam_mh[hr] = mHr(p); a.adam_mh[hi] = mHi(p);
             a.adam_vh[hr] = vHr(p); a.adam_vh[hi] = vHi(p);

@@ -232,7 +232,7 @@ __device__ __forceinline__ float wave_incl_scan(float v, int lane)              
 
 // polyphase-4 row length (in float2) for a sample-rate array of `len` cells: phase arrays end up 16 (mod 64) dwords apart, so
 // the stride-4 reads of consecutive lanes are bank-conflict free
-__host__ __device__ inline int wave_lph(int len)
+__host__ __device__ constexpr inline int wave_lph(int len)
 {
     int lph = (len + 3) / 4 + 1;
     while ((lph & 31) != 8 && (lph & 31) != 24) lph++;
