@@ -197,8 +197,9 @@ def errors(post, bits, t0, n, depth):
         return (post < 0) != (tx & 1).astype(bool)
 
 
-def outer(post, bits, m, t, n_o, C_o, K, spread, t0=0, depth=None):
-    """-> (out[R, C_o, 4] int64 = status, pre_err, post_err, nflip; loc[R, C_o, t] int16; the Counter of the branches)."""
+def outer(post, bits, m, t, n_o, C_o, K, spread, t0=0, depth=None, memo=None):
+    """-> (out[R, C_o, 4] int64 = status, pre_err, post_err, nflip; loc[R, C_o, t] int16; the Counter of the branches).  memo: a dict that
+    keeps decode()'s answer and branches per error pattern, for tensors of many thousand codewords drawn from few patterns."""
     R, C, n = post.shape
     assert C_o * n_o <= C * K and 1 <= K <= n
     e = errors(post, bits, t0, n, depth)
@@ -208,7 +209,15 @@ def outer(post, bits, m, t, n_o, C_o, K, spread, t0=0, depth=None):
         pat = e[r][c, i]                                        # [C_o, n_o]
         for a in range(C_o):
             pos = [int(p) for p in np.nonzero(pat[a])[0]]
-            status, flips = decode(m, t, n_o, pos, count)
+            if memo is None:
+                status, flips = decode(m, t, n_o, pos, count)
+            else:
+                key = (m, t, n_o, tuple(pos))
+                if key not in memo:
+                    own = collections.Counter()
+                    memo[key] = decode(m, t, n_o, pos, own) + (own,)
+                status, flips, own = memo[key]
+                count.update(own)
             left = set(pos) ^ set(flips)
             out[r, a] = status, len(pos), len(left), len(flips)
             loc[r, a, :len(flips)] = flips

@@ -72,6 +72,27 @@ def test_the_edges_of_the_ranges_pass_every_rule_but_the_last(over):
     assert _call(dict(d, m=3)) == SHAPE and _call(dict(d, post=None)) == NULL
 
 
+@pytest.mark.parametrize("m", range(4, 14))
+def test_the_lengths_on_both_sides_of_the_envelope_are_refused(m):
+    """Every admissible (m, t): n_o == parity(m, t), which leaves no message bit, and n_o == 2^m, one past the full length, are refused, and
+    by the outer code's own rules alone -- one outer codeword on one LDPC codeword of 8192 payload bits, so every other rule passes, the fit
+    included.  The entry point's own coset walk is reached in no other way; that n_o == parity + 1 is accepted and decoded is
+    tests/test_bch_envelope_gpu.py's to show."""
+    import _ref_bch as B
+    q, seen = (1 << m) - 1, 0
+    for t in range(1, 17):
+        par = B.parity(m, t)
+        if par >= q:
+            continue
+        seen += 1
+        for n_o in (par, 1 << m):
+            d = _base(C=1, n=8192, K=8192, N=-(-8192 // 12), t0=0, m=m, t=t, n_o=n_o, C_o=1)
+            assert d["C_o"] * d["n_o"] <= d["C"] * d["K"] and d["t0"] * d["w"] + d["C"] * d["n"] <= d["N"] * d["w"]
+            assert _call(d) == SHAPE, (m, t, n_o)
+            assert _call(dict(d, R=0)) == OK and _call(dict(d, out=None)) == NULL
+    assert seen == {4: 7, 5: 15}.get(m, 16)
+
+
 def test_declared_and_exported():
     import os
     from vae_equalizer_amd import _native as nat

@@ -26,6 +26,82 @@ def test_parity_values():
     assert B.parity(4, 8) == 15                             # 2t reaches 2^m - 1: every coset, the one of 0 among them
 
 
+def _pmul(a, b):
+    """The product of two polynomials over GF(2), bit k the coefficient of x^k."""
+    r = 0
+    while b:
+        if b & 1:
+            r ^= a
+        a, b = a << 1, b >> 1
+    return r
+
+
+def _pdivmod(a, b):
+    q = 0
+    while a.bit_length() >= b.bit_length():
+        s = a.bit_length() - b.bit_length()
+        q, a = q | 1 << s, a ^ b << s
+    return q, a
+
+
+def _pgcd(a, b):
+    while b:
+        a, b = b, _pdivmod(a, b)[1]
+    return a
+
+
+def _minimal_polynomial(m, j):
+    """The monic polynomial over GF(2) of least degree with the root beta = alpha^j, with no walk over the conjugates: the first power beta^d
+    that is a GF(2) combination of 1, beta, .., beta^(d-1) (m-bit vectors, by elimination) gives x^d + that combination."""
+    exp, _ = B.tables(m)
+    q = (1 << m) - 1
+    basis = {}                                              # leading bit -> (reduced vector, the polynomial in beta that produced it)
+    for d in range(m + 1):
+        v, p = int(exp[j * d % q]), 1 << d
+        while v and v.bit_length() - 1 in basis:
+            bv, bp = basis[v.bit_length() - 1]
+            v, p = v ^ bv, p ^ bp
+        if v == 0:
+            return p
+        basis[v.bit_length() - 1] = (v, p)
+    raise AssertionError("m + 1 vectors of m bits are dependent")
+
+
+def _evaluate(m, poly, j):
+    """poly(alpha^j) in GF(2^m)."""
+    exp, _ = B.tables(m)
+    q, v = (1 << m) - 1, 0
+    for k in range(poly.bit_length()):
+        if (poly >> k) & 1:
+            v ^= int(exp[j * k % q])
+    return v
+
+
+@pytest.mark.parametrize("m", sorted(B.POLY))
+def test_parity_over_the_envelope(m):
+    """All 16 values of t: parity(m, t) is the degree of the generator, the lcm of the minimal polynomials of alpha^1 .. alpha^2t built by
+    polynomial arithmetic over GF(2) -- something that is no coset walk for the three coset walks (this model's, engine.BchCode's and, through
+    it and tests/test_abi_refusals_bch_host.py, the entry point's) to answer to -- and BchCode holds that value or refuses the pair."""
+    from vae_equalizer_amd.engine import BchCode
+    q, g, seen = (1 << m) - 1, 1, []
+    for t in range(1, 17):
+        for j in (2 * t - 1, 2 * t):
+            f = _minimal_polynomial(m, j)
+            assert _evaluate(m, f, j) == 0 and f.bit_length() - 1 <= m
+            g = _pmul(g, _pdivmod(f, _pgcd(g, f))[0])      # lcm(g, f)
+        assert all(_evaluate(m, g, j) == 0 for j in range(1, 2 * t + 1)) and _pdivmod((1 << q) | 1, g)[1] == 0   # g divides x^q + 1
+        seen.append(g.bit_length() - 1)
+        assert B.parity(m, t) == g.bit_length() - 1, (m, t)
+        if B.parity(m, t) < q:
+            code = BchCode(m, t)
+            assert code.parity == B.parity(m, t) and code.n == q and code.k == q - code.parity
+        else:
+            with pytest.raises(ValueError):
+                BchCode(m, t)
+    print(m, seen)
+    assert seen == sorted(seen) and seen[0] == m
+
+
 def _patterns(n_o, wt, rng):
     if math.comb(n_o, wt) <= LIMIT:
         return [list(p) for p in itertools.combinations(range(n_o), wt)]
