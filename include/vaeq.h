@@ -660,6 +660,7 @@ int vaeq_awgn_dfe_soft(int32_t R, int64_t N, int32_t n_lev, int32_t K2, const fl
  * out[R][C][5] int32 = iters (full iterations executed: 0 for a codeword that passes the first test), ok (the test passed at exit), post_err
  * (decisions of the final L against the TX bits, over the n bits), pre_err (the same of the input), erased (inputs equal to +-0).
  * post[R][C][n] float32 (nullable): the final L in codeword order.
+ * The LLRs must not be NaN here: what a NaN does to the minimum search is not fixed (vaeq_ldpc_decode_q maps a NaN to +0).
  * One workgroup per codeword, one thread per check of the layer in flight, the whole state in LDS: vaeq_ldpc_lds_bytes(mb, nb, Z) bytes (L,
  * the TX bits as bytes, 16 bytes per check), VAEQ_ERR_SHAPE from that call outside the ranges of mb, nb and Z below.  Integer counts and a
  * fixed operation order: two calls give identical bits.

@@ -50,6 +50,9 @@ CASES = [
     ("row-weight-1", _base(shifts=_holes(3, 6, 7, 1)), SHAPE), ("row-weight-0", _base(shifts=_holes(3, 6, 7, 0)), SHAPE),
     ("row-weight-33", _base(mb=2, nb=33, Z=37, N=4000, shifts=_table(2, 33, 37)), SHAPE),
     ("oversize-state", _base(mb=8, nb=32, Z=512, N=40000, shifts=_table(8, 32, 512)), SHAPE),
+    # nb = 64 next to the 64 KiB: Z = 186 is 65 472 bytes (tests/test_ldpc_envelope_gpu.py decodes it), Z = 187 is 65 824; the table is good (32 blocks per row)
+    ("state-65824-at-nb=64", _base(mb=2, nb=64, Z=187, N=5000, shifts=_holes(2, 64, 187, 32)), SHAPE),
+    ("row-weight-64-at-nb=64", _base(mb=2, nb=64, Z=186, N=5000, shifts=_table(2, 64, 186)), SHAPE),
 ]
 
 
@@ -73,6 +76,7 @@ def test_lds_bytes():
     assert f(4, 24, 211) == 4 * 5064 + 5064 + 16 * 844                            # L, the TX bits as bytes, 16 bytes per check
     assert f(3, 6, 7) == 4 * 42 + 44 + 16 * 21                                    # (the bytes padded to whole words)
     assert f(8, 32, 512) > 64 * 1024 >= f(2, 8, 512)
+    assert f(2, 64, 186) == 65472 <= 64 * 1024 < f(2, 64, 187) == 65824            # the two sides of the limit at the most block columns
     for bad in ((0, 6, 7), (9, 6, 7), (3, 1, 7), (3, 65, 7), (3, 6, 1), (3, 6, 513)):
         assert f(*bad) == SHAPE
 

@@ -59,6 +59,11 @@ CASES = [
     ("row-weight-1", _base(shifts=_holes(3, 6, 7, 1)), SHAPE), ("row-weight-0", _base(shifts=_holes(3, 6, 7, 0)), SHAPE),
     ("row-weight-33", _base(mb=2, nb=33, Z=37, N=4000, shifts=_table(2, 33, 37)), SHAPE),
     ("oversize-state", _base(mb=8, nb=64, Z=512, N=40000, shifts=_table(8, 64, 512)), SHAPE),
+    # nb = 64 next to the 64 KiB: 3 n + 8 m = 208 Z at mb = 2, so Z = 315 is 65 520 bytes (tests/test_ldpc_envelope_gpu.py decodes it) and Z = 316 is
+    # 65 728; the table is good (32 blocks per row), bit-packed and behind the interleaver
+    ("state-65728-at-nb=64", _base(mb=2, nb=64, Z=316, N=9000, shifts=_holes(2, 64, 316, 32)), SHAPE),
+    ("state-65728-at-nb=64-depth=5", _base(mb=2, nb=64, Z=316, N=9000, depth=5, shifts=_holes(2, 64, 316, 32)), SHAPE),
+    ("row-weight-64-at-nb=64", _base(mb=2, nb=64, Z=315, N=9000, shifts=_table(2, 64, 315)), SHAPE),
     # the interleaver's fit rule at depth >= 1: 5 codewords of S = 4 symbols need 20 symbols behind t0, the base N has 18
     ("depth=2-symbol-aligned-fit", _base(depth=2, **GOOD), SHAPE), ("depth=1-symbol-aligned-fit", _base(depth=1, N=11 + 19, **GOOD), SHAPE),
     # one case per rule of the fixed-point decoder
@@ -103,6 +108,8 @@ def test_lds_bytes():
     assert f(1, 3, 7) == 44 + 24 + 8 * 7                                          # (the 42 bytes of L and the 21 of the bits, both padded)
     assert f(3, 32, 512) == 61440 <= 64 * 1024 < g(3, 32, 512)                    # a code the float decoder must refuse
     assert f(8, 64, 512) > 64 * 1024
+    assert f(2, 64, 315) == 208 * 315 == 65520 <= 64 * 1024 < f(2, 64, 316) == 65728   # the two sides of the limit at the most block columns
+    assert g(2, 64, 186) == 65472 and f(2, 64, 186) == 208 * 186
     for bad in ((0, 6, 7), (9, 6, 7), (3, 1, 7), (3, 65, 7), (3, 6, 1), (3, 6, 513)):
         assert f(*bad) == SHAPE
 

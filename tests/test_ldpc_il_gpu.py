@@ -17,37 +17,9 @@ import torch
 
 import _ref_ldpc as M
 import _ref_ldpc_il as IL
+from _ldpc_cases import _check, _counters, _decode
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _decode(shifts, Z, llr, bits, **kw):
-    from vae_equalizer_amd.engine import LdpcCode, ldpc_decode
-    r = ldpc_decode(llr, bits, LdpcCode(shifts, Z), want_post=True, **kw)
-    torch.cuda.synchronize()
-    return r
-
-
-def _counters(r):
-    return np.stack([r[k].cpu().numpy() for k in ("iters", "ok", "bit_err", "pre_err", "erased")], -1)
-
-
-def _check(r, want_out, want_post, n, tag):
-    got_out, got_post = _counters(r), r["post"].cpu().numpy()
-    print(f"{tag}: iters {np.bincount(want_out[..., 0].ravel()).tolist()} ok {int(want_out[..., 1].sum())}/{want_out[..., 1].size} "
-          f"pre_err {int(want_out[..., 3].sum())} post_err {int(want_out[..., 2].sum())} erased {int(want_out[..., 4].sum())}; "
-          f"counters differ in {int((got_out != want_out).sum())}, post in {int((_bits(got_post) != _bits(want_post)).sum())} of {want_post.size}")
-    assert got_out.dtype == np.int64 and got_post.dtype == np.float32 and got_post.shape == want_post.shape
-    assert np.array_equal(got_out, want_out)
-    assert np.array_equal(got_post, want_post) and np.array_equal(_bits(got_post), _bits(want_post))
-    C = want_out.shape[1]
-    assert np.array_equal(r["BER_post"].cpu().numpy(), (want_out[..., 2].sum(1) / np.float32(C * n)).astype(np.float32))
-    assert np.array_equal(r["BER_pre"].cpu().numpy(), (want_out[..., 3].sum(1) / np.float32(C * n)).astype(np.float32))
-    assert np.array_equal(r["FER"].cpu().numpy(), (want_out[..., 2] > 0).mean(1).astype(np.float32))
 
 
 @pytest.mark.parametrize("depth", IL.DEPTHS)
