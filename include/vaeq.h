@@ -719,6 +719,48 @@ int vaeq_ldpc_decode_q(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, i
                        int32_t beta, int32_t max_iter, int32_t *out, int16_t *post, void *stream);
 int64_t vaeq_ldpc_q_lds_bytes(int32_t mb, int32_t nb, int32_t Z);
 
+/* Spatially coupled LDPC codes with a sliding-window decoder: a terminated chain of Lc positions, far longer than what vaeq_ldpc_decode can hold
+ * in LDS, decoded by a window of W row-block positions that slides along it (no reference counterpart).
+ * The code: components_host[ms + 1][mb][nb] int32 in HOST memory, -1 = a zero block, 0 <= s < Z = vaeq_ldpc_decode's Z x Z circulant (check i to
+ * variable (i + s) mod Z of its block).  The coupled matrix has block rows (t, l), t = 0 .. Lc + ms - 1, l = 0 .. mb - 1, row block index t mb + l,
+ * and block columns (i, c), i = 0 .. Lc - 1, c = 0 .. nb - 1, column block index i nb + c; block ((t, l), (i, c)) is components[t - i][l][c] when
+ * 0 <= t - i <= ms and zero otherwise.  n_chain = Lc nb Z bits, (Lc + ms) mb Z checks, design rate 1 - (Lc + ms) mb / (Lc nb); the chain is
+ * terminated, its first and last ms row blocks are lighter.
+ * The tensors llr[R][w][N], bits[R][w][N] and the bit map are vaeq_ldpc_decode's with n = n_chain: C chains per run, bit j of chain c is global
+ * bit g = c n_chain + j at symbol t0 + g / w, plane g % w, and t0 w + C n_chain <= N w.  Column block i of chain c is thus codeword c Lc + i of
+ * nb Z bits of that map.  No encoder: coset decoding towards the syndrome of the TX bits.
+ *   start      as in vaeq_ldpc_decode: L[v] = llr of bit v, sigma = the parity of the TX bits on each check, every check's (m1, m2, idx, signs)
+ *              zero; pre_err and erased are counted on the input over the n_chain bits.
+ *   positions  p = 0 .. P - 1, P = max(1, Lc + ms - W + 1).  The active rows at p are t in [p, min(p + W, Lc + ms)), every l.
+ *   test       H x = sigma on the hard decisions L < 0, restricted to the rows t in [p, min(p + T, Lc + ms)) for p < P - 1 and to all active
+ *              rows at the last position; before the first iteration of a position and after every full one.  The position ends at success
+ *              or after `iters` iterations.
+ *   iteration  the active layers in ascending (t, l), each exactly vaeq_ldpc_decode's layer update with the same float32 operations, each
+ *              rounded on its own; the edges of a check in ascending coupled block column: i ascending (t - i descending), then c ascending;
+ *              idx = the first edge that attains m1.  Edges whose i falls outside [0, Lc) do not exist.
+ *   between    nothing is reset.  Rows that stay keep their state, row p is never visited again, row p + W starts from zeros when it enters.
+ *              Column blocks p - ms .. p - 1 stay in the window and are updated like any other (they are not frozen).  Column block i is
+ *              final once position min(i + ms, P - 1) has ended.
+ * out[R][C][6] int32 = iters (the sum over the positions), ok (1 iff the last test of every position passed), post_err (the final decisions
+ * against the TX bits over n_chain), pre_err, erased, iters_max (the most iterations at any one position).  Nullable: post[R][C][n_chain]
+ * float32, the final L; pos_err[R][C][Lc] int32, the errors of each column block in its final state (the decoding wave, and how errors
+ * propagate along the chain); pos_iters[R][C][P] int32, the iterations of each position.
+ * When W >= Lc + ms there is one position and its test covers every row: the call equals vaeq_ldpc_decode on the coupled
+ * shifts[(Lc + ms) mb][Lc nb] with max_iter = iters, in the five shared counters and in every bit of post.
+ * One workgroup per chain, one thread per check of the layer in flight.  The window is a ring in LDS, vaeq_ldpc_sc_lds_bytes(ms, mb, nb, Z, W):
+ * W + ms column blocks (L as float32, the TX bits as bytes padded to a word) and 16 bytes per check of W row blocks; VAEQ_ERR_SHAPE from that
+ * call outside the ranges of ms, mb, nb, Z and W below.  The LLRs must not be NaN.  Integer counts and a fixed order: two calls give identical bits.
+ * Refusals, all before any HIP call and in vaeq_ldpc_decode's order: R == 0 is VAEQ_OK (its pointers may be NULL); a NULL components_host, llr,
+ * bits or out is VAEQ_ERR_NULL, before any shape rule; then VAEQ_ERR_SHAPE for R < 0, C < 1, N < 1, N > 0x3fffffff, w outside 1 .. 64, t0 < 0,
+ * t0 > N, iters outside 1 .. 100, ms outside 1 .. 7, mb outside 1 .. 4, nb outside 2 .. 32, Z outside 2 .. 512, W outside ms + 1 .. 32, Lc outside
+ * 1 .. 65535, T outside 1 .. W; for a state above 64 KiB, t0 w + C n_chain > N w, R C > 0x7fffffff and C Lc > 0x7fffffff (a column block's
+ * codeword index); last for the table: a shift < -1 or >= Z, an l with more than 32 non-zero blocks over its ms + 1 components, a block row
+ * (t, l) of the coupled matrix with fewer than 2 non-zero blocks, the truncated rows at both ends counted with the blocks they really have. */
+int vaeq_ldpc_sc_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t ms, int32_t mb, int32_t nb, int32_t Z, int32_t Lc,
+                        const int32_t *components_host, const float *llr, const int8_t *bits, int32_t W, int32_t T, float alpha, int32_t iters,
+                        int32_t *out, float *post, int32_t *pos_err, int32_t *pos_iters, void *stream);
+int64_t vaeq_ldpc_sc_lds_bytes(int32_t ms, int32_t mb, int32_t nb, int32_t Z, int32_t W);
+
 /* The outer code behind the LDPC decoders: a bounded-distance hard-decision decoder of a shortened binary BCH code over the payload bits of
  * `post`, so that the figure an optical-FEC comparison is judged by -- errors after the outer code -- is counted on the device.  As with the inner
  * code there is no encoder: the result depends on the error pattern alone.

@@ -68,7 +68,7 @@ n1 = (lmmse_filter_order - 1) // 2 + 1
 N_SHIFT_LMMSE, N_SHIFT_DFE = 21, 24                    # find_shift_symb lags (:280, :292)
 
 info_metrics = False    # True: main() also returns the info dicts of both curves (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp)
-fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=engine.BchCode, ...) puts engine.bch_outer behind it, and the .mat also gains BER_outer and FER_outer): main() also returns engine.ldpc_decode's figures of both curves' LLRs
+fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=engine.BchCode, ...) puts engine.bch_outer behind it, and the .mat also gains BER_outer and FER_outer; code=engine.ScLdpcCode takes window, iters and test in place of max_iter, depth and quant and decodes with engine.ldpc_sc_decode): main() also returns engine.ldpc_decode's figures of both curves' LLRs
 base_seed = None        # int -> reproducible frames (the reference's stream under the same seed); None = like the reference
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
 

@@ -781,6 +781,100 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, 
     return ret
 
 
+class ScLdpcCode:
+    """A spatially coupled LDPC code for ldpc_sc_decode: components[ms + 1, mb, nb] of circulant shifts (-1 = a zero block, 0 <= s < Z as in
+    LdpcCode) coupled into a terminated chain of L positions.  Block row (t, l), t = 0 .. L + ms - 1, holds components[t - i, l, c] in block
+    column (i, c) for 0 <= t - i <= ms.  .ms, .mb, .nb, .Z, .L; .n = L nb Z bits (n_chain), .m = (L + ms) mb Z checks, .rate = the design rate
+    1 - (L + ms) mb / (L nb).  The decoder's envelope is vaeq_ldpc_sc_decode's to refuse."""
+
+    def __init__(self, components, Z, L):
+        import numpy as np
+        self.components = np.ascontiguousarray(np.asarray(components, dtype=np.int32))
+        if self.components.ndim != 3 or self.components.shape[0] < 1:
+            raise ValueError(f"expected components[ms + 1, mb, nb], got shape {self.components.shape}")
+        self.Z, self.L = int(Z), int(L)
+        if self.L < 1:
+            raise ValueError(f"a chain has at least one position, got L={L}")
+        self.ms = int(self.components.shape[0]) - 1
+        self.mb, self.nb = (int(d) for d in self.components.shape[1:])
+        self.n, self.m = self.L * self.nb * self.Z, (self.L + self.ms) * self.mb * self.Z
+        self.rate = 1.0 - (self.L + self.ms) * self.mb / (self.L * self.nb)
+
+    def coupled(self):
+        """The LdpcCode of the coupled shifts[(L + ms) mb, L nb] (for tests and small chains)."""
+        import numpy as np
+        s = np.full(((self.L + self.ms) * self.mb, self.L * self.nb), -1, np.int32)
+        for i in range(self.L):
+            for d in range(self.ms + 1):
+                s[(i + d) * self.mb:(i + d + 1) * self.mb, i * self.nb:(i + 1) * self.nb] = self.components[d]
+        return LdpcCode(s, self.Z)
+
+
+def sc_array_code(ms, nb, Z, L):
+    """The coupled array code: mb = 1, shift (2^d (2c + 1)) mod Z in component d, column c; column weight ms + 1, row weight (ms + 1) nb.
+    For a prime Z > (2 nb - 1) 2^ms the coupled matrix has no 4-cycles.  Why: write b = 2c + 1, odd and at most 2 nb - 1.  A 4-cycle joins two
+    row blocks t > t' and two block columns, b at offsets d, d' and b' at offsets e, e' with d - d' = e - e' = t - t' = k, and needs
+    b (2^d - 2^d') = b' (2^e - 2^e') mod Z, that is b 2^d' (2^k - 1) = b' 2^e' (2^k - 1).  0 < 2^k - 1 < Z is invertible modulo the prime Z,
+    so b 2^d' = b' 2^e' mod Z; both sides are integers below Z, so they are equal as integers, and an odd number times a power of two factors
+    in one way: b = b' and d' = e', the same block column twice.  tests/test_ref_ldpc_sc_host.py checks H^T H."""
+    import numpy as np
+    d, c = np.arange(int(ms) + 1)[:, None, None], np.arange(int(nb))[None, None, :]
+    return ScLdpcCode((2 ** d * (2 * c + 1)) % int(Z), Z, L)
+
+
+def ldpc_sc_decode(llr, bits, code, window, t0=0, chains=None, iters=10, alpha=None, test=None, want_post=False, want_profile=False, outer=None):
+    """Post-FEC figures of per-bit LLRs under a spatially coupled code on the device (vaeq_ldpc_sc_decode): a window of `window` row-block
+    positions slides along the chain of the ScLdpcCode `code`; at each of the P = max(1, L + ms - window + 1) positions at most `iters`
+    iterations of ldpc_decode's layered normalized min-sum over the rows inside, until the rows of the first `test` positions of the window
+    (default ms + 1: the rows that touch the block about to leave) are satisfied.  llr, bits, t0 and the bit map as for ldpc_decode with
+    n = code.n; chains: per run, default the most that fit behind t0.  alpha defaults to 0.75.
+    -> ldpc_decode's dict, a chain where it has a codeword (iters [R,C]: the sum over the positions; ok: every position's last test passed; FER:
+    the share of chains with bit_err > 0), plus iters_max [R,C] (the most iterations at one position) and positions (P).  want_post:
+    post[R,C,n] f32.  want_profile: pos_err [R,C,L] (the errors of each column block in its final state) and pos_iters [R,C,P].
+    outer: as for ldpc_decode, bch_outer over the final LLRs seen as [R, C L, nb Z]: every column block is a codeword of nb Z bits under the
+    same bit map, its first (nb - mb) Z bits the default payload.  No interleaver and no fixed point here."""
+    if not isinstance(code, ScLdpcCode):
+        raise ValueError(f"ldpc_sc_decode takes an ScLdpcCode, got {code!r}")
+    if outer is not None:
+        outer = resolve_outer(outer, code)
+    alpha = 0.75 if alpha is None else alpha
+    test = code.ms + 1 if test is None else test
+    if llr.shape != bits.shape or llr.dim() not in (3, 4):
+        raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
+    dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
+    llr = llr.reshape(R, -1, N).contiguous()
+    bits = bits.reshape(R, -1, N).contiguous()
+    w, n = llr.shape[1], code.n
+    C_ = int(chains) if chains is not None else _ldpc_fit(N, w, n, t0, None)
+    if chains is None and C_ < 1:
+        raise ValueError(f"no chain of {n} bits fits into {N - int(t0)} symbols of {w} bits")
+    P = max(1, code.L + code.ms - int(window) + 1)
+    Cn = max(C_, 0)
+    out = torch.empty(R, Cn, 6, dtype=torch.int32, device=dev)
+    post = torch.empty(R, Cn, n, dtype=torch.float32, device=dev) if want_post or outer is not None else None
+    pos_err = torch.empty(R, Cn, code.L, dtype=torch.int32, device=dev) if want_profile else None
+    pos_iters = torch.empty(R, Cn, P, dtype=torch.int32, device=dev) if want_profile else None
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_ldpc_sc_decode(R, C_, N, w, int(t0), code.ms, code.mb, code.nb, code.Z, code.L,
+                                                code.components.ctypes.data_as(C.c_void_p), nat.ptr(llr), nat.ptr(bits, torch.int8), int(window),
+                                                int(test), float(alpha), int(iters), nat.ptr(out, torch.int32), nat.ptr(post),
+                                                nat.ptr(pos_err, torch.int32), nat.ptr(pos_iters, torch.int32), nat.current_stream(dev)),
+                  "vaeq_ldpc_sc_decode")
+    o = out.long()
+    tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)
+    ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
+               BER_post=(o[..., 2].sum(1).double() / tot).float(), BER_pre=(o[..., 3].sum(1).double() / tot).float(),
+               FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float(), iters_max=o[..., 5], positions=P)
+    if want_post:
+        ret["post"] = post
+    if want_profile:
+        ret["pos_err"], ret["pos_iters"] = pos_err.long(), pos_iters.long()
+    if outer is not None:
+        ret["outer"] = bch_outer(post.view(R, Cn * code.L, code.nb * code.Z), bits, outer["code"], code.nb * code.Z, t0=t0, payload=outer["payload"],
+                                 spread=outer["spread"], codewords=outer["codewords"])
+    return ret
+
+
 class BchCode:
     """A narrow-sense primitive binary BCH code over GF(2^m) with designed correction t, shortened to n bits (default 2^m - 1), for bch_outer:
     .m, .t, .n, .parity (the size of the union of the cyclotomic cosets of 1 .. 2t modulo 2^m - 1), .k = n - parity, .rate = k / n.  ValueError
@@ -820,7 +914,8 @@ def resolve_outer(outer, code=None):
     payload = outer.get("payload")
     if payload is None and code is not None:
         payload = (code.nb - code.mb) * code.Z
-    if payload is not None and (int(payload) < 1 or (code is not None and int(payload) > code.n)):
+    n = None if code is None else code.nb * code.Z             # (a column block of an ScLdpcCode is the codeword of the outer decoder's map)
+    if payload is not None and (int(payload) < 1 or (n is not None and int(payload) > n)):
         raise ValueError(f"outer['payload'] = {payload}: the first 1 .. n bits of a codeword")
     return dict(code=outer["code"], payload=None if payload is None else int(payload), spread=bool(outer.get("spread", True)),
                 codewords=outer.get("codewords"))
@@ -868,13 +963,21 @@ def bch_outer(post, bits, code, n, t0=0, depth=None, payload=None, spread=True, 
     return ret
 
 
-FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant", "outer")
+FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant", "window", "iters", "test", "outer")
+FEC_BLOCK_ONLY, FEC_SC_ONLY = ("max_iter", "depth", "quant"), ("window", "iters", "test")
 
 
 def check_fec(fec):
     """ValueError for a fec= dict that fec_figures would refuse (None passes): for a runner to call before it allocates or launches anything."""
     if fec is not None and (set(fec) - set(FEC_KEYS) or "code" not in fec):
         raise ValueError(f"fec takes {', '.join(FEC_KEYS)}; got {sorted(fec)}")
+    if fec is not None:
+        sc = isinstance(fec["code"], ScLdpcCode)
+        wrong = [k for k in (FEC_BLOCK_ONLY if sc else FEC_SC_ONLY) if k in fec]
+        if wrong:
+            raise ValueError(f"fec with {'an ScLdpcCode' if sc else 'an LdpcCode'} does not take {', '.join(wrong)}")
+        if sc and fec.get("window") is None:
+            raise ValueError("fec with an ScLdpcCode needs window, the row-block positions inside the decoding window")
     if fec is not None and fec.get("quant") is not None:
         resolve_quant(fec["quant"])
         if fec.get("alpha") is not None:
@@ -894,18 +997,20 @@ def fec_figures(llr, fec):
     """The batch runners' fec= : ldpc_decode of an "llr" dict (llr, bits) under fec = dict(code, t0, max_iter, alpha, depth, quant, outer; all but
     code optional; quant = dict(bits, ...) decodes in fixed point, vaeq_ldpc_decode_q; outer = dict(code=BchCode, ...) adds bch_outer's figures
     under "outer").  With an outer code the runs are walked in chunks whose `post` stays within OUTER_POST_BYTES; codewords are independent, so
-    the figures are those of one call."""
+    the figures are those of one call.  With an ScLdpcCode under code it is ldpc_sc_decode under fec = dict(code, window, t0, iters, alpha, test,
+    outer; code and window required): max_iter, depth and quant are a ValueError there, as window, iters and test are with an LdpcCode."""
     check_fec(fec)
     kw = {k: v for k, v in fec.items() if k != "code"}
     L, B = llr["llr"], llr["bits"]
+    decode = ldpc_sc_decode if isinstance(fec["code"], ScLdpcCode) else ldpc_decode
     if fec.get("outer") is None or L.shape[0] == 0:
-        return ldpc_decode(L, B, fec["code"], **kw)
+        return decode(L, B, fec["code"], **kw)
     R, N, n = L.shape[0], L.shape[-1], fec["code"].n
     w = L.numel() // max(R * N, 1)
     C_ = int(kw["codewords"]) if kw.get("codewords") is not None else _ldpc_fit(N, w, n, kw.get("t0", 0), kw.get("depth"))
     per_run = max(C_, 1) * n * (4 if fec.get("quant") is None else 2)
     step = max(1, int(OUTER_POST_BYTES) // per_run)
-    return _cat_figures([ldpc_decode(L[r:r + step], B[r:r + step], fec["code"], **kw) for r in range(0, R, step)])
+    return _cat_figures([decode(L[r:r + step], B[r:r + step], fec["code"], **kw) for r in range(0, R, step)])
 
 
 def cma_epilogue(y, data, amp_levels, nu_sc, var):
