@@ -761,6 +761,39 @@ int vaeq_ldpc_sc_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, 
                         int32_t *out, float *post, int32_t *pos_err, int32_t *pos_iters, void *stream);
 int64_t vaeq_ldpc_sc_lds_bytes(int32_t ms, int32_t mb, int32_t nb, int32_t Z, int32_t W);
 
+/* The fixed-point window decoder: vaeq_ldpc_sc_decode's sliding window with vaeq_ldpc_decode_q's integer layer rule, as a hardware window decoder
+ * holds its 4 to 6-bit LLRs and messages.  Like vaeq_ldpc_decode_q and unlike vaeq_ldpc_sc_decode it sees the scale of the LLRs.  Both comments
+ * above hold word for word where they are named here; nothing of them is restated.
+ * From vaeq_ldpc_sc_decode, unchanged: the code components_host[ms + 1][mb][nb], the coupled matrix, the tensors and the bit map with n = n_chain;
+ * coset decoding without an encoder; the positions p = 0 .. P - 1, the active rows, the test rows T and when the test runs (on L < 0); the layer
+ * order (ascending (t, l)) and the edge order (ascending coupled block column); "between": nothing is reset, a row starts from zeros when it
+ * enters, and a column block is final once position min(i + ms, P - 1) has ended; out[R][C][6], pos_err[R][C][Lc] and pos_iters[R][C][P].
+ * From vaeq_ldpc_decode_q, unchanged: the constants Cmax = Mmax and Lmax; the quantiser (float32 multiply, a NaN becomes +0, clamp, rint with ties
+ * to even), applied to every bit of the chain; pre_err counted on the raw input and erased counting Q == 0, both over the n_chain bits; f; the
+ * layer update in integers -- t_e exact, the clamp to Mmax before the minimum search, idx the first edge that attains m1 after the clamp,
+ * L = min(max(t_e + r'_e, -Lmax), Lmax); negative means < 0.
+ * Edge numbering: an edge's number e is its number in the full row (i ascending, then c ascending, over all ms + 1 components), wherever the row
+ * lies in the chain.  Edges whose i falls outside [0, Lc) do not exist: they contribute no magnitude to m1 and m2, no sign to S, can not be the
+ * specified idx, and nothing is written for them.
+ * post[R][C][n_chain] int16 (nullable): the final L; post_err and pos_err count L < 0 against the TX bits.
+ * When W >= Lc + ms there is one position and its test covers every row: the call equals vaeq_ldpc_decode_q with depth = 0 on the coupled
+ * shifts[(Lc + ms) mb][Lc nb] with max_iter = iters and the same qbits, abits, scale, num and beta, in the five shared counters and in every bit
+ * of post.
+ * One workgroup per chain, one thread per check of the layer in flight.  The window is a ring in LDS, vaeq_ldpc_sc_q_lds_bytes(ms, mb, nb, Z, W) =
+ * 2 (W + ms) nb Z (L as int16, padded to a word) + (W + ms) nb Z (the TX bits as bytes, padded to a word) + 8 W mb Z (one dword
+ * m1 | m2 << 8 | idx << 16 | sigma << 24 and one dword of signs per check of W row blocks), at most 64 KiB; VAEQ_ERR_SHAPE from that call outside
+ * the ranges of ms, mb, nb, Z and W, which are vaeq_ldpc_sc_decode's, as those of Lc, T and iters are.  Integers and a fixed order: two calls give
+ * identical bits.
+ * Refusals, all before any HIP call and in vaeq_ldpc_sc_decode's order: R == 0 is VAEQ_OK (its pointers may be NULL); a NULL components_host, llr,
+ * bits or out is VAEQ_ERR_NULL, before any shape rule; then VAEQ_ERR_SHAPE for vaeq_ldpc_sc_decode's shape rules with this state size; then for
+ * qbits outside 2 .. 8, abits outside qbits .. 15, a scale that is not finite or <= 0, num outside 1 .. 8, beta outside 0 .. 127; and last the
+ * table's rules. */
+int vaeq_ldpc_sc_decode_q(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t ms, int32_t mb, int32_t nb, int32_t Z, int32_t Lc,
+                          const int32_t *components_host, const float *llr, const int8_t *bits, int32_t W, int32_t T,
+                          int32_t qbits, int32_t abits, float scale, int32_t num, int32_t beta, int32_t iters,
+                          int32_t *out, int16_t *post, int32_t *pos_err, int32_t *pos_iters, void *stream);
+int64_t vaeq_ldpc_sc_q_lds_bytes(int32_t ms, int32_t mb, int32_t nb, int32_t Z, int32_t W);
+
 /* The outer code behind the LDPC decoders: a bounded-distance hard-decision decoder of a shortened binary BCH code over the payload bits of
  * `post`, so that the figure an optical-FEC comparison is judged by -- errors after the outer code -- is counted on the device.  As with the inner
  * code there is no encoder: the result depends on the error pattern alone.

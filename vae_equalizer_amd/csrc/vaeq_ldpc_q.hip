@@ -17,31 +17,11 @@
 
 #include "vaeq.h"
 #include "vaeq_launch.h"
-#include "vaeq_ldpc.h"
+#include "vaeq_ldpc_sc.h"
 
 namespace vaeq {
 
 inline int64_t ldpc_q_state_bytes(int64_t mb, int64_t nb, int64_t Z) { return ((2 * nb * Z + 3) & ~(int64_t)3) + ((nb * Z + 3) & ~(int64_t)3) + 8 * mb * Z; }
-
-// the median of three: the clamp to [lo, hi] of x, and the second smallest of (m1, m2, a) when m1 <= m2
-__device__ __forceinline__ int ldpc_med3(int a, int b, int c)
-{
-    int r;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-// x negated when bit e of sg is set
-__device__ __forceinline__ int ldpc_q_signed(int x, uint32_t sg, int e)
-{
-    const int mask = -(int)((sg >> e) & 1u);
-    return (x ^ mask) - mask;
-}
-
-struct ldpc_q_rule {
-    float scale;
-    int cmax, lmax, num, beta;                                 // Cmax = Mmax = 2^(qbits-1) - 1, Lmax = 2^(abits-1) - 1
-};
 
 template <bool IL>
 __global__ __launch_bounds__(LDPC_Z) void ldpc_q_kernel(const ldpc_table tab, int C, long long N, int w, long long t0, int mb, int nb, int Z,
@@ -187,8 +167,7 @@ extern "C" int vaeq_ldpc_decode_q(int32_t R, int32_t C, int64_t N, int32_t w, in
     const bool il = depth >= 1;
     const int64_t lds = ldpc_q_state_bytes(mb, nb, Z);
     if (!ldpc_shape_ok(R, C, N, w, t0, depth, mb, nb, Z, max_iter, lds, il)) return VAEQ_ERR_SHAPE;
-    if (qbits < 2 || qbits > 8 || abits < qbits || abits > 15 || !(scale > 0.f) || !isfinite(scale) || num < 1 || num > 8 || beta < 0 || beta > 127)
-        return VAEQ_ERR_SHAPE;
+    if (!ldpc_q_rule_ok(qbits, abits, scale, num, beta)) return VAEQ_ERR_SHAPE;
     ldpc_table tab;
     if (!ldpc_pack(mb, nb, Z, shifts_host, &tab)) return VAEQ_ERR_SHAPE;
     const ldpc_q_rule q = {scale, (1 << (qbits - 1)) - 1, (1 << (abits - 1)) - 1, (int)num, (int)beta};

@@ -822,7 +822,8 @@ def sc_array_code(ms, nb, Z, L):
     return ScLdpcCode((2 ** d * (2 * c + 1)) % int(Z), Z, L)
 
 
-def ldpc_sc_decode(llr, bits, code, window, t0=0, chains=None, iters=10, alpha=None, test=None, want_post=False, want_profile=False, outer=None):
+def ldpc_sc_decode(llr, bits, code, window, t0=0, chains=None, iters=10, alpha=None, test=None, want_post=False, want_profile=False, outer=None,
+                   quant=None):
     """Post-FEC figures of per-bit LLRs under a spatially coupled code on the device (vaeq_ldpc_sc_decode): a window of `window` row-block
     positions slides along the chain of the ScLdpcCode `code`; at each of the P = max(1, L + ms - window + 1) positions at most `iters`
     iterations of ldpc_decode's layered normalized min-sum over the rows inside, until the rows of the first `test` positions of the window
@@ -832,11 +833,18 @@ def ldpc_sc_decode(llr, bits, code, window, t0=0, chains=None, iters=10, alpha=N
     the share of chains with bit_err > 0), plus iters_max [R,C] (the most iterations at one position) and positions (P).  want_post:
     post[R,C,n] f32.  want_profile: pos_err [R,C,L] (the errors of each column block in its final state) and pos_iters [R,C,P].
     outer: as for ldpc_decode, bch_outer over the final LLRs seen as [R, C L, nb Z]: every column block is a codeword of nb Z bits under the
-    same bit map, its first (nb - mb) Z bits the default payload.  No interleaver and no fixed point here."""
+    same bit map, its first (nb - mb) Z bits the default payload.  No interleaver here.
+    quant: ldpc_decode's dict(bits, scale=None, app_bits=None, num=6, beta=0) with its defaults decodes in fixed point instead
+    (vaeq_ldpc_sc_decode_q): the same window with ldpc_decode's integer layer rule, which sees the scale of the LLRs.  alpha is a ValueError
+    then; post is int16, erased counts what the quantiser rounded to zero, and the resolved dict comes back under "quant"."""
     if not isinstance(code, ScLdpcCode):
         raise ValueError(f"ldpc_sc_decode takes an ScLdpcCode, got {code!r}")
     if outer is not None:
         outer = resolve_outer(outer, code)
+    if quant is not None:
+        if alpha is not None:
+            raise ValueError("alpha belongs to the float decoder; the fixed-point one is normalised by quant['num'] and quant['beta']")
+        quant = resolve_quant(quant)
     alpha = 0.75 if alpha is None else alpha
     test = code.ms + 1 if test is None else test
     if llr.shape != bits.shape or llr.dim() not in (3, 4):
@@ -851,15 +859,20 @@ def ldpc_sc_decode(llr, bits, code, window, t0=0, chains=None, iters=10, alpha=N
     P = max(1, code.L + code.ms - int(window) + 1)
     Cn = max(C_, 0)
     out = torch.empty(R, Cn, 6, dtype=torch.int32, device=dev)
-    post = torch.empty(R, Cn, n, dtype=torch.float32, device=dev) if want_post or outer is not None else None
+    post_t = torch.float32 if quant is None else torch.int16
+    post = torch.empty(R, Cn, n, dtype=post_t, device=dev) if want_post or outer is not None else None
     pos_err = torch.empty(R, Cn, code.L, dtype=torch.int32, device=dev) if want_profile else None
     pos_iters = torch.empty(R, Cn, P, dtype=torch.int32, device=dev) if want_profile else None
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_ldpc_sc_decode(R, C_, N, w, int(t0), code.ms, code.mb, code.nb, code.Z, code.L,
-                                                code.components.ctypes.data_as(C.c_void_p), nat.ptr(llr), nat.ptr(bits, torch.int8), int(window),
-                                                int(test), float(alpha), int(iters), nat.ptr(out, torch.int32), nat.ptr(post),
-                                                nat.ptr(pos_err, torch.int32), nat.ptr(pos_iters, torch.int32), nat.current_stream(dev)),
-                  "vaeq_ldpc_sc_decode")
+        head = (R, C_, N, w, int(t0), code.ms, code.mb, code.nb, code.Z, code.L, code.components.ctypes.data_as(C.c_void_p), nat.ptr(llr),
+                nat.ptr(bits, torch.int8), int(window), int(test))
+        tail = (int(iters), nat.ptr(out, torch.int32), nat.ptr(post, post_t), nat.ptr(pos_err, torch.int32), nat.ptr(pos_iters, torch.int32),
+                nat.current_stream(dev))
+        if quant is not None:
+            nat.check(nat.lib().vaeq_ldpc_sc_decode_q(*head, quant["bits"], quant["app_bits"], quant["scale"], quant["num"], quant["beta"], *tail),
+                      "vaeq_ldpc_sc_decode_q")
+        else:
+            nat.check(nat.lib().vaeq_ldpc_sc_decode(*head, float(alpha), *tail), "vaeq_ldpc_sc_decode")
     o = out.long()
     tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)
     ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
@@ -869,6 +882,8 @@ def ldpc_sc_decode(llr, bits, code, window, t0=0, chains=None, iters=10, alpha=N
         ret["post"] = post
     if want_profile:
         ret["pos_err"], ret["pos_iters"] = pos_err.long(), pos_iters.long()
+    if quant is not None:
+        ret["quant"] = quant
     if outer is not None:
         ret["outer"] = bch_outer(post.view(R, Cn * code.L, code.nb * code.Z), bits, outer["code"], code.nb * code.Z, t0=t0, payload=outer["payload"],
                                  spread=outer["spread"], codewords=outer["codewords"])
@@ -963,8 +978,8 @@ def bch_outer(post, bits, code, n, t0=0, depth=None, payload=None, spread=True, 
     return ret
 
 
-FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant", "window", "iters", "test", "outer")
-FEC_BLOCK_ONLY, FEC_SC_ONLY = ("max_iter", "depth", "quant"), ("window", "iters", "test")
+FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant", "window", "iters", "test", "fixed", "outer")
+FEC_BLOCK_ONLY, FEC_SC_ONLY = ("max_iter", "depth", "quant"), ("window", "iters", "test", "fixed")
 
 
 def check_fec(fec):
@@ -978,10 +993,11 @@ def check_fec(fec):
             raise ValueError(f"fec with {'an ScLdpcCode' if sc else 'an LdpcCode'} does not take {', '.join(wrong)}")
         if sc and fec.get("window") is None:
             raise ValueError("fec with an ScLdpcCode needs window, the row-block positions inside the decoding window")
-    if fec is not None and fec.get("quant") is not None:
-        resolve_quant(fec["quant"])
-        if fec.get("alpha") is not None:
-            raise ValueError("fec takes alpha for the float decoder or quant for the fixed-point one, not both")
+    for key in ("quant", "fixed"):                              # the fixed-point rule: quant with an LdpcCode, fixed with an ScLdpcCode
+        if fec is not None and fec.get(key) is not None:
+            resolve_quant(fec[key])
+            if fec.get("alpha") is not None:
+                raise ValueError(f"fec takes alpha for the float decoder or {key} for the fixed-point one, not both")
     if fec is not None and fec.get("outer") is not None:
         resolve_outer(fec["outer"], fec["code"])
 
@@ -998,9 +1014,10 @@ def fec_figures(llr, fec):
     code optional; quant = dict(bits, ...) decodes in fixed point, vaeq_ldpc_decode_q; outer = dict(code=BchCode, ...) adds bch_outer's figures
     under "outer").  With an outer code the runs are walked in chunks whose `post` stays within OUTER_POST_BYTES; codewords are independent, so
     the figures are those of one call.  With an ScLdpcCode under code it is ldpc_sc_decode under fec = dict(code, window, t0, iters, alpha, test,
-    outer; code and window required): max_iter, depth and quant are a ValueError there, as window, iters and test are with an LdpcCode."""
+    fixed, outer; code and window required): max_iter, depth and quant are a ValueError there, as window, iters, test and fixed are with an
+    LdpcCode.  fixed = dict(bits, ...), quant's format, is the window decoder's quant=: fixed point, vaeq_ldpc_sc_decode_q."""
     check_fec(fec)
-    kw = {k: v for k, v in fec.items() if k != "code"}
+    kw = {"quant" if k == "fixed" else k: v for k, v in fec.items() if k != "code"}
     L, B = llr["llr"], llr["bits"]
     decode = ldpc_sc_decode if isinstance(fec["code"], ScLdpcCode) else ldpc_decode
     if fec.get("outer") is None or L.shape[0] == 0:
@@ -1008,7 +1025,7 @@ def fec_figures(llr, fec):
     R, N, n = L.shape[0], L.shape[-1], fec["code"].n
     w = L.numel() // max(R * N, 1)
     C_ = int(kw["codewords"]) if kw.get("codewords") is not None else _ldpc_fit(N, w, n, kw.get("t0", 0), kw.get("depth"))
-    per_run = max(C_, 1) * n * (4 if fec.get("quant") is None else 2)
+    per_run = max(C_, 1) * n * (4 if kw.get("quant") is None else 2)
     step = max(1, int(OUTER_POST_BYTES) // per_run)
     return _cat_figures([decode(L[r:r + step], B[r:r + step], fec["code"], **kw) for r in range(0, R, step)])
 
