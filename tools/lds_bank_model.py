@@ -6,6 +6,7 @@ For a lane -> (group, part) mapping and a part stride it counts, per loop trip, 
 dwords on the same of the 64 banks serialise.  passes(read) = sum over the two half-waves of the maximum bank multiplicity.
 Usage: python tools/lds_bank_model.py [B] [M]
        python tools/lds_bank_model.py dp_d3 | dp_tappair      (the DP wave kernel's D phase / tap-pair tap gradients at the baked B = 100)
+       python tools/lds_bank_model.py dp_fir_carry | dp_du_carry | dp_d3_carry   (its FIR / dL/dU / D loops with the carried cells, against the plain loops)
 """
 import sys
 from collections import defaultdict
@@ -241,7 +242,76 @@ def dp_tappair_model(B=100, M=25):
     return ok
 
 
+def _carry_report(title, plain, carry):
+    """plain / carry: {stage: [worst passes per half-wave of each per-lane read of that stage]} -> (plain, carry) totals per step; prints both."""
+    tp, tc = sum(sum(v) for v in plain.values()), sum(sum(v) for v in carry.values())
+    np_, nc = sum(len(v) for v in plain.values()), sum(len(v) for v in carry.values())
+    wp, wc = max(max(v) for v in plain.values()), max(max(v) for v in carry.values())
+    print(f"DP wave kernel, {title}: per-lane reads per step {np_} -> {nc}, passes per half-wave {tp} -> {tc}, worst read {wp} -> {wc}")
+    return dict(plain_reads=np_, carry_reads=nc, plain_passes=tp, carry_passes=tc, plain_worst=wp, carry_worst=wc)
+
+
+def _pair_cells(bases, B, M, Lph, first):
+    """Per-lane sample reads of the symbol-pair loops (pair_fir, pair_du): lane l < B / 2 reads cells 4 l + 4 g + j, the lanes beyond shadow lane 0.
+    first(g): the j a stage still reads.  -> {(array, stage): [passes]}; the left-over tap's cells are stage G."""
+    G = M // 4
+    lanes = [l if l < B // 2 else 0 for l in range(64)]
+    ph = lambda c: (c & 3) * Lph + (c >> 2)
+    out = {}
+    for ai, base in enumerate(bases):
+        for g in range(G):
+            out[(ai, g)] = [max(half_passes([base + l + ph(4 * g + j) for l in lanes])) for j in first(g)]
+        out[(ai, G)] = [max(half_passes([base + l + ph(c) for l in lanes])) for c in ([4 * G + 2] if first(G) == "carry" else [4 * G, 4 * G + 2])]
+    return out
+
+
+def dp_fir_carry_model(B=100, M=25):
+    """FIR (P1) at the baked B = 100: the sample reads of pair_fir (six per stage and p) against pair_fir_carry's (stage g >= 1 and the left-over tap
+    take cells j = 0, 1 resp. 4G from registers).  Tap reads are one word per wave.    python tools/lds_bank_model.py dp_fir_carry"""
+    Lph = wave_lph(2 * B + M - 1)
+    bases = [p * 4 * Lph for p in range(2)]
+    plain = _pair_cells(bases, B, M, Lph, lambda g: range(6) if g < M // 4 else "plain")
+    carry = _pair_cells(bases, B, M, Lph, lambda g: (range(6) if g == 0 else range(2, 6)) if g < M // 4 else "carry")
+    return _carry_report(f"FIR, B = {B}, M = {M}, Lph = {Lph}", plain, carry)
+
+
+def dp_du_carry_model(B=100, M=25):
+    """dL/dU (P4b) at the baked B = 100: the same on the residual e, both chi.    python tools/lds_bank_model.py dp_du_carry"""
+    Lph = wave_lph(2 * B + M - 1)
+    E = 2 * 4 * Lph
+    bases = [E + c * 4 * Lph for c in range(2)]
+    plain = _pair_cells(bases, B, M, Lph, lambda g: range(6) if g < M // 4 else "plain")
+    carry = _pair_cells(bases, B, M, Lph, lambda g: (range(6) if g == 0 else range(2, 6)) if g < M // 4 else "carry")
+    return _carry_report(f"dL/dU, B = {B}, M = {M}, Lph = {Lph}", plain, carry)
+
+
+def dp_d3_carry_model(B=100, M=25):
+    """D phase (P3) at the baked B = 100, three tau per lane (D3Map): the four mu reads of a tap stage against the carried form's (stage b >= 1 takes
+    d = 1, 2 from registers).    python tools/lds_bank_model.py dp_d3_carry"""
+    mh = M // 2
+    T = B - mh
+    Lph, Uph = wave_lph(2 * B + M - 1), B // 2 + 1
+    U = 2 * 2 * 4 * Lph
+    m3 = [(l & 31) if (l & 31) < (T + 2) // 3 else 0 for l in range(64)]
+    uE = [U + (m & 1) * Uph + ((3 * m) >> 1) for m in m3]
+    uO = [U + ((m & 1) ^ 1) * Uph + ((3 * m) >> 1) + (m & 1) for m in m3]
+    plain, carry = {}, {}
+    for nu in range(2):
+        for b in range((mh + 1) // 2):
+            sl = (mh >> 1) - b
+            reads = [max(half_passes([a + nu * 2 * Uph + o for a in base])) for base, o in ((uO, sl - 1), (uE, sl), (uO, sl), (uE, sl + 1))]
+            plain[(nu, b)] = reads
+            carry[(nu, b)] = reads if b == 0 else reads[:2]
+    return _carry_report(f"D, B = {B}, M = {M}, Uph = {Uph}", plain, carry)
+
+
+DP_CARRY = {"dp_fir_carry": dp_fir_carry_model, "dp_du_carry": dp_du_carry_model, "dp_d3_carry": dp_d3_carry_model}
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] in DP_CARRY:
+        r = DP_CARRY[sys.argv[1]]()
+        sys.exit(0 if r["carry_worst"] <= r["plain_worst"] and r["carry_passes"] <= r["plain_passes"] else 1)
     if len(sys.argv) > 1 and sys.argv[1] == "dp_d3":
         dp_d3_model()
         sys.exit(0)

@@ -17,7 +17,8 @@
 //     lane = (tap, half of the sum range); halves are combined with one cross-half shuffle; the lane that ends up
 //     with a gradient also owns that parameter's Adam moments (LDS rows of their own) and writes the updated tap to LDS.
 //   * every 8-byte LDS read is pinned to one ds_read_b64 (lds2), the tap loops are two-deep software pipelines (pipe2) whose first
-//     term starts the accumulators; streamed rows go through buffer descriptors (scalar row offsets, out-of-range offsets as masks).
+//     term starts the accumulators (at the baked B = 100 their stages also hand the cells they share to one another in registers, pipe2_carry);
+//     streamed rows go through buffer descriptors (scalar row offsets, out-of-range offsets as masks).
 //   * wave sums and prefix scans run on DPP in a fixed order: bitwise reproducible, no LDS round trips.
 //   (DESIGN.md section 5 has the measurements behind each of these.)
 //
@@ -97,6 +98,92 @@ __host__ __device__ inline WaveLayout wave_layout(int B, int M, int NW = 1)
     return l;
 }
 
+// Cells that consecutive stages of the convolution-shaped tap loops share (the baked B = 100, M = 25 kernel carries them in registers instead of
+// reading them again, pipe2_carry).  All indices are relative to the lane's base cell.
+//   FIR, dL/dU: stage g reads the sample cells 4g + j, j = 0..5, at xg[0], xg[Lph], xg[2 Lph], xg[3 Lph], xg[1], xg[Lph + 1] (xg = xp + g, 4-way
+//               polyphase): j = 4, 5 of stage g are j = 0, 1 of stage g + 1, and cell 4G of the tap left over after G stages is j = 4 of stage G - 1.
+//   D (D3Map):  stage b reads the mu cells mh - 2b + d, d = -1..2, at uo[sl - 1], ue[sl], uo[sl], ue[sl + 1] (sl = mh / 2 - b, 2-way polyphase,
+//               mh even): d = -1, 0 of stage b are d = 1, 2 of stage b + 1.
+// (The cells U[3 m + 0..2] of the a = mh term, read ahead of the D loops, are d = -1, 0 of the LAST stage and one cell below; they are consumed first:
+//  keeping two of them to the end of both loops would take registers through the whole phase and a peeled last trip, for 4 of 827 reads.  Left alone.)
+struct CellCarry {
+    static constexpr int fir_off(int g, int j, int Lph) { return g + (j < 4 ? j * Lph : (j - 4) * Lph + 1); }   // what the code adds to xp
+    static constexpr int poly4(int c, int Lph) { return (c & 3) * Lph + (c >> 2); }
+    static constexpr int d3_off(int b, int d, int mh, int Uph) { return (d & 1 ? Uph : 0) + (mh >> 1) - b + (d == -1 ? -1 : d == 2 ? 1 : 0); }   // added to ue
+    static constexpr int poly2(int c, int Uph) { return (c & 1) * Uph + (c >> 1); }
+    // the carried cell is the one the next stage would have read, every offset is the polyphase place of its cell, and no read leaves its array
+    static constexpr bool fir_exact(int B, int M)
+    {
+        const int G = M / 4, len = 2 * B + M - 1, Lph = wave_lph(len);
+        if (M % 4 != 1 || G < 2 || G % 2) return false;                          // one tap left over; pipe2_carry: an even number of stages
+        for (int g = 0; g < G; g++)
+            for (int j = 0; j < 6; j++) {
+                if (fir_off(g, j, Lph) != poly4(4 * g + j, Lph)) return false;
+                if (4 * (B / 2 - 1) + 4 * g + j >= len) return false;               // the last lane with a symbol pair
+                if (g + 1 < G && j >= 4 && fir_off(g, j, Lph) != fir_off(g + 1, j - 4, Lph)) return false;
+            }
+        return poly4(4 * G, Lph) == fir_off(G - 1, 4, Lph) && 4 * (B / 2 - 1) + 4 * G + 2 < len;   // the left-over tap's two cells: 4G (carried), 4G + 2
+    }
+    static constexpr bool d3_exact(int B, int M)
+    {
+        const int mh = M / 2, NB = (mh + 1) / 2, Uph = B / 2 + 1, T = B - mh;
+        if ((mh & 1) || NB < 2 || NB % 2) return false;
+        for (int b = 0; b < NB; b++)
+            for (int d = -1; d <= 2; d++) {
+                // even lane base (3 m even): ue is the even phase; odd base: ue = phase 1, uo = phase 0 one slot up -- the same offsets on swapped rows
+                if (d3_off(b, d, mh, Uph) != poly2(mh - 2 * b + d, Uph)) return false;
+                if (mh - 2 * b + d < 0 || 3 * (D3Map_nm_lanes(T) - 1) + mh - 2 * b + d >= 2 * Uph) return false;
+                if (b + 1 < NB && d <= 0 && d3_off(b, d, mh, Uph) != d3_off(b + 1, d + 2, mh, Uph)) return false;
+            }
+        return true;
+    }
+    static constexpr int D3Map_nm_lanes(int T) { return (T + 2) / 3; }           // D3Map::nm_lanes (defined below; asserted equal there)
+};
+static_assert(CellCarry::fir_exact(100, 25), "B = 100: the FIR / dL/dU stages must carry exactly the cells the next stage would have read, inside x / e");
+static_assert(CellCarry::d3_exact(100, 25), "B = 100: the D stages must carry exactly the mu cells the next stage would have read, inside U");
+
+// pair_fir (below) for the baked B = 100 kernel: the same stages, but stage g >= 1 takes its first two sample cells from the registers of stage g - 1
+// (12 reads per 32 packed FMAs instead of 14) and the left-over tap its first cell from the last stage's.  Every output keeps its terms, their order and
+// its even / odd sub-chains; stage 0 is pair_fir's, statement for statement (it decides which first product is rounded on its own).
+template <int M, bool INIT>
+__device__ __forceinline__ void pair_fir_carry(cacc (&acc)[2][2], cacc (&acc2)[2][2], const float2 *xp, int Lph, const float4 *wq)
+{
+    constexpr int G = M / 4;
+    auto tapA = [&](int k) -> v2f { return lds2(reinterpret_cast<const float2 *>(wq + k)); };
+    auto tapB = [&](int k) -> v2f { return lds2(reinterpret_cast<const float2 *>(wq + k) + 1); };
+    auto taps = [&](int g, v2f (&r)[14]) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) { r[6 + 2 * t] = tapA(4 * g + t); r[7 + 2 * t] = tapB(4 * g + t); }
+    };
+    auto loadF = [&](v2f (&r)[14]) {
+        r[0] = lds2(xp); r[1] = lds2(xp + Lph); r[2] = lds2(xp + 2 * Lph); r[3] = lds2(xp + 3 * Lph); r[4] = lds2(xp + 1); r[5] = lds2(xp + Lph + 1);
+        taps(0, r);
+    };
+    auto loadM = [&](int g, v2f (&r)[14]) { r[2] = lds2(xp + g + 2 * Lph); r[3] = lds2(xp + g + 3 * Lph); taps(g, r); };
+    auto loadL = [&](int g, v2f (&r)[14]) { r[4] = lds2(xp + g + 1); r[5] = lds2(xp + g + Lph + 1); };
+    auto fma0 = [&](const v2f (&r)[14]) {
+        cmacf<INIT>(acc[0][0], r[6], r[0]); cmacf<INIT>(acc[0][1], r[7], r[0]); cmacf<INIT>(acc[1][0], r[6], r[2]); cmacf<INIT>(acc[1][1], r[7], r[2]);
+        cmacf<INIT>(acc2[0][0], r[8], r[1]); cmacf<INIT>(acc2[0][1], r[9], r[1]); cmacf<INIT>(acc2[1][0], r[8], r[3]); cmacf<INIT>(acc2[1][1], r[9], r[3]);
+        cmac(acc[0][0], r[10], r[2]); cmac(acc[0][1], r[11], r[2]); cmac(acc[1][0], r[10], r[4]); cmac(acc[1][1], r[11], r[4]);
+        cmac(acc2[0][0], r[12], r[3]); cmac(acc2[0][1], r[13], r[3]); cmac(acc2[1][0], r[12], r[5]); cmac(acc2[1][1], r[13], r[5]);
+    };
+    auto stage = [&](const v2f (&r)[14], const v2f (&p)[14], auto mid) {          // p[4], p[5]: this stage's cells j = 0, 1
+        cmac(acc[0][0], r[6], p[4]); cmac(acc[0][1], r[7], p[4]); cmac(acc2[0][0], r[8], p[5]); cmac(acc2[0][1], r[9], p[5]);
+        // (volatile: stays in front of the loads into p[4], p[5])
+        asm volatile("" : "+v"(acc[0][0].a), "+v"(acc[0][0].b), "+v"(acc[0][1].a), "+v"(acc[0][1].b), "+v"(acc2[0][0].a), "+v"(acc2[0][0].b),
+                     "+v"(acc2[0][1].a), "+v"(acc2[0][1].b));
+        mid();
+        cmac(acc[1][0], r[6], r[2]); cmac(acc[1][1], r[7], r[2]); cmac(acc2[1][0], r[8], r[3]); cmac(acc2[1][1], r[9], r[3]);
+        cmac(acc[0][0], r[10], r[2]); cmac(acc[0][1], r[11], r[2]); cmac(acc[1][0], r[10], r[4]); cmac(acc[1][1], r[11], r[4]);
+        cmac(acc2[0][0], r[12], r[3]); cmac(acc2[0][1], r[13], r[3]); cmac(acc2[1][0], r[12], r[5]); cmac(acc2[1][1], r[13], r[5]);
+    };
+    constexpr int k = 4 * G;                                                       // the left-over tap (even: into acc)
+    v2f ta, tb, xb;
+    auto pre = [&]() { ta = tapA(k); tb = tapB(k); xb = lds2(xp + ((k + 2) & 3) * Lph + ((k + 2) >> 2)); };
+    auto post = [&](const v2f (&r)[14]) { cmac(acc[0][0], ta, r[4]); cmac(acc[0][1], tb, r[4]); cmac(acc[1][0], ta, xb); cmac(acc[1][1], tb, xb); };
+    pipe2_carry<14>(G, loadF, loadM, loadL, fma0, stage, pre, post);
+}
+
 // y[sym] += sum_k taps[k] * x[4l + 2*sym + k] for the lane's symbol pair, one input polarisation (FIR): T = float4 tap quads
 // (o0.re, o0.im, o1.re, o1.im), acc[sym][o] += w * x.  xp = phase-0 pointer of the lane (slot = lane).
 // A dependent v_pk_fma_f32 can issue only every ~12 cycles (measured: one wave with 8 accumulator chains reaches 64 % of the packed-FMA rate,
@@ -104,9 +191,15 @@ __host__ __device__ inline WaveLayout wave_layout(int B, int M, int NW = 1)
 // independent chains: here the even taps accumulate into acc, the odd taps into acc2 (the caller adds them once at the end).
 // INIT: the first taps start the accumulators (no zeroing); else they are added to.
 // SPLIT = false (shapes not baked into the kernel, where run-time strides already cost registers): all taps into acc, acc2 untouched.
-template <int M, bool INIT, bool PIPE = true, bool SPLIT = true>
+// CARRY (the baked B = 100 kernel): the sample cells a stage shares with the one before stay in registers, see CellCarry and pair_fir_carry.
+template <int M, bool INIT, bool PIPE = true, bool SPLIT = true, bool CARRY = false>
 __device__ __forceinline__ void pair_fir(cacc (&acc)[2][2], cacc (&accx)[2][2], const float2 *xp, int Lph, const float4 *wq)
 {
+    if constexpr (CARRY) {
+        static_assert(PIPE && SPLIT, "the carried form is the pipelined, split one");
+        pair_fir_carry<M, INIT>(acc, accx, xp, Lph, wq);
+        return;
+    }
     cacc (&acc2)[2][2] = SPLIT ? accx : acc;
     auto tapA = [&](int k) -> v2f { return lds2(reinterpret_cast<const float2 *>(wq + k)); };       // (re, im) of o = 0
     auto tapB = [&](int k) -> v2f { return lds2(reinterpret_cast<const float2 *>(wq + k) + 1); };   // (re, im) of o = 1
@@ -139,7 +232,7 @@ __device__ __forceinline__ void pair_fir(cacc (&acc)[2][2], cacc (&accx)[2][2], 
 // dL/dU for the lane's symbol pair: the FIR's shape on the residual e with conjugated channel taps, acc[chi][sym][nu] += e[chi] * conj(h[chi][nu]),
 // BOTH chi in one loop (16 independent accumulator chains, see pair_fir).  ep = phase-0 pointer of the lane into e[chi = 0] (chi = 1: + 4 Lph);
 // ht[chi * 2 + nu] = the tap rows (float2, MP apart).  Runs at the kernel's register peak (the demapper's moments are live): one operand set.
-template <int M, bool MERGE = true>
+template <int M, bool MERGE = true, bool CARRY = false>
 __device__ __forceinline__ void pair_du(cacc (&acc)[2][2][2], const float2 *ep, int Lph, const float2 *ht, int MP)
 {
     constexpr int G = M / 4;
@@ -155,7 +248,62 @@ __device__ __forceinline__ void pair_du(cacc (&acc)[2][2][2], const float2 *ep, 
         cmacf<F>(acc[chi][0][0], x[6 + 2 * t], x[t]); cmacf<F>(acc[chi][0][1], x[7 + 2 * t], x[t]);
         cmacf<F>(acc[chi][1][0], x[6 + 2 * t], x[t + 2]); cmacf<F>(acc[chi][1][1], x[7 + 2 * t], x[t + 2]);
     };
-    if constexpr (MERGE) {                             // both chi per stage: 28 reads feeding 64 FMAs on 16 chains
+    if constexpr (CARRY) {
+        // the merged form for the baked B = 100 kernel: stage g >= 1 takes the sample cells j = 0, 1 of both chi from the registers of stage g - 1 (CellCarry:
+        // 24 reads per 64 packed FMAs instead of 28), the left-over tap its first cell from the last stage's.  Every chain keeps its terms and their order
+        // (tap 4g .. 4g + 3); stage 0 is the plain one, statement for statement.  Per chi -- the carry restarts where the array changes
+        static_assert(MERGE && M % 4 == 1, "the carried form is the merged one, with one tap left over");
+        auto loadF = [&](v2f (&r)[28]) { load1(0, 0, r); load1(1, 0, r + 14); };
+        auto loadM = [&](int g, v2f (&r)[28]) {
+#pragma unroll
+            for (int chi = 0; chi < 2; chi++) {
+                const float2 *xg = ep + chi * 4 * Lph + g;
+                v2f *x = r + 14 * chi;
+                x[2] = lds2(xg + 2 * Lph); x[3] = lds2(xg + 3 * Lph);
+#pragma unroll
+                for (int t = 0; t < 4; t++) { x[6 + 2 * t] = lds2(ht + (chi * 2 + 0) * MP + 4 * g + t); x[7 + 2 * t] = lds2(ht + (chi * 2 + 1) * MP + 4 * g + t); }
+            }
+        };
+        auto loadL = [&](int g, v2f (&r)[28]) {
+#pragma unroll
+            for (int chi = 0; chi < 2; chi++) { r[14 * chi + 4] = lds2(ep + chi * 4 * Lph + g + 1); r[14 * chi + 5] = lds2(ep + chi * 4 * Lph + g + Lph + 1); }
+        };
+        auto fma0 = [&](const v2f (&r)[28]) {
+            fma1(0, r, 0, std::true_type{}); fma1(1, r + 14, 0, std::true_type{});
+#pragma unroll
+            for (int t = 1; t < 4; t++) { fma1(0, r, t, std::false_type{}); fma1(1, r + 14, t, std::false_type{}); }
+        };
+        auto stage = [&](const v2f (&r)[28], const v2f (&p)[28], auto) {           // p[14 chi + 4], p[14 chi + 5]: this stage's cells j = 0, 1
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+#pragma unroll
+                for (int chi = 0; chi < 2; chi++) {
+                    const v2f *x = r + 14 * chi;
+                    cmac(acc[chi][0][0], x[6 + 2 * t], p[14 * chi + 4 + t]); cmac(acc[chi][0][1], x[7 + 2 * t], p[14 * chi + 4 + t]);
+                    cmac(acc[chi][1][0], x[6 + 2 * t], x[t + 2]); cmac(acc[chi][1][1], x[7 + 2 * t], x[t + 2]);
+                }
+#pragma unroll
+            for (int t = 2; t < 4; t++) { fma1(0, r, t, std::false_type{}); fma1(1, r + 14, t, std::false_type{}); }
+        };
+        constexpr int k = 4 * G;                                                   // the left-over tap
+        v2f ta[2], tb[2], xb[2];
+        auto pre = [&]() {
+#pragma unroll
+            for (int chi = 0; chi < 2; chi++) {
+                ta[chi] = lds2(ht + (chi * 2 + 0) * MP + k); tb[chi] = lds2(ht + (chi * 2 + 1) * MP + k);
+                xb[chi] = lds2(ep + chi * 4 * Lph + ((k + 2) & 3) * Lph + ((k + 2) >> 2));
+            }
+        };
+        auto post = [&](const v2f (&r)[28]) {
+#pragma unroll
+            for (int chi = 0; chi < 2; chi++) {
+                cmac(acc[chi][0][0], ta[chi], r[14 * chi + 4]); cmac(acc[chi][0][1], tb[chi], r[14 * chi + 4]);
+                cmac(acc[chi][1][0], ta[chi], xb[chi]); cmac(acc[chi][1][1], tb[chi], xb[chi]);
+            }
+        };
+        pipe2_carry<28, false>(G, loadF, loadM, loadL, fma0, stage, pre, post);
+        return;
+    } else if constexpr (MERGE) {                      // both chi per stage: 28 reads feeding 64 FMAs on 16 chains
         auto load = [&](int g, v2f (&r)[28]) { load1(0, g, r); load1(1, g, r + 14); };
         auto fma = [&](int, const v2f (&r)[28], auto first) {
             fma1(0, r, 0, first); fma1(1, r + 14, 0, first);
@@ -414,7 +562,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     constexpr bool PIPE = VAEQ_PIPE && FIXL;               // run-time layouts keep more addresses live: there one operand set,
     constexpr bool WIDE = FIXL;                            // ... 8 accumulator chains and one chi at a time in dL/dU (fits the register file)
     // B100: the baked B = 100 kernel on one wave, the shape that is measured step by step and whose bits are pinned (tests/test_dp_wave_bits_gpu.py).
-    // It alone takes five forms; every other instantiation keeps the plain one, instruction for instruction:
+    // It alone takes six forms; every other instantiation keeps the plain one, instruction for instruction:
     //  * the halves of the two tap gradients meet on v_permlane32_swap (half_sum: one swap + one add per kept value) instead of 16 ds_bpermute_b32
     //    through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms (profiles/r04/kernel_variants_ab.txt)
     //  * the next window's prefetch is issued without a branch around it (the launch's very last step fetches with every lane out of range: zeros, no
@@ -430,7 +578,11 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     //    and takes the second tap's operands from the registers of the first: 12 instead of 16 per-lane LDS reads per 32 packed FMAs, every output's
     //    chain in its old order; the lane that ends up with a tap's sum owns the tap and its Adam moments
     //    (profiles/r07/tapgrad_lds_bound.txt, profiles/r07/kernel_variants_ab.txt)
+    //  * (M = 25) the FIR, dL/dU and the D convolution carry the cells that consecutive stages share in registers (CellCarry, pipe2_carry): 12 instead of
+    //    14, 24 instead of 28 and 6 instead of 8 per-lane LDS reads per stage, every output's chain in its old order
+    //    (profiles/r08/cell_carry_bound.txt, profiles/r08/kernel_variants_ab.txt)
     constexpr bool B100 = BT == 100 && NW == 1;
+    constexpr bool CARRY = B100 && M == 25 && PIPE && WIDE;
     constexpr int QAUX = B100 ? 2 : 0;                         // cache policy of the q stores
     const int B = BT ? BT : a.B;
     const int BS = BT ? BT : BL ? BL : B;                      // the minibatch length the LDS layout (offsets, row strides) is made for
@@ -583,8 +735,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             float2 y[2][2];                                    // [sym][o]
             {
                 cacc ya[2][2], yb[2][2];                       // lanes without a symbol pair recompute lane 0's (Xa): no divergence, nothing to zero
-                pair_fir<M, true, PIPE, WIDE>(ya, yb, Xa, Lph, Wt);
-                pair_fir<M, false, PIPE, WIDE>(ya, yb, Xa + 4 * Lph, Lph, Wt + M);
+                pair_fir<M, true, PIPE, WIDE, CARRY>(ya, yb, Xa, Lph, Wt);   // (CARRY: per p -- the carry restarts where the array changes)
+                pair_fir<M, false, PIPE, WIDE, CARRY>(ya, yb, Xa + 4 * Lph, Lph, Wt + M);
 #pragma unroll
                 for (int sy = 0; sy < 2; sy++)
 #pragma unroll
@@ -769,8 +921,10 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 // change at most the sign of a D that is zero -- and x - (+-0) = x for every received sample x other than -0 (all pinned bits equal).
                 constexpr int T = 100 - mh, NB = (mh + 1) / 2;
                 static_assert((mh & 1) == 0 && (Mh & 3) == 0 && D3Map::exact(100, M), "D3Map: mh even (a = mh stands alone, its odd tap is the pad)");
-                int l3 = lane;                                 // the per-lane pointers are derived once per STEP: hoisted out of the step loop they
-                asm volatile("" : "+v"(l3));                   // would be ten more registers live through every phase, the register peak included
+                // the per-lane pointers below depend on the lane alone: nothing pins them inside the step, so they are derived once, ahead of the frame
+                // loop (about ten registers live through every phase -- since the tap loops carry their shared cells the register peak has room for
+                // them: 252 VGPRs in the bench kernel, 256 at most over the 18 baked kernels, no scratch; profiles/r08/kernel_variants_ab.txt)
+                const int l3 = lane;
                 const int m3 = D3Map::m(l3, T), modd = m3 & 1, m3h = (3 * m3) >> 1;
                 cacc D3[3][2];                                 // [i][par]: D[chi, 2 (3 m + i) + par]
                 // the lane's six cells are the consecutive samples c = Mh + 6 m + k of its chi; 6 m = 2 (mod 4) for odd m: two pointer cases.
@@ -824,7 +978,33 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
 #pragma unroll
                             for (int i = 0; i < 3; i++) { cmac(D3[i][0], t2, r[i]); cmac(D3[i][1], t3, r[i]); }
                         };
-                        if (v == 0) pipe2<8, true, PIPE>(NB, load, fma);
+                        if constexpr (CARRY) {
+                            // stage b >= 1 takes its cells d = 1, 2 from the registers of stage b - 1 (its d = -1, 0): 6 reads per 24 packed FMAs.  Stage 0
+                            // is the plain one, statement for statement; per nu -- the carry restarts where the array changes
+                            static_assert(CellCarry::d3_exact(100, M) && CellCarry::D3Map_nm_lanes(T) == D3Map::nm_lanes(T), "CellCarry");
+                            auto loadF = [&](v2f (&r)[8]) { load(0, r); };
+                            auto loadM = [&](int b, v2f (&r)[8]) {
+#pragma unroll
+                                for (int t = 0; t < 4; t++) r[4 + t] = lds2(hv + 4 * b + t);
+                            };
+                            auto loadL = [&](int b, v2f (&r)[8]) { const int sl = (mh >> 1) - b; r[0] = lds2(uo + sl - 1); r[1] = lds2(ue + sl); };
+                            auto stage = [&](const v2f (&r)[8], const v2f (&p)[8], auto mid) {   // p[0], p[1]: this stage's cells d = 1, 2
+                                v2f t0 = r[4], t1 = r[5], t2 = r[6], t3 = r[7];
+                                asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));     // pin: see fma
+                                cmac(D3[2][0], t0, p[1]); cmac(D3[2][1], t1, p[1]); cmac(D3[1][0], t0, p[0]); cmac(D3[1][1], t1, p[0]);
+                                cmac(D3[2][0], t2, p[0]); cmac(D3[2][1], t3, p[0]);
+                                // (volatile: stays in front of the loads into p[0], p[1])
+                                asm volatile("" : "+v"(D3[1][0].a), "+v"(D3[1][0].b), "+v"(D3[1][1].a), "+v"(D3[1][1].b), "+v"(D3[2][0].a), "+v"(D3[2][0].b),
+                                             "+v"(D3[2][1].a), "+v"(D3[2][1].b));
+                                mid();
+                                cmac(D3[0][0], t0, r[1]); cmac(D3[0][1], t1, r[1]); cmac(D3[1][0], t2, r[1]); cmac(D3[1][1], t3, r[1]);
+                                cmac(D3[0][0], t2, r[0]); cmac(D3[0][1], t3, r[0]);
+                            };
+                            auto none = [&]() {};
+                            auto done = [&](const v2f (&)[8]) {};
+                            if (v == 0) pipe2_carry<8>(NB, loadF, loadM, loadL, [&](const v2f (&r)[8]) { fma(0, r, std::true_type{}); }, stage, none, done);
+                            else pipe2_carry<8>(NB, loadF, loadM, loadL, [&](const v2f (&r)[8]) { fma(0, r, std::false_type{}); }, stage, none, done);
+                        } else if (v == 0) pipe2<8, true, PIPE>(NB, load, fma);
                         else pipe2<8, false, PIPE>(NB, load, fma);
                     }
                 }
@@ -981,10 +1161,9 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 cacc ca[2][2];
                 if constexpr (TP) {
                     // tap pairs (TapPairMap): ca[tap of the pair][nu] of the lane's chi over its half of the tau range; read tap a = 2 slot (mh even: its U
-                    // cells tau + mh - a of even tau are the even phase), the other tap a + 1 from registers.  The pointers are derived once per STEP (see P3)
+                    // cells tau + mh - a of even tau are the even phase), the other tap a + 1 from registers.  The pointers are derived once, ahead of the frame loop (see P3)
                     static_assert(TapPairMap::exact(100, M) && UNI, "TapPairMap");
-                    int lt = lane;
-                    asm volatile("" : "+v"(lt));
+                    const int lt = lane;
                     constexpr int NH = TapPairMap::dh_pairs(100, M);
                     const int par = TapPairMap::par(lt, M), sl = TapPairMap::alo(lt, M) >> 1, ma = TapPairMap::part_h(lt, M) * NH;
                     const int ceA = par + Mh, ceB = par + Mh + 2;
@@ -1112,7 +1291,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 float2 au0[2][2], au1[2][2];                   // chi = 0 / 1: [sym][nu]
                 {
                     cacc cu[2][2][2];                          // [chi][sym][nu]
-                    pair_du<M, WIDE>(cu, Ea, Lph, Ht, MP);
+                    pair_du<M, WIDE, CARRY>(cu, Ea, Lph, Ht, MP);
 #pragma unroll
                     for (int sy = 0; sy < 2; sy++)
 #pragma unroll
@@ -1189,8 +1368,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 if constexpr (TP) {
                     // tap pairs (TapPairMap): read tap k + 2 = 2 (a + 1) + par, the pair's lower tap k from registers; ca[o-half order][p]: [0] = the lower
                     // tap, which the lower half keeps
-                    int lt = lane;
-                    asm volatile("" : "+v"(lt));
+                    const int lt = lane;
                     constexpr int NQ = TapPairMap::dw_pairs(100);
                     const int cA = TapPairMap::tap(lt, M, 1), cB = cA + 2, ma = TapPairMap::part_w(lt) * NQ;
                     const float2 *gA = GY + TapPairMap::c(lt, M) * BS + 2 * ma;

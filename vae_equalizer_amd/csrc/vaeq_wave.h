@@ -162,6 +162,53 @@ __device__ __forceinline__ void pipe2(int n, L load, F fma)
     if (i < n) fma(i, B, std::false_type{});
 }
 
+// pipe2 for loops whose stage i + 1 consumes operands that stage i already holds (the carried cells): those stay where stage i's loads put them, in
+// the OTHER register set, and are read there.  n >= 2 stages, n even.  loadF(r): every operand of stage 0;  loadM(i, r): the operands of stage i that
+// are neither carried in nor carried on;  loadL(i, r): the cells stage i carries on to stage i + 1 (they overwrite the ones stage i - 1 carried on, in
+// the same set);  fma0(r): stage 0;  stage(r, p, mid): stage i >= 1 with its own operands in r and the carried ones in p -- it consumes everything it
+// needs of p FIRST, then calls mid() (the loadL into p), then does the rest: no operand is copied on the back edge.  pre() runs ahead of the last
+// stage's FMAs (reads of what follows the loop), and the last stage's set is handed to post(r).  No load runs past stage n - 1.
+// PIPE = false: load, compute, load, compute ... as in pipe2 (one stage's operands live at a time, plus the carried cells); pre() runs behind the last stage.
+template <int NR, bool PIPE = true, class LF, class LM, class LL, class F0, class S, class PRE, class POST>
+__device__ __forceinline__ void pipe2_carry(int n, LF loadF, LM loadM, LL loadL, F0 fma0, S stage, PRE pre, POST post)
+{
+    v2f A[NR], B[NR];
+    loadF(A);
+    if constexpr (!PIPE) {
+        fma0(A);
+        int i = 1;
+#pragma unroll 1
+        for (; i + 1 < n; i += 2) {
+            loadM(i, B);
+            loadL(i, B);
+            stage(B, A, []() {});
+            loadM(i + 1, A);
+            loadL(i + 1, A);
+            stage(A, B, []() {});
+        }
+        loadM(i, B);
+        loadL(i, B);
+        stage(B, A, []() {});
+        pre();
+        post(B);
+        return;
+    }
+    loadM(1, B);
+    loadL(1, B);
+    fma0(A);
+    int i = 1;
+#pragma unroll 1
+    for (; i + 1 < n; i += 2) {                        // B holds stage i, A what stage i - 1 carried on
+        loadM(i + 1, A);
+        stage(B, A, [&]() { loadL(i + 1, A); });
+        loadM(i + 2, B);
+        stage(A, B, [&]() { loadL(i + 2, B); });
+    }
+    pre();
+    stage(B, A, []() {});
+    post(B);
+}
+
 // Final combine of the two packed partial sums, ONE v_pk_add_f32 each: the swap of b's halves and the sign ride on op_sel / neg (the backend
 // does not find this form: it shuffles the halves with v_mov and adds them as scalars).
 __device__ __forceinline__ v2f cfin2(const cacc &c)                                    // sum t * v = (a.x - b.y, a.y + b.x)
