@@ -826,6 +826,52 @@ int64_t vaeq_ldpc_sc_q_lds_bytes(int32_t ms, int32_t mb, int32_t nb, int32_t Z, 
 int vaeq_bch_outer(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t n, int32_t K, int32_t m, int32_t t, int32_t n_o,
                    int32_t C_o, int32_t spread, const void *post, int32_t post_i16, const int8_t *bits, int32_t *out, int16_t *loc, void *stream);
 
+/* Hard-decision FEC: a staircase code over BCH components with a sliding-window iterative decoder, for the figure a coherent-optics comparison
+ * quotes beside the soft-decision one -- whether the link is error-free behind a hard-decision FEC at a given pre-FEC BER (no reference
+ * counterpart).  No encoder: every component code is linear and bounded-distance decoding depends on the error pattern alone, so the whole
+ * iterative decoder, miscorrections included, acts on e = received xor transmitted exactly as it would on a transmitted codeword.
+ * The component code: vaeq_bch_outer's narrow-sense primitive binary BCH code over GF(2^m) -- the same polynomials, position p belongs to
+ * alpha^p -- with designed correction t, shortened to 2 s bits; parity(m, t) as there, and parity(m, t) < 2 s <= 2^m - 1.
+ * The chain: L transmitted blocks B_1 .. B_L of s x s bits; B_0 is not transmitted, it is all zero and is never flipped.  n_chain = L s^2.  The
+ * tensors llr[R][w][N] / bits[R][w][N] and the bit-packed map are vaeq_ldpc_decode's: C chains per run, bit (a, b) of block i of chain c is
+ * global bit g = c n_chain + (i - 1) s^2 + a s + b at symbol t0 + g / w, plane g % w, and t0 w + C n_chain <= N w.  The received bit is
+ * llr < 0: a NaN and +-0 are bit 0, as in the decoders.
+ *   components pair i (1 .. L) has the components j = 0 .. s - 1, each the word [column j of B_(i-1) | row j of B_i]: position p < s is bit (p, j)
+ *              of block i - 1, position s + p' is bit (j, p') of block i.
+ *   rule       a component is decided by vaeq_bch_outer's rule with n_o = 2 s on its part of e: status 0, nothing flipped; status 1, the unique
+ *              set of at most t positions with the component's syndromes is flipped; status 2, nothing flipped.  One addition: in pair 1 a set
+ *              that contains a position below s is status 2 -- B_0 holds nothing to flip, and without this rule a miscorrection writes errors
+ *              into a block that does not exist.
+ *   positions  q = 0 .. P - 1, P = max(1, L - W + 1).  The active pairs at q are i = q + 1 .. min(q + W, L).
+ *   iteration  the active pairs in ascending i.  In a pair step every component is decided on the state before the step, then all flips are
+ *              applied (a pair's components own disjoint bits: this equals any sequential order).  A position ends after an iteration that
+ *              flips nothing, which is counted, or after `iters` iterations.
+ *   between    nothing is reset.  Block i is final once position min(i, P - 1) has ended.
+ * out[R][C][8] int32, the first six in vaeq_ldpc_sc_decode's layout: iters (the sum over the positions), ok (1 iff at every position the last
+ * executed iteration had every active component at status 0), post_err (errors after decoding, over n_chain), pre_err (errors before), erased
+ * (inputs equal to +-0), iters_max (the most iterations at any one position), nflip (all flips), bad_flips (flips of a bit whose error bit was
+ * 0 at that moment: what miscorrection costs).  Nullable: hard[R][C][n_chain] int8, the final decisions (the TX bit xor the final error bit);
+ * pos_err[R][C][L] int32, the errors of blocks 1 .. L in their final state; pos_iters[R][C][P] int32.
+ * The last block is protected by one component per bit, not by two like every other: it keeps more errors than the steady state of the chain,
+ * and a short chain's post_err is mostly its tail.  pos_err is how a user reads the steady state: the blocks before the last.
+ * One workgroup per chain, one lane per component of the pair in flight.  The state in LDS is vaeq_staircase_lds_bytes(m, s, W) = 4 2^m (the
+ * exp and log tables of GF(2^m), uint16) + 8 (W + 1) s ceil(s / 32) (the error pattern of the window's W + 1 blocks as bitmaps, each block
+ * row-major and transposed, a row in whole 32-bit words), at most 64 KiB; VAEQ_ERR_SHAPE from that call for m outside 4 .. 10, s outside
+ * 2 .. 511, 2 s > 2^m - 1 or W outside 1 .. 32.  That figure and its bound are the state a caller sizes, the kernel's dynamic LDS; the kernel
+ * keeps a few hundred bytes of counters in static LDS besides (416 as built: profiles/staircase/scan_isa.txt), so the largest accepted
+ * shape holds 65 936 bytes per workgroup, of the 160 KiB of a gfx950 CU.  Integers and a fixed order: two calls give identical bits.
+ * The counts are 32 bits wide while the envelope admits a chain of more than 2^31 bits (L s^2 reaches 1.7e10): post_err, pre_err, erased and
+ * pos_err are exact for n_chain < 2^31, nflip and bad_flips while the flips stay below 2^31, and past that each is the count modulo 2^32.
+ * Refusals, all before any HIP call and in vaeq_ldpc_sc_decode's order: R == 0 is VAEQ_OK (its pointers may be NULL); a NULL llr, bits or out is
+ * VAEQ_ERR_NULL, before any shape rule; then VAEQ_ERR_SHAPE for the tensor rules of the LDPC calls (R < 0, C < 1, N < 1, N > 0x3fffffff, w
+ * outside 1 .. 64, t0 < 0, t0 > N), iters outside 1 .. 100, m outside 4 .. 10, t outside 1 .. 8, s outside 2 .. 511, 2 s > 2^m - 1,
+ * parity(m, t) >= 2 s, L outside 1 .. 65535, W outside 1 .. 32; then for a state above 64 KiB, t0 w + C n_chain > N w (decided
+ * without forming C n_chain, which passes 2^63 inside the envelope) and R C > 0x7fffffff. */
+int vaeq_staircase_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t m, int32_t t, int32_t s, int32_t L,
+                          const float *llr, const int8_t *bits, int32_t W, int32_t iters,
+                          int32_t *out, int8_t *hard, int32_t *pos_err, int32_t *pos_iters, void *stream);
+int64_t vaeq_staircase_lds_bytes(int32_t m, int32_t s, int32_t W);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

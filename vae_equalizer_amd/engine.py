@@ -978,12 +978,84 @@ def bch_outer(post, bits, code, n, t0=0, depth=None, payload=None, spread=True, 
     return ret
 
 
+class StaircaseCode:
+    """A staircase code for staircase_decode: a chain of L blocks of s x s bits over the BchCode `component`, whose even length is 2 s.  Component
+    j of pair i is the word [column j of block i - 1 | row j of block i]; block 0 is all zero and is not transmitted.  .component, .L, .s = n // 2,
+    .n = L s^2 bits (n_chain), .rate = 1 - parity / s.  A rate of zero or below is allowed: that is a decoder test, not a code.  ValueError
+    outside vaeq_staircase_decode's envelope: m in 4 .. 10, t in 1 .. 8, s in 2 .. 511, L in 1 .. 65535."""
+
+    def __init__(self, component, L):
+        import numbers
+        if not isinstance(component, BchCode):
+            raise ValueError(f"StaircaseCode takes a BchCode as its component, got {component!r}")
+        if not isinstance(L, numbers.Integral) or isinstance(L, bool) or not 1 <= int(L) <= 65535:
+            raise ValueError(f"StaircaseCode: a chain of 1 .. 65535 blocks, got L={L!r}")
+        if component.n % 2 or not 4 <= component.m <= 10 or not 1 <= component.t <= 8 or not 2 <= component.n // 2 <= 511:
+            raise ValueError(f"StaircaseCode: a component with m in 4 .. 10, t in 1 .. 8 and an even n = 2 s, s in 2 .. 511; got m={component.m}, "
+                             f"t={component.t}, n={component.n}")
+        self.component, self.L, self.s = component, int(L), component.n // 2
+        self.n = self.L * self.s * self.s
+        self.rate = 1.0 - component.parity / self.s
+
+
+def staircase_decode(llr, bits, code, window, t0=0, chains=None, iters=8, want_hard=False, want_profile=False):
+    """Post-FEC figures of per-bit LLRs behind a hard-decision staircase code on the device (vaeq_staircase_decode): the hard decisions llr < 0
+    against the TX bits give the error pattern of every chain of the StaircaseCode `code`; a window of `window` pairs of neighbouring blocks
+    slides along the chain, and at each of the P = max(1, L - window + 1) positions the pairs inside are decoded component by component, at most
+    `iters` times, until an iteration flips nothing.  llr, bits, t0 and the bit map as for ldpc_decode with n = code.n; chains: per run, default
+    the most that fit behind t0.  No encoder: the figures depend on the error pattern alone.
+    -> ldpc_sc_decode's dict, a chain where it has one (iters [R,C]: the sum over the positions; ok: at every position the last iteration found
+    every component clean; bit_err, pre_err, erased, iters_max [R,C] int64; positions (P); BER_post[R], BER_pre[R], FER[R] f32), plus nflip and
+    bad_flips [R,C] (all flips, and those of a bit that was right at that moment: what miscorrection costs).  want_hard: hard[R,C,n] int8, the
+    final decisions.  want_profile: pos_err [R,C,L] (the errors of each block in its final state; the last block has one component per bit and
+    keeps more than the steady state) and pos_iters [R,C,P]."""
+    if not isinstance(code, StaircaseCode):
+        raise ValueError(f"staircase_decode takes a StaircaseCode, got {code!r}")
+    if llr.shape != bits.shape or llr.dim() not in (3, 4):
+        raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
+    dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
+    llr = llr.reshape(R, -1, N).contiguous()
+    bits = bits.reshape(R, -1, N).contiguous()
+    w, n = llr.shape[1], code.n
+    C_ = int(chains) if chains is not None else _ldpc_fit(N, w, n, t0, None)
+    if chains is None and C_ < 1:
+        raise ValueError(f"no chain of {n} bits fits into {N - int(t0)} symbols of {w} bits")
+    P = max(1, code.L - int(window) + 1)
+    Cn = max(C_, 0)
+    out = torch.empty(R, Cn, 8, dtype=torch.int32, device=dev)
+    hard = torch.empty(R, Cn, n, dtype=torch.int8, device=dev) if want_hard else None
+    pos_err = torch.empty(R, Cn, code.L, dtype=torch.int32, device=dev) if want_profile else None
+    pos_iters = torch.empty(R, Cn, P, dtype=torch.int32, device=dev) if want_profile else None
+    bch = code.component
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_staircase_decode(R, C_, N, w, int(t0), bch.m, bch.t, code.s, code.L, nat.ptr(llr), nat.ptr(bits, torch.int8),
+                                                  int(window), int(iters), nat.ptr(out, torch.int32), nat.ptr(hard, torch.int8),
+                                                  nat.ptr(pos_err, torch.int32), nat.ptr(pos_iters, torch.int32), nat.current_stream(dev)),
+                  "vaeq_staircase_decode")
+    o = out.long()
+    tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)
+    ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
+               BER_post=(o[..., 2].sum(1).double() / tot).float(), BER_pre=(o[..., 3].sum(1).double() / tot).float(),
+               FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float(), iters_max=o[..., 5], positions=P,
+               nflip=o[..., 6], bad_flips=o[..., 7])
+    if want_hard:
+        ret["hard"] = hard
+    if want_profile:
+        ret["pos_err"], ret["pos_iters"] = pos_err.long(), pos_iters.long()
+    return ret
+
+
 FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant", "window", "iters", "test", "fixed", "outer")
 FEC_BLOCK_ONLY, FEC_SC_ONLY = ("max_iter", "depth", "quant"), ("window", "iters", "test", "fixed")
+FEC_STAIRCASE_KEYS = ("code", "window", "t0", "iters")
 
 
 def check_fec(fec):
     """ValueError for a fec= dict that fec_figures would refuse (None passes): for a runner to call before it allocates or launches anything."""
+    if isinstance(fec, dict) and isinstance(fec.get("code"), StaircaseCode):
+        if set(fec) - set(FEC_STAIRCASE_KEYS) or fec.get("window") is None:
+            raise ValueError(f"fec with a StaircaseCode takes {', '.join(FEC_STAIRCASE_KEYS)}, window required; got {sorted(fec)}")
+        return
     if fec is not None and (set(fec) - set(FEC_KEYS) or "code" not in fec):
         raise ValueError(f"fec takes {', '.join(FEC_KEYS)}; got {sorted(fec)}")
     if fec is not None:
@@ -1015,8 +1087,12 @@ def fec_figures(llr, fec):
     under "outer").  With an outer code the runs are walked in chunks whose `post` stays within OUTER_POST_BYTES; codewords are independent, so
     the figures are those of one call.  With an ScLdpcCode under code it is ldpc_sc_decode under fec = dict(code, window, t0, iters, alpha, test,
     fixed, outer; code and window required): max_iter, depth and quant are a ValueError there, as window, iters, test and fixed are with an
-    LdpcCode.  fixed = dict(bits, ...), quant's format, is the window decoder's quant=: fixed point, vaeq_ldpc_sc_decode_q."""
+    LdpcCode.  fixed = dict(bits, ...), quant's format, is the window decoder's quant=: fixed point, vaeq_ldpc_sc_decode_q.  With a StaircaseCode
+    under code it is staircase_decode, hard-decision FEC, under fec = dict(code, window, t0, iters; code and window required); every other key
+    is a ValueError there."""
     check_fec(fec)
+    if isinstance(fec["code"], StaircaseCode):
+        return staircase_decode(llr["llr"], llr["bits"], **fec)
     kw = {"quant" if k == "fixed" else k: v for k, v in fec.items() if k != "code"}
     L, B = llr["llr"], llr["bits"]
     decode = ldpc_sc_decode if isinstance(fec["code"], ScLdpcCode) else ldpc_decode
