@@ -872,6 +872,45 @@ int vaeq_staircase_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0
                           int32_t *out, int8_t *hard, int32_t *pos_err, int32_t *pos_iters, void *stream);
 int64_t vaeq_staircase_lds_bytes(int32_t m, int32_t s, int32_t W);
 
+/* The inner code in front of the hard-decision FEC: a soft-in / hard-out Chase decoder of a short single-error-correcting code over the demappers'
+ * LLRs, as a concatenated scheme such as 400ZR's places a Hamming-type word in front of its staircase code (no reference counterpart).  No encoder:
+ * the code is linear and the rule symmetric, so it acts on e = received xor transmitted exactly as it would on a transmitted codeword.
+ * The code: cols_host[n] int32 in HOST memory, column j of the parity-check matrix as an r-bit integer; n in 3 .. 256, r in 2 .. 10, the columns
+ * distinct, non-zero and below 2^r -- any such matrix corrects one error.  A Hamming code is cols[j] = j + 1, the extended Hamming code with d = 4
+ * is cols[j] = (j << 1) | 1, either one shortened to its first n columns.  The table is validated on every call and travels to the kernel by value.
+ * The tensors llr[R][w][N] / bits[R][w][N] and the bit map are vaeq_ldpc_decode's with this n, C codewords per run: depth == 0 its bit-packed map
+ * and fit rule, depth >= 1 vaeq_ldpc_decode_il's symbol interleaver with its fit rule and its unused planes.
+ * The rule for one codeword, in integers and float32 so that a numpy model reproduces every bit:
+ *   input      x_j = the LLR of bit j, a NaN mapped to +0;  y_j = (x_j < 0): +-0 is bit 0;  a_j = |x_j| in float32, +inf allowed;
+ *              e_j = y_j xor bit_j;  s0 = xor over the j with e_j = 1 of cols[j].
+ *   positions  the n positions ordered by (a_j, j) ascending; l_0 .. l_(p-1) are the first p, the least reliable; p in 0 .. min(6, n).
+ *   patterns   T = 0 .. 2^p - 1:  F_T = { l_i : bit i of T };  s_T = s0 xor (xor over F_T of cols).  s_T == 0: the candidate of T flips F_T.
+ *              s_T == cols[v] (v is unique): the candidate flips the symmetric difference of F_T and {v}.  Otherwise T has no candidate.
+ *   metric     of a candidate: from +0.0f, add a of its flipped positions one float32 addition at a time -- the members of F_T in ascending i,
+ *              without v where v cancelled a member, then v last where it was added.  (x + (+0.0f) = x bit for bit for every x >= +0, so an
+ *              addition predicated to +0.0f is the same sum; the kernel adds that way.)
+ *   winner     the candidate with the smallest (metric, T), the metric compared as a number (= as its bit pattern: it is never negative).
+ *   status 0   the winner flips nothing; this is the case exactly when s0 == 0.   status 1   the winner flips at least one bit; its flips are
+ *              applied.   status 2   no T has a candidate; nothing is flipped (a perfect code, n = 2^r - 1, never gets here).
+ * out[R][C][6] int32 = status, pre_err (the weight of e over the n bits), post_err (the weight after the flips), nflip, erased (x_j == 0 after
+ * the NaN map), pay_err (post_err restricted to the payload, the first K bits of the codeword, 1 <= K <= n).  A miscorrection is status 1 with
+ * post_err > 0, an undetected error status 0 with pre_err > 0.
+ * The payload stream (both pointers or neither): llr_out[R][C K] float32 and bits_out[R][C K] int8.  Payload bit i of codeword c is stream entry
+ * u = c K + i (spread == 0) or u = i C + c (spread == 1: a bit interleaver over the run, which turns one failed inner word into isolated errors,
+ * as vaeq_bch_outer's spread does).  An entry holds +1.0f / -1.0f for a decided 0 / 1 (the TX bit xor the final error bit) and the TX bit: the
+ * stream is a valid [R][1][C K] input (w = 1, N = C K, t0 = 0) of every decoder above, which is the whole concatenation.
+ * Workgroups of four waves, grid-stride over tiles of up to 32 consecutive codewords of a run (at most 2048 bits), gathered by all four and then
+ * decoded one wave per codeword; the columns, a 2^r syndrome -> position table, the tile and its part of the stream in LDS (under 24 KiB).
+ * Integers and a fixed order of float32 additions: two calls give identical bits.
+ * Refusals, all before any HIP call and in vaeq_ldpc_decode's order: R == 0 is VAEQ_OK (its pointers may be NULL); a NULL cols_host, llr, bits or
+ * out, or exactly one of llr_out and bits_out, is VAEQ_ERR_NULL, before any shape rule; then VAEQ_ERR_SHAPE for the tensor rules of the LDPC calls
+ * (R < 0, C < 1, N < 1, N > 0x3fffffff, w outside 1 .. 64, t0 < 0, t0 > N), depth outside 0 .. C, n outside 3 .. 256, r outside 2 .. 10, p outside
+ * 0 .. min(6, n), K outside 1 .. n, spread outside 0 .. 1, that depth's fit rule (t0 w + C n > N w, or t0 + C ceil(n / w) > N), R C > 0x7fffffff, and
+ * C K > 0x3fffffff when a stream is asked for; last for the table: a column below 1 or >= 2^r, or one that occurs twice. */
+int vaeq_chase_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t n, int32_t r, const int32_t *cols_host,
+                      const float *llr, const int8_t *bits, int32_t p, int32_t K, int32_t spread, int32_t *out, float *llr_out,
+                      int8_t *bits_out, void *stream);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

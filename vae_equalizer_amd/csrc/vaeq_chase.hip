@@ -1,0 +1,250 @@
+// vaeq_chase.hip -- the soft-in / hard-out inner decoder of include/vaeq.h (vaeq_chase_decode): Chase decoding of a single-error-correcting
+// code given by the columns of its parity-check matrix, over the demappers' LLRs under the LDPC decoders' bit maps, against the TX bits.  The rule
+// acts on e = received xor transmitted, so there is no encoder; integers and float32 additions in a fixed order, so a numpy model gives the same bits.
+//
+// The mapping: workgroups of four waves; the columns and the syndrome -> position table (2^r uint16) built once per workgroup in LDS from the
+// by-value columns; then a workgroup takes tiles of up to 32 consecutive codewords of a run (at most 2048 bits), grid-stride over the tiles.
+// All 256 threads gather the tile through ldpc_gather, one (codeword, symbol) each -- lanes on consecutive symbols of a plane in the bit-packed
+// map, on consecutive codewords (which are consecutive symbols) behind the interleaver -- and file |x| (with the error bit on top) and the TX bit
+// of every position in LDS.  One wave then decodes one codeword: lane l holds the positions l, l + 64, l + 128, l + 192.  The p least reliable
+// positions come from p wave-wide minima of the key |x| bits << 16 | j, after which their (position, column, |x|) are wave-uniform; lane T
+// evaluates test pattern T -- one table lookup and at most seven predicated additions -- and one more minimum over metric bits << 8 | T picks
+// the winner.  Counters are ballots and popcounts.  The payload stream leaves through a transposed byte tile in LDS (rows of 33 bytes: no bank
+// conflict on either side), so that under either spread a wave's stores are runs of consecutive stream entries.  Everything leaves as plain
+// vector stores.  Every loop has a static bound.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vaeq.h"
+#include "vaeq_launch.h"
+#include "vaeq_ldpc.h"
+
+namespace vaeq {
+
+constexpr int CHASE_N = 256, CHASE_R = 10, CHASE_P = 6, CHASE_WAVES = 4, CHASE_NT = 64 * CHASE_WAVES, CHASE_SLOTS = CHASE_N / 64;
+constexpr int CHASE_TILE = 2048, CHASE_TW = 32, CHASE_ROW = 33;   // a tile: bits, codewords; a row of the stream tile in bytes (TW padded by one)
+constexpr int64_t CHASE_GRID = 2048;
+constexpr uint32_t CHASE_NONE = 0xffffu;
+static_assert(CHASE_NT == CHASE_N, "thread j of a workgroup files column j");
+
+struct chase_table {
+    uint16_t col[CHASE_N];
+};
+static_assert(sizeof(chase_table) <= 512, "the table travels in the kernel arguments");
+
+struct chase_args {
+    long long N, t0, tiles;                                    // tiles = R tiles_run
+    int C, w, depth, n, r, p, K, spread, tw, tiles_run;        // tw: the codewords of a full tile, tiles_run = ceil(C / tw)
+};
+
+// the codewords of a full tile and the dynamic LDS of a workgroup: |x| with the error bit (uint32) and the TX bit (uint8) of every position of a
+// tile, each with CHASE_N entries of slack behind (a wave's four slots reach that far past the start of its codeword), and the stream tile
+static inline int chase_tile_words(int n) { return CHASE_TILE / n < CHASE_TW ? CHASE_TILE / n : CHASE_TW; }
+static inline size_t chase_lds_bytes(int n, int K, bool want_stream)
+{
+    const size_t pos = (size_t)chase_tile_words(n) * (n | 1) + CHASE_N;   // a codeword every n | 1 entries: an odd stride, the codewords on different banks
+    return 4 * pos + (want_stream ? ((size_t)K * CHASE_ROW + 3) / 4 * 4 : 0) + pos;
+}
+
+// op over the 64 lanes, the same value in every lane (and in a scalar register): inside a row of 16 lanes four DPP steps -- the neighbour in the
+// quad, the other pair, the other quad of the half row (row_half_mirror), the other half (row_mirror) -- then the four rows by readlane.  No
+// LDS round trip: a butterfly of __shfl_xor is six dependent ds_bpermute, and a codeword needs up to nine reductions one after another.
+template <class Op>
+__device__ __forceinline__ uint32_t chase_wave_reduce(uint32_t x, Op op)
+{
+    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, false));    // quad_perm [1, 0, 3, 2]
+    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, false));    // quad_perm [2, 3, 0, 1]
+    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xf, 0xf, false));   // row_half_mirror
+    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xf, 0xf, false));   // row_mirror
+    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 16);
+    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
+    return op(op(r0, r1), op(r2, r3));
+}
+__device__ __forceinline__ uint32_t chase_wave_min(uint32_t x) { return chase_wave_reduce(x, [](uint32_t a, uint32_t b) { return a < b ? a : b; }); }
+__device__ __forceinline__ uint32_t chase_wave_xor(uint32_t x) { return chase_wave_reduce(x, [](uint32_t a, uint32_t b) { return a ^ b; }); }
+
+template <bool IL>
+__global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, const chase_table tab, const float *__restrict__ llr,
+                                                         const int8_t *__restrict__ bits, int32_t *__restrict__ out,
+                                                         float *__restrict__ llr_out, int8_t *__restrict__ bits_out)
+{
+    extern __shared__ __align__(16) unsigned char chase_lds[];
+    __shared__ uint16_t COL[CHASE_N], POS[1 << CHASE_R];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = A.n, p = A.p, K = A.K, C = A.C, w = A.w;
+    const int ns = n | 1, npos = A.tw * ns + CHASE_N;
+    uint32_t *TA = reinterpret_cast<uint32_t *>(chase_lds);    // the bits of |x|, the error bit in bit 31
+    uint8_t *ST = chase_lds + 4 * (size_t)npos;                // the stream tile: row i, CHASE_ROW bytes, holds TX bit | decided bit << 1 of payload bit i
+    uint8_t *TT = ST + (llr_out ? ((size_t)K * CHASE_ROW + 3) / 4 * 4 : 0);
+
+    for (int s = tid; s < (1 << CHASE_R); s += CHASE_NT) POS[s] = (uint16_t)CHASE_NONE;
+    __syncthreads();
+    {   // CHASE_NT == CHASE_N: thread j owns column j; the columns are distinct, so no two threads write one entry
+        const uint32_t c = tid < n ? tab.col[tid] : 0u;
+        COL[tid] = (uint16_t)c;
+        if (tid < n) POS[c] = (uint16_t)tid;
+    }
+    __syncthreads();
+
+    const int SM = IL ? (n + w - 1) / w : (n + w - 2) / w + 1;  // the most symbols a codeword touches
+    for (long long tile = blockIdx.x; tile < A.tiles; tile += gridDim.x) {
+        const size_t run = (size_t)(tile / A.tiles_run);
+        const int cw0 = (int)(tile - (long long)run * A.tiles_run) * A.tw, TW = min(A.tw, C - cw0);
+        for (int item = tid; item < TW * SM; item += CHASE_NT) {   // one (codeword, symbol) per thread: ldpc_gather's loop runs once, for s
+            int wd, sy;
+            if constexpr (IL) { sy = item / TW; wd = item - sy * TW; }
+            else { wd = item / SM; sy = item - wd * SM; }
+            const int base = wd * ns;
+            ldpc_gather(ldpc_window_of<IL>(cw0 + wd, C, w, A.t0, A.depth, n), run, A.N, w, n, sy, SM, llr, bits, [&](long long j, float x, uint32_t b) {
+                x = x != x ? 0.0f : x;                         // a NaN is +0
+                const uint32_t e = (uint32_t)(x < 0) ^ b;
+                TA[base + (int)j] = (__float_as_uint(x) & 0x7fffffffu) | e << 31;
+                TT[base + (int)j] = (uint8_t)b;
+            });
+        }
+        __syncthreads();
+        for (int wd = wave; wd < TW; wd += CHASE_WAVES) {      // one wave, one codeword
+            const int base = wd * ns;
+            const size_t g = run * (size_t)C + (size_t)(cw0 + wd);
+
+            uint32_t key[CHASE_SLOTS];                             // the bits of |x| of the positions not yet taken, all ones otherwise
+            uint32_t err = 0, txb = 0, s0 = 0;                     // bit k: slot k of this lane
+            int pre = 0, erased = 0;
+#pragma unroll
+            for (int k = 0; k < CHASE_SLOTS; k++) key[k] = ~0u;
+#pragma unroll
+            for (int k = 0; k < CHASE_SLOTS; k++) {
+                if (64 * k >= n) break;                            // wave-uniform: a slot no position falls into
+                const int j = 64 * k + lane;
+                const bool in = j < n;
+                const uint32_t word = TA[base + j], a = word & 0x7fffffffu, e = in ? word >> 31 : 0u;
+                key[k] = in ? a : ~0u;
+                err |= e << k;
+                txb |= (in ? (uint32_t)TT[base + j] : 0u) << k;
+                s0 ^= e ? (uint32_t)COL[j] : 0u;
+                pre += __popcll(__ballot(e != 0));
+                erased += __popcll(__ballot(in && a == 0));
+            }
+            s0 = chase_wave_xor(s0);
+
+            // the p least reliable positions: wave-uniform position, column and |x|
+            uint32_t lp[CHASE_P], lc[CHASE_P];
+            float la[CHASE_P];
+#pragma unroll
+            for (int i = 0; i < CHASE_P; i++) {
+                lp[i] = CHASE_NONE;
+                lc[i] = 0;
+                la[i] = 0.0f;
+                if (i < p) {                                       // wave-uniform; p <= n: a position is left
+                    uint32_t m = key[0];                               // by (|x|, j): the smallest |x| (its bits order as it does: it is never
+#pragma unroll
+                    for (int k = 1; k < CHASE_SLOTS; k++) m = min(m, key[k]);   // negative), then the smallest position that has it
+                    m = chase_wave_min(m);
+                    uint32_t at = CHASE_NONE;
+#pragma unroll
+                    for (int k = CHASE_SLOTS - 1; k >= 0; k--) at = key[k] == m ? (uint32_t)(64 * k + lane) : at;
+                    lp[i] = chase_wave_min(at);
+                    la[i] = __uint_as_float(m);
+                    lc[i] = COL[lp[i]];
+#pragma unroll
+                    for (int k = 0; k < CHASE_SLOTS; k++) key[k] = (uint32_t)(64 * k + lane) == lp[i] ? ~0u : key[k];
+                }
+            }
+
+            // lane T: test pattern T
+            const uint32_t T = (uint32_t)lane;
+            uint32_t s = s0;
+#pragma unroll
+            for (int i = 0; i < CHASE_P; i++) s ^= (T >> i) & 1u ? lc[i] : 0u;
+            const uint32_t v = s ? (uint32_t)POS[s] : CHASE_NONE;  // s < 2^r: a xor of columns
+            const bool cand = T < (1u << p) && (s == 0 || v != CHASE_NONE);
+            float metric = 0.0f;
+            bool cancelled = false;
+#pragma unroll
+            for (int i = 0; i < CHASE_P; i++) {                    // x + (+0) = x for x >= 0: the predicated add is the specified sum
+                const bool in = (T >> i) & 1u, hit = in && lp[i] == v;
+                metric += in && !hit ? la[i] : 0.0f;
+                cancelled |= hit;
+            }
+            const uint32_t av = TA[base + (int)min(v, (uint32_t)CHASE_N - 1u)] & 0x7fffffffu;
+            metric += v != CHASE_NONE && !cancelled ? __uint_as_float(av) : 0.0f;
+            const uint32_t mine = cand ? __float_as_uint(metric) : ~0u, best = chase_wave_min(mine);   // by (metric, T)
+
+            int status = 2, nflip = 0;
+            uint32_t flip = 0;                                     // bit k: slot k of this lane is flipped
+            if (best != ~0u) {                                     // wave-uniform
+                const uint32_t Tw = chase_wave_min(mine == best ? T : CHASE_NONE), vw = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)Tw);
+#pragma unroll
+                for (int k = 0; k < CHASE_SLOTS; k++) {
+                    if (64 * k >= n) break;
+                    const uint32_t j = (uint32_t)(64 * k + lane);
+                    uint32_t f = vw == j;                          // the symmetric difference of F_T and {v}
+#pragma unroll
+                    for (int i = 0; i < CHASE_P; i++) f ^= (uint32_t)(((Tw >> i) & 1u) && lp[i] == j);
+                    flip |= f << k;
+                    nflip += __popcll(__ballot(f != 0));
+                }
+                status = nflip ? 1 : 0;
+            }
+            err ^= flip;
+            int post = 0, pay_post = 0;
+#pragma unroll
+            for (int k = 0; k < CHASE_SLOTS; k++) {
+                if (64 * k >= n) break;
+                const int j = 64 * k + lane;
+                const bool e = (err >> k) & 1u;
+                post += __popcll(__ballot(e));
+                pay_post += __popcll(__ballot(e && j < K));
+                if (llr_out && j < K) ST[j * CHASE_ROW + wd] = (uint8_t)(((txb >> k) & 1u) | (((txb >> k) & 1u) ^ (uint32_t)e) << 1);
+            }
+            if (lane < 6) {
+                const int val = lane == 0 ? status : lane == 1 ? pre : lane == 2 ? post : lane == 3 ? nflip : lane == 4 ? erased : pay_post;
+                out[(size_t)g * 6 + lane] = val;
+            }
+        }
+        if (llr_out) {                                         // (uniform: a kernel argument)
+            __syncthreads();
+            const size_t sbase = run * (size_t)C * (size_t)K;
+            for (int item = tid; item < TW * K; item += CHASE_NT) {   // consecutive lanes, consecutive stream entries: along the codewords under
+                int wd, i;                                            // the spread, along the payload bits without
+                if (A.spread) { i = item / TW; wd = item - i * TW; }
+                else { wd = item / K; i = item - wd * K; }
+                const size_t u = sbase + (A.spread ? (size_t)i * (size_t)C + (size_t)(cw0 + wd) : (size_t)(cw0 + wd) * (size_t)K + (size_t)i);
+                const uint32_t d = ST[i * CHASE_ROW + wd];
+                llr_out[u] = d & 2u ? -1.0f : 1.0f;
+                bits_out[u] = (int8_t)(d & 1u);
+            }
+        }
+        __syncthreads();                                       // the tiles are the next iteration's
+    }
+}
+
+}  // namespace vaeq
+
+extern "C" int vaeq_chase_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t n, int32_t r,
+                                 const int32_t *cols_host, const float *llr, const int8_t *bits, int32_t p, int32_t K, int32_t spread,
+                                 int32_t *out, float *llr_out, int8_t *bits_out, void *stream)
+{
+    using namespace vaeq;
+    if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
+    if (!cols_host || !llr || !bits || !out || !llr_out != !bits_out) return VAEQ_ERR_NULL;
+    if (R < 0 || C < 1 || N < 1 || N > 0x3fffffff || w < 1 || w > LDPC_W || t0 < 0 || t0 > N || depth < 0 || depth > C || n < 3 || n > CHASE_N ||
+        r < 2 || r > CHASE_R || p < 0 || p > CHASE_P || p > n || K < 1 || K > n || spread < 0 || spread > 1)
+        return VAEQ_ERR_SHAPE;
+    if (depth >= 1 ? t0 + (int64_t)C * ((n + w - 1) / w) > N : t0 * w + (int64_t)C * n > N * w) return VAEQ_ERR_SHAPE;
+    if ((int64_t)R * C > 0x7fffffff || (llr_out && (int64_t)C * K > 0x3fffffff)) return VAEQ_ERR_SHAPE;
+    chase_table tab = {};
+    bool seen[1 << CHASE_R] = {};
+    for (int j = 0; j < n; j++) {                              // distinct, non-zero, below 2^r
+        const int32_t c = cols_host[j];
+        if (c < 1 || c >= (1 << r) || seen[c]) return VAEQ_ERR_SHAPE;
+        seen[c] = true;
+        tab.col[j] = (uint16_t)c;
+    }
+    const int tw = chase_tile_words(n), tiles_run = (C + tw - 1) / tw;
+    const chase_args A = {(long long)N, (long long)t0, (long long)R * tiles_run, (int)C, (int)w, (int)depth, (int)n, (int)r, (int)p, (int)K, (int)spread,
+                          tw, tiles_run};
+    const dim3 grid((unsigned)(A.tiles < CHASE_GRID ? A.tiles : CHASE_GRID)), block(CHASE_NT);
+    return launch(depth >= 1 ? chase_kernel<true> : chase_kernel<false>, grid, block, chase_lds_bytes(n, K, llr_out != nullptr),
+                  reinterpret_cast<hipStream_t>(stream), A, tab, llr, bits, out, llr_out, bits_out);
+}

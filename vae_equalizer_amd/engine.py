@@ -1045,6 +1045,116 @@ def staircase_decode(llr, bits, code, window, t0=0, chains=None, iters=8, want_h
     return ret
 
 
+class HammingCode:
+    """A single-error-correcting code for chase_decode, given by the columns of its parity-check matrix: cols[n], column j an r-bit integer.
+    .n, .r, .cols (int32), .rank (of the columns over GF(2)), .k = n - rank, .rate = k / n.  ValueError outside vaeq_chase_decode's envelope: n in
+    3 .. 256, r in 2 .. 10, integer columns that are distinct, non-zero and below 2^r.  hamming_code builds the two textbook families; a standard's
+    own matrix (the OIF 400ZR (128,119) word among them) is not in this package: a user who has its columns passes them here."""
+
+    def __init__(self, cols, r):
+        import numbers
+        import numpy as np
+        if not isinstance(r, numbers.Integral) or isinstance(r, bool) or not 2 <= int(r) <= 10:
+            raise ValueError(f"HammingCode: r in 2 .. 10, got {r!r}")
+        c = np.asarray(cols)
+        if c.ndim != 1 or not 3 <= c.size <= 256 or c.dtype == bool or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError(f"HammingCode: 3 .. 256 integer columns, got {c.dtype} of shape {c.shape}")
+        if (c < 1).any() or (c >= 1 << int(r)).any() or np.unique(c).size != c.size:
+            raise ValueError(f"HammingCode: the columns are distinct, non-zero and below 2^{int(r)}")
+        self.cols, self.n, self.r = np.ascontiguousarray(c.astype(np.int32)), int(c.size), int(r)
+        basis = {}                                             # leading bit -> a reduced column: Gaussian elimination over GF(2)
+        for x in (int(v) for v in self.cols):
+            while x and x.bit_length() in basis:
+                x ^= basis[x.bit_length()]
+            if x:
+                basis[x.bit_length()] = x
+        self.rank = len(basis)
+        self.k = self.n - self.rank
+        self.rate = self.k / self.n
+
+
+def hamming_code(m, extended=True, n=None):
+    """The HammingCode of the textbook column rules, shortened to its first n columns: extended (d = 4): r = m + 1, cols[j] = (j << 1) | 1,
+    n <= 2^m (the default); plain (d = 3): r = m, cols[j] = j + 1, n <= 2^m - 1 (the default).  hamming_code(7) is the extended (128, 120) code,
+    hamming_code(3, extended=False) the perfect (7, 4) code.  .k = n - r wherever the kept columns have rank r.  This is NOT the (128, 119) matrix of
+    the OIF 400ZR agreement, which this package does not hold: pass its columns to HammingCode."""
+    import numbers
+    import numpy as np
+    if not isinstance(m, numbers.Integral) or isinstance(m, bool) or (n is not None and (not isinstance(n, numbers.Integral) or isinstance(n, bool))):
+        raise ValueError(f"hamming_code takes integers, got m={m!r}, n={n!r}")
+    m, full = int(m), (1 << int(m)) - (0 if extended else 1) if 1 <= int(m) <= 10 else 0
+    n = full if n is None else int(n)
+    if not 1 <= n <= full:
+        raise ValueError(f"hamming_code({m}, extended={bool(extended)}): n in 1 .. {full}, got {n}")
+    j = np.arange(n, dtype=np.int64)
+    return HammingCode((j << 1) | 1 if extended else j + 1, m + 1 if extended else m)
+
+
+def chase_decode(llr, bits, code, t0=0, codewords=None, depth=None, patterns=4, payload=None, spread=True, want_stream=False):
+    """The soft-in / hard-out inner decoder in front of the hard-decision FEC (vaeq_chase_decode): Chase decoding of the HammingCode `code` over
+    per-bit LLRs against the TX bits (no encoder: the rule acts on the error pattern).  llr, bits, t0, depth and the bit map as for ldpc_decode with
+    n = code.n; codewords: per run, default the most that fit behind t0.  patterns = p in 0 .. min(6, n): the 2^p test patterns over the p least
+    reliable positions, each completed by syndrome decoding; the candidate with the smallest sum of |llr| over its flips wins.  p = 0 is plain
+    syndrome decoding of the hard decisions.  payload: the first K bits of every codeword (default code.k).
+    -> dict(status, pre_err, bit_err, nflip, erased, pay_err [R,C] int64: status 0 = zero syndrome, 1 = flipped nflip bits, 2 = no candidate,
+    left alone; bit_err the errors after decoding over the n bits, pay_err those among the payload; BER_post[R], BER_pre[R] over the C n bits,
+    BER_payload[R] over the C K payload bits, FER[R] the share of codewords with bit_err > 0, f32; miscorrected[R] (status 1 with bit_err > 0) and
+    undetected[R] (status 0 with pre_err > 0) int64).  want_stream: stream = dict(llr[R,1,C K] f32, bits[R,1,C K] int8), the decided payload
+    bits as +-1.0 and their TX bits, codeword after codeword or, with spread, bit-interleaved over the run (payload bit i of codeword c at
+    i C + c): a valid input of every decoder here with t0 = 0, which is how staircase_decode runs behind this one."""
+    if not isinstance(code, HammingCode):
+        raise ValueError(f"chase_decode takes a HammingCode, got {code!r}")
+    if llr.shape != bits.shape or llr.dim() not in (3, 4):
+        raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
+    dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
+    llr = llr.reshape(R, -1, N).contiguous()
+    bits = bits.reshape(R, -1, N).contiguous()
+    w, n = llr.shape[1], code.n
+    C_ = int(codewords) if codewords is not None else _ldpc_fit(N, w, n, t0, depth)
+    if codewords is None and C_ < 1:
+        raise ValueError(f"no codeword of {n} bits fits into {N - int(t0)} symbols of {w} bits")
+    K = code.k if payload is None else int(payload)
+    if not 1 <= K <= n:
+        raise ValueError(f"payload = {K}: the first 1 .. {n} bits of a codeword")
+    Cn = max(C_, 0)
+    out = torch.empty(R, Cn, 6, dtype=torch.int32, device=dev)
+    s_llr = torch.empty(R, 1, Cn * K, dtype=torch.float32, device=dev) if want_stream else None
+    s_bits = torch.empty(R, 1, Cn * K, dtype=torch.int8, device=dev) if want_stream else None
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_chase_decode(R, C_, N, w, int(t0), 0 if depth is None else int(depth), n, code.r, code.cols.ctypes.data_as(C.c_void_p),
+                                              nat.ptr(llr), nat.ptr(bits, torch.int8), int(patterns), K, int(bool(spread)), nat.ptr(out, torch.int32),
+                                              nat.ptr(s_llr), nat.ptr(s_bits, torch.int8), nat.current_stream(dev)), "vaeq_chase_decode")
+    o = out.long()
+    tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)
+    ret = dict(status=o[..., 0], pre_err=o[..., 1], bit_err=o[..., 2], nflip=o[..., 3], erased=o[..., 4], pay_err=o[..., 5],
+               BER_post=(o[..., 2].sum(1).double() / tot).float(), BER_pre=(o[..., 1].sum(1).double() / tot).float(),
+               BER_payload=(o[..., 5].sum(1).double() / torch.full_like(tot, float(max(C_ * K, 1)))).float(),
+               FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float(),
+               miscorrected=((o[..., 0] == 1) & (o[..., 2] > 0)).sum(1), undetected=((o[..., 0] == 0) & (o[..., 1] > 0)).sum(1))
+    if want_stream:
+        ret["stream"] = dict(llr=s_llr, bits=s_bits)
+    return ret
+
+
+INNER_KEYS = ("code", "patterns", "depth", "payload", "spread")
+
+
+def resolve_inner(inner):
+    """The inner= dict(code=HammingCode, patterns=4, depth=None, payload=None, spread=True) of a fec= with a StaircaseCode, its defaults filled in.
+    ValueError for an unknown key, a missing code or one that is no HammingCode, patterns outside 0 .. min(6, n), a payload outside 1 .. n (or a
+    code without a payload bit where none is given), a depth below 1."""
+    import numbers
+    if not isinstance(inner, dict) or set(inner) - set(INNER_KEYS) or not isinstance(inner.get("code"), HammingCode):
+        raise ValueError(f"inner takes a dict of {', '.join(INNER_KEYS)} with a HammingCode under code; got {sorted(inner) if isinstance(inner, dict) else inner!r}")
+    code = inner["code"]
+    patterns, payload, depth = inner.get("patterns", 4), inner.get("payload"), inner.get("depth")
+    payload = code.k if payload is None else payload
+    for name, v, lo, hi in (("patterns", patterns, 0, min(6, code.n)), ("payload", payload, 1, code.n), ("depth", 1 if depth is None else depth, 1, None)):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or v < lo or (hi is not None and v > hi):
+            raise ValueError(f"inner[{name!r}] = {v!r}: an integer in {lo} .. {'' if hi is None else hi}")
+    return dict(code=code, patterns=int(patterns), depth=None if depth is None else int(depth), payload=int(payload), spread=bool(inner.get("spread", True)))
+
+
 FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant", "window", "iters", "test", "fixed", "outer")
 FEC_BLOCK_ONLY, FEC_SC_ONLY = ("max_iter", "depth", "quant"), ("window", "iters", "test", "fixed")
 FEC_STAIRCASE_KEYS = ("code", "window", "t0", "iters")
@@ -1053,8 +1163,10 @@ FEC_STAIRCASE_KEYS = ("code", "window", "t0", "iters")
 def check_fec(fec):
     """ValueError for a fec= dict that fec_figures would refuse (None passes): for a runner to call before it allocates or launches anything."""
     if isinstance(fec, dict) and isinstance(fec.get("code"), StaircaseCode):
-        if set(fec) - set(FEC_STAIRCASE_KEYS) or fec.get("window") is None:
-            raise ValueError(f"fec with a StaircaseCode takes {', '.join(FEC_STAIRCASE_KEYS)}, window required; got {sorted(fec)}")
+        if set(fec) - set(FEC_STAIRCASE_KEYS) - {"inner"} or fec.get("window") is None:
+            raise ValueError(f"fec with a StaircaseCode takes {', '.join(FEC_STAIRCASE_KEYS)}, inner, window required; got {sorted(fec)}")
+        if fec.get("inner") is not None:
+            resolve_inner(fec["inner"])
         return
     if fec is not None and (set(fec) - set(FEC_KEYS) or "code" not in fec):
         raise ValueError(f"fec takes {', '.join(FEC_KEYS)}; got {sorted(fec)}")
@@ -1089,10 +1201,21 @@ def fec_figures(llr, fec):
     fixed, outer; code and window required): max_iter, depth and quant are a ValueError there, as window, iters, test and fixed are with an
     LdpcCode.  fixed = dict(bits, ...), quant's format, is the window decoder's quant=: fixed point, vaeq_ldpc_sc_decode_q.  With a StaircaseCode
     under code it is staircase_decode, hard-decision FEC, under fec = dict(code, window, t0, iters; code and window required); every other key
-    is a ValueError there."""
+    is a ValueError there, but for inner = dict(code=HammingCode, patterns=4, depth=None, payload=None, spread=True): the concatenated scheme,
+    chase_decode on the LLRs behind t0 and the staircase code on its payload stream from 0 (as many chains as fit the C K stream bits).  The
+    staircase's dict comes back with BER_pre the inner decoder's -- the channel's, what a sweep's BER_pre_fec column means -- and the inner
+    decoder's dict under "inner"."""
     check_fec(fec)
+    if isinstance(fec["code"], StaircaseCode) and fec.get("inner") is not None:
+        inner = resolve_inner(fec["inner"])
+        first = chase_decode(llr["llr"], llr["bits"], inner["code"], t0=fec.get("t0", 0), depth=inner["depth"], patterns=inner["patterns"],
+                             payload=inner["payload"], spread=inner["spread"], want_stream=True)
+        stream = first.pop("stream")
+        ret = staircase_decode(stream["llr"], stream["bits"], **{k: v for k, v in fec.items() if k not in ("inner", "t0")})
+        ret["BER_pre"], ret["inner"] = first["BER_pre"], first
+        return ret
     if isinstance(fec["code"], StaircaseCode):
-        return staircase_decode(llr["llr"], llr["bits"], **fec)
+        return staircase_decode(llr["llr"], llr["bits"], **{k: v for k, v in fec.items() if k != "inner"})
     kw = {"quant" if k == "fixed" else k: v for k, v in fec.items() if k != "code"}
     L, B = llr["llr"], llr["bits"]
     decode = ldpc_sc_decode if isinstance(fec["code"], ScLdpcCode) else ldpc_decode
