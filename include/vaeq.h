@@ -911,6 +911,70 @@ int vaeq_chase_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, in
                       const float *llr, const int8_t *bits, int32_t p, int32_t K, int32_t spread, int32_t *out, float *llr_out,
                       int8_t *bits_out, void *stream);
 
+/* Soft-decision turbo product codes: a Chase-Pyndiah soft-in / soft-out decoder of a product code whose rows and columns are words of two
+ * single-error-correcting codes, iterated rows / columns, as the 100G soft-decision FEC of coherent optics decoded its extended-Hamming product
+ * codes (no reference counterpart).  Unlike the float32 min-sum LDPC decoder it is NOT invariant to a common factor on the LLRs: it mixes them
+ * with a beta given in absolute units (times scale), so it shows what an equalizer's noise-variance estimate costs behind the FEC.
+ * The code: a block is an array of n1 x n2 bits, n = n1 n2.  Every row is a word of the row code cols2_host[n2] (columns of r2 bits), every
+ * column a word of the column code cols1_host[n1] (columns of r1 bits); both are vaeq_chase_decode tables (host memory, validated on every call,
+ * by value to the kernel) under its rules: n1, n2 in 3 .. 256, r1, r2 in 2 .. 10, the columns distinct, non-zero and below 2^r.
+ * The tensors llr[R][w][N] / bits[R][w][N] and the bit-packed map are vaeq_ldpc_decode's with this n, C blocks per run: bit (a, b) of block c is
+ * global bit g = c n + a n2 + b at symbol t0 + g / w, plane g % w, and t0 w + C n <= N w.  No interleaver option: a product code is its own.
+ * No encoder: both codes are linear and the rule symmetric; it is stated on r, the LLR towards the transmitted bit, and acts there exactly as a
+ * real decoder acts on a transmitted codeword -- except for inputs that are exactly zero, which a real decoder reads as bit 0 whatever was sent
+ * and which here become a zero towards the transmitted bit (-0 against a TX bit 1, +0 otherwise; neither is < 0).
+ * The rule, in integers and float32 so that a numpy model reproduces every bit:
+ *   input      x_j = the LLR of bit j, a NaN mapped to +0;  r_j = bits_j ? -x_j : x_j, then clamped, min(max(r_j, -clip), clip), which also tames
+ *              infinities.  pre_err counts (x_j < 0) xor bits_j, as every decoder here does; erased counts x_j == 0.
+ *   state      W_j float32, +0 at the start.
+ *   schedule   half-iterations h = 0 .. 2 iters - 1; an even h decodes all rows, an odd h all columns.  All words of a half-iteration are
+ *              decided on the state before it (they own disjoint bits).  The soft input of a word is R_j = r_j + alpha_h W_j: one float32
+ *              multiplication, then one float32 addition, not fused.
+ *   one word   of length n' and table cols, as vaeq_chase_decode with a_j = |R_j| and e_j = (R_j < 0): s0 the xor of the columns with e_j = 1,
+ *              the p least reliable positions by (a_j, j), the test patterns T = 0 .. 2^p - 1, their candidates, flip sets Phi_T and metrics
+ *              m_T exactly as there, in the same order of additions; the winner D is the smallest (m_T, T); d_j = e_j xor [j in Phi_D].
+ *              Status 0: s0 == 0.  Status 1: the winner flips.  Status 2: no candidate; then d_j = e_j and W'_j = +0 for the whole word.
+ *   soft out   max-log, Pyndiah, per position j of a word of status 0 / 1: m_C(j) = the minimum of m_T over the candidates with j in the
+ *              symmetric difference of Phi_T and Phi_D (a plain minimum: no order, no tie-break; candidates equal to D as a set compete
+ *              nowhere).  With such a candidate: Delta = m_C(j) - m_D, one float32 subtraction, never negative; L_j = d_j ? -Delta : Delta;
+ *              W'_j = L_j - R_j, one float32 subtraction.  Without one: W'_j = d_j ? -beta : beta with beta = fl(beta_h scale_r) where that
+ *              product is > 0 (a NaN, a zero and a negative product give +0), at most clip; nbeta counts these positions.  Then W'_j is
+ *              clamped, min(max(W'_j, -clip), clip), and replaces W_j.  Putting the extrinsic value of a position without a competitor at
+ *              +-beta is a choice: it is the form used in most work after Pyndiah 1998, not the only one.
+ *   stop       after half-iteration h the decisions d of the whole block are tested: if no word of h had status 2 and every word of the OTHER
+ *              direction has a zero syndrome on d, decoding stops, ok = 1.  The test also runs after the last half-iteration.  A clean block
+ *              costs one half-iteration.
+ * out[R][C][8] int32, the first five in vaeq_staircase_decode's layout: iters (half-iterations executed), ok, post_err (the weight of the final
+ * d), pre_err, erased, pay_err (final errors among rows < K1 and columns < K2, 1 <= K1 <= n1, 1 <= K2 <= n2), nstat2 (status-2 words over all
+ * executed half-iterations), nbeta.
+ * Nullable: llr_out[R][C n] float32 and bits_out[R][C n] int8 (both or neither), a stream as vaeq_chase_decode's -- +1.0f / -1.0f for the
+ * decided bit (the TX bit xor the final d) and the TX bit, block after block in bit order, a valid [R][1][C n] input of every decoder here;
+ * ext[R][C][n] float32, W after the last executed half-iteration, as it stands; half_err[R][C][2 iters] int32, the weight of d after each
+ * executed half-iteration, -1 behind the stop.  scale[R] float32 in DEVICE memory, nullable = 1.0f; alpha_host[2 iters], beta_host[2 iters] in
+ * host memory.
+ * Bounds: p in 0 .. min(6, n1, n2), iters in 1 .. 16, every alpha_h finite in [0, 16], every beta_h finite and >= 0, clip finite in (0, 2^96].
+ * Under them no infinity and no NaN arises anywhere: |r|, |W| and beta are at most clip, so |R| <= 17 clip, a metric adds at most 7 of those and
+ * every difference stays below 2^105.
+ * One workgroup per block in flight, grid-stride; r, W and a byte of TX bit and decision per bit stay in LDS for all half-iterations, the rows at
+ * the odd stride n2 | 1; one wave per word, the competitors by LDS atomic minima on the metrics' bit patterns (order-free: two calls give
+ * identical bits).  16 waves where n > 4096, else 4.  vaeq_tpc_lds_bytes(n1, r1, n2, r2) = 8 n1 (n2 | 1) (r and W) + n1 (n2 | 1) padded to a
+ * word (the bytes) + 4 waves max(n1, n2) (a competitor array per wave) + 2 (n1 + n2) padded to a word (the columns) + 2 (2^r1 + 2^r2) (syndrome
+ * -> position), the kernel's dynamic LDS, at most 156 KiB: with the kernel's static counters (under 1 KiB) that fits the 160 KiB of a CU.  The
+ * extended (128, 120)^2 block holds 158 336 bytes.  That call returns VAEQ_ERR_SHAPE outside the ranges of n1, r1, n2, r2 and VAEQ_ERR_LDS above
+ * the bound.
+ * Refusals, all before any HIP call and in vaeq_chase_decode's order: R == 0 is VAEQ_OK (its pointers may be NULL); a NULL cols1_host,
+ * cols2_host, llr, bits, alpha_host, beta_host or out, or exactly one of llr_out and bits_out, is VAEQ_ERR_NULL, before any shape rule; then
+ * VAEQ_ERR_SHAPE for the tensor rules of the LDPC calls (R < 0, C < 1, N < 1, N > 0x3fffffff, w outside 1 .. 64, t0 < 0, t0 > N), the ranges
+ * above, K1 outside 1 .. n1, K2 outside 1 .. n2, the fit rule (t0 w + C n > N w; C n stays below 2^47), R C > 0x7fffffff, and C n > 0x3fffffff
+ * when a stream is asked for; then VAEQ_ERR_LDS for a state above the bound; last VAEQ_ERR_SHAPE for the two tables, cols1_host first: a column
+ * below 1 or >= 2^r, or one that occurs twice. */
+int vaeq_tpc_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0,
+                    int32_t n1, int32_t r1, const int32_t *cols1_host, int32_t n2, int32_t r2, const int32_t *cols2_host,
+                    const float *llr, const int8_t *bits, int32_t p, int32_t iters,
+                    const float *alpha_host, const float *beta_host, const float *scale, float clip,
+                    int32_t K1, int32_t K2, int32_t *out, float *llr_out, int8_t *bits_out, float *ext, int32_t *half_err, void *stream);
+int64_t vaeq_tpc_lds_bytes(int32_t n1, int32_t r1, int32_t n2, int32_t r2);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

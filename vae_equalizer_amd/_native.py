@@ -13,7 +13,7 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("VAEQ_LIB") or os.path.join(_PKG, "libvaeq_hip.so")   # VAEQ_LIB: A/B builds of the kernels (tools/build_variant.sh)
-SOURCES = ["vaeq_dp.hip", "vaeq_dp_wave.hip", "vaeq_dp_wave_mw.hip", "vaeq_dp_wave_mw8.hip", "vaeq_dp_wave_bk.hip", "vaeq_dp_wave_b128.hip", "vaeq_dp_wave_fl.hip", "vaeq_awgn.hip", "vaeq_awgn_wave.hip", "vaeq_misc.hip", "vaeq_ops.hip", "vaeq_nn.hip", "vaeq_nn_ops.hip", "vaeq_cma.hip", "vaeq_awgn_cma.hip", "vaeq_awgn_dfe.hip", "vaeq_epilogue.hip", "vaeq_epilogue_info.hip", "vaeq_cma_info.hip", "vaeq_awgn_info.hip", "vaeq_awgn_track_info.hip", "vaeq_epilogue_llr.hip", "vaeq_awgn_llr.hip", "vaeq_cma_llr.hip", "vaeq_awgn_track_llr.hip", "vaeq_ldpc.hip", "vaeq_ldpc_q.hip", "vaeq_ldpc_sc.hip", "vaeq_ldpc_sc_q.hip", "vaeq_bch.hip", "vaeq_staircase.hip", "vaeq_chase.hip", "vaeq_gen.hip"]
+SOURCES = ["vaeq_dp.hip", "vaeq_dp_wave.hip", "vaeq_dp_wave_mw.hip", "vaeq_dp_wave_mw8.hip", "vaeq_dp_wave_bk.hip", "vaeq_dp_wave_b128.hip", "vaeq_dp_wave_fl.hip", "vaeq_awgn.hip", "vaeq_awgn_wave.hip", "vaeq_misc.hip", "vaeq_ops.hip", "vaeq_nn.hip", "vaeq_nn_ops.hip", "vaeq_cma.hip", "vaeq_awgn_cma.hip", "vaeq_awgn_dfe.hip", "vaeq_epilogue.hip", "vaeq_epilogue_info.hip", "vaeq_cma_info.hip", "vaeq_awgn_info.hip", "vaeq_awgn_track_info.hip", "vaeq_epilogue_llr.hip", "vaeq_awgn_llr.hip", "vaeq_cma_llr.hip", "vaeq_awgn_track_llr.hip", "vaeq_ldpc.hip", "vaeq_ldpc_q.hip", "vaeq_ldpc_sc.hip", "vaeq_ldpc_sc_q.hip", "vaeq_bch.hip", "vaeq_staircase.hip", "vaeq_chase.hip", "vaeq_tpc.hip", "vaeq_gen.hip"]
 HEADERS = ["vaeq_common.h", "vaeq_launch.h", "vaeq_wave.h", "vaeq_validate.h", "vaeq_dp_wave_kernel.h", "vaeq_gen_fused.h", "vaeq_epilogue_lds.h", "vaeq_epilogue_keep.h", "vaeq_info.h", "vaeq_llr.h", "vaeq_noise.h", "vaeq_awgn_eval.h", "vaeq_nn_dev.h", "vaeq_nn_enc_backward_body.h", "vaeq_ldpc.h", "vaeq_ldpc_sc.h"]
 _LIB = None
 
@@ -113,7 +113,8 @@ EXPORTS = ["vaeq_dp_train", "vaeq_dp_step_debug", "vaeq_dp_lds_bytes", "vaeq_dp_
            "vaeq_awgn_track_info", "vaeq_awgn_dfe_soft", "vaeq_dp_epilogue_llr", "vaeq_awgn_llr",
            "vaeq_cma_epilogue_llr", "vaeq_awgn_track_llr", "vaeq_ldpc_decode", "vaeq_ldpc_lds_bytes", "vaeq_ldpc_decode_il",
            "vaeq_ldpc_decode_q", "vaeq_ldpc_q_lds_bytes", "vaeq_bch_outer", "vaeq_ldpc_sc_decode", "vaeq_ldpc_sc_lds_bytes",
-           "vaeq_ldpc_sc_decode_q", "vaeq_ldpc_sc_q_lds_bytes", "vaeq_staircase_decode", "vaeq_staircase_lds_bytes", "vaeq_chase_decode"]
+           "vaeq_ldpc_sc_decode_q", "vaeq_ldpc_sc_q_lds_bytes", "vaeq_staircase_decode", "vaeq_staircase_lds_bytes", "vaeq_chase_decode",
+           "vaeq_tpc_decode", "vaeq_tpc_lds_bytes"]
 
 
 def lib():
@@ -203,6 +204,11 @@ def lib():
         L.vaeq_chase_decode.restype = C.c_int
         L.vaeq_chase_decode.argtypes = ([C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p] * 3
                                         + [C.c_int32] * 3 + [C.c_void_p] * 4)
+        L.vaeq_tpc_decode.restype = C.c_int
+        L.vaeq_tpc_decode.argtypes = ([C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64] + [C.c_int32, C.c_int32, C.c_void_p] * 2
+                                      + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 3 + [C.c_float] + [C.c_int32] * 2 + [C.c_void_p] * 6)
+        L.vaeq_tpc_lds_bytes.restype = C.c_int64
+        L.vaeq_tpc_lds_bytes.argtypes = [C.c_int32] * 4
         L.vaeq_awgn_track_info.restype = C.c_int
         L.vaeq_awgn_track_info.argtypes = [C.c_int32, C.c_int64, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p] * 9
         L.vaeq_awgn_dfe_soft.restype = C.c_int

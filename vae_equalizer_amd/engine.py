@@ -1136,6 +1136,126 @@ def chase_decode(llr, bits, code, t0=0, codewords=None, depth=None, patterns=4, 
     return ret
 
 
+class ProductCode:
+    """A product code for tpc_decode: blocks of col.n x row.n bits whose columns are words of the HammingCode `col` and whose rows are words of
+    the HammingCode `row`.  .col, .row, .n = col.n row.n, .k = col.k row.k, .rate = k / n.  ValueError for anything but two HammingCodes, or a
+    block whose state passes the LDS bound of vaeq_tpc_decode (include/vaeq.h; the extended (128, 120)^2 block fits)."""
+
+    def __init__(self, col, row):
+        if not isinstance(col, HammingCode) or not isinstance(row, HammingCode):
+            raise ValueError(f"ProductCode takes two HammingCodes, got {col!r} and {row!r}")
+        self.col, self.row = col, row
+        self.n, self.k = col.n * row.n, col.k * row.k
+        self.rate = self.k / self.n
+        if nat.lib().vaeq_tpc_lds_bytes(col.n, col.r, row.n, row.r) < 0:
+            raise ValueError(f"ProductCode: the state of a block of {col.n} x {row.n} bits does not fit the LDS of a CU (vaeq_tpc_lds_bytes)")
+
+
+TPC_ALPHA = (0.0, 0.2, 0.3, 0.5, 0.7, 0.9, 1.0, 1.0)          # Pyndiah's schedules per half-iteration, continued with 1
+TPC_BETA = (0.2, 0.4, 0.6, 0.8, 1.0, 1.0)
+TPC_CLIP = 2.0 ** 60
+
+
+def _tpc_schedule(name, given, default, iters, hi):
+    """-> float32[2 iters]: `given` (2 iters values) or the default continued with 1; ValueError outside vaeq_tpc_decode's bounds."""
+    import numpy as np
+    if given is None:
+        v = np.array((list(default) + [1.0] * (2 * iters))[:2 * iters], np.float32)
+    else:
+        try:
+            v = np.ascontiguousarray(np.asarray(given, dtype=np.float32).reshape(-1))
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: 2 iters = {2 * iters} numbers, got {given!r}") from None
+    if v.shape != (2 * iters,) or not np.isfinite(v).all() or (v < 0).any() or (hi is not None and (v > hi).any()):
+        raise ValueError(f"{name}: 2 iters = {2 * iters} finite values in [0, {'inf' if hi is None else hi}{')' if hi is None else ']'}, got {given!r}")
+    return v
+
+
+def resolve_tpc(code, iters=4, patterns=4, alpha=None, beta=None, clip=None, payload=None):
+    """tpc_decode's host-side arguments with their defaults filled in -> dict(iters, patterns, alpha, beta (float32[2 iters]), clip, payload
+    (K1, K2)).  ValueError outside vaeq_tpc_decode's bounds."""
+    import math
+    import numbers
+    if not isinstance(code, ProductCode):
+        raise ValueError(f"tpc_decode takes a ProductCode, got {code!r}")
+    for name, v, lo, hi in (("iters", iters, 1, 16), ("patterns", patterns, 0, min(6, code.col.n, code.row.n))):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not lo <= v <= hi:
+            raise ValueError(f"{name} = {v!r}: an integer in {lo} .. {hi}")
+    iters = int(iters)
+    clip = TPC_CLIP if clip is None else clip
+    if not isinstance(clip, numbers.Real) or isinstance(clip, bool) or not math.isfinite(clip) or not 0 < clip <= 2.0 ** 96:
+        raise ValueError(f"clip = {clip!r}: finite, in (0, 2^96]")
+    K = (code.col.k, code.row.k) if payload is None else payload
+    if (not isinstance(K, (tuple, list)) or len(K) != 2 or any(not isinstance(v, numbers.Integral) or isinstance(v, bool) for v in K)
+            or not 1 <= K[0] <= code.col.n or not 1 <= K[1] <= code.row.n):
+        raise ValueError(f"payload = {K!r}: (K1, K2), the first 1 .. {code.col.n} rows and 1 .. {code.row.n} columns of a block")
+    return dict(iters=iters, patterns=int(patterns), alpha=_tpc_schedule("alpha", alpha, TPC_ALPHA, iters, 16.0),
+                beta=_tpc_schedule("beta", beta, TPC_BETA, iters, None), clip=float(clip), payload=(int(K[0]), int(K[1])))
+
+
+def tpc_decode(llr, bits, code, t0=0, blocks=None, iters=4, patterns=4, alpha=None, beta=None, scale=None, clip=None, payload=None,
+               want_stream=False, want_ext=False, want_profile=False):
+    """Post-FEC figures of per-bit LLRs behind a soft-decision turbo product code on the device (vaeq_tpc_decode): Chase-Pyndiah decoding of the
+    ProductCode `code`, rows in the even half-iterations and columns in the odd ones, at most 2 iters of them, each word by a Chase decoder over
+    2^patterns test patterns whose competing candidates give the extrinsic values.  llr, bits, t0 and the bit map as for ldpc_decode with
+    n = code.n; blocks: per run, default the most that fit behind t0.  No encoder: the rule is stated on the LLRs towards the TX bits.
+    alpha, beta: 2 iters values per half-iteration, default Pyndiah's schedules (0, .2, .3, .5, .7, .9, 1, 1 and .2, .4, .6, .8, 1, 1, continued
+    with 1).  scale: per run ([R] tensor or a number), the unit of beta; default the float32 mean of |llr| over the run's tensor, non-finite
+    entries counted as 0, formed on the device without a host synchronisation.  Unlike min-sum LDPC decoding the result depends on the scale of
+    the LLRs.  clip: the bound of |r| and |W|, default 2^60.  payload = (K1, K2): the first rows and columns of a block, default (col.k, row.k).
+    -> staircase_decode's common keys (iters [R,C]: half-iterations executed; ok: stopped on a product codeword; bit_err, pre_err, erased [R,C]
+    int64; BER_post[R], BER_pre[R], FER[R] f32) plus pay_err, nstat2 (words without a candidate), nbeta (positions without a competitor) [R,C],
+    BER_payload[R] over the C K1 K2 payload bits, and the resolved alpha, beta (tuples of float), scale ([R] f32) and clip.  want_stream:
+    stream = dict(llr[R,1,C n] f32, bits[R,1,C n] int8), the decided bits as +-1.0 and their TX bits, a valid input of every decoder here with
+    t0 = 0.  want_ext: ext[R,C,n] f32, the extrinsic values after the last executed half-iteration.  want_profile: half_err[R,C,2 iters] int64,
+    the errors after each executed half-iteration, -1 behind the stop."""
+    prm = resolve_tpc(code, iters, patterns, alpha, beta, clip, payload)
+    if llr.shape != bits.shape or llr.dim() not in (3, 4):
+        raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
+    dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
+    llr = llr.reshape(R, -1, N).contiguous()
+    bits = bits.reshape(R, -1, N).contiguous()
+    w, n = llr.shape[1], code.n
+    C_ = int(blocks) if blocks is not None else _ldpc_fit(N, w, n, t0, None)
+    if blocks is None and C_ < 1:
+        raise ValueError(f"no block of {n} bits fits into {N - int(t0)} symbols of {w} bits")
+    if scale is None:
+        scale = torch.where(torch.isfinite(llr), llr.abs(), torch.zeros((), dtype=llr.dtype, device=dev)).mean(dim=(1, 2), dtype=torch.float32)
+    elif not torch.is_tensor(scale):
+        scale = torch.full((R,), float(scale), dtype=torch.float32, device=dev)
+    scale = scale.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    if scale.shape != (R,):
+        raise ValueError(f"scale: one value per run, [{R}], got {tuple(scale.shape)}")
+    Cn, H = max(C_, 0), 2 * prm["iters"]
+    out = torch.empty(R, Cn, 8, dtype=torch.int32, device=dev)
+    s_llr = torch.empty(R, 1, Cn * n, dtype=torch.float32, device=dev) if want_stream else None
+    s_bits = torch.empty(R, 1, Cn * n, dtype=torch.int8, device=dev) if want_stream else None
+    ext = torch.empty(R, Cn, n, dtype=torch.float32, device=dev) if want_ext else None
+    half = torch.empty(R, Cn, H, dtype=torch.int32, device=dev) if want_profile else None
+    K1, K2 = prm["payload"]
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vaeq_tpc_decode(R, C_, N, w, int(t0), code.col.n, code.col.r, code.col.cols.ctypes.data_as(C.c_void_p), code.row.n,
+                                            code.row.r, code.row.cols.ctypes.data_as(C.c_void_p), nat.ptr(llr), nat.ptr(bits, torch.int8),
+                                            prm["patterns"], prm["iters"], prm["alpha"].ctypes.data_as(C.c_void_p),
+                                            prm["beta"].ctypes.data_as(C.c_void_p), nat.ptr(scale) if R else None, prm["clip"], K1, K2,
+                                            nat.ptr(out, torch.int32), nat.ptr(s_llr), nat.ptr(s_bits, torch.int8), nat.ptr(ext),
+                                            nat.ptr(half, torch.int32), nat.current_stream(dev)), "vaeq_tpc_decode")
+    o = out.long()
+    tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)
+    ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4], pay_err=o[..., 5], nstat2=o[..., 6],
+               nbeta=o[..., 7], BER_post=(o[..., 2].sum(1).double() / tot).float(), BER_pre=(o[..., 3].sum(1).double() / tot).float(),
+               BER_payload=(o[..., 5].sum(1).double() / torch.full_like(tot, float(max(C_ * K1 * K2, 1)))).float(),
+               FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float(),
+               alpha=tuple(float(v) for v in prm["alpha"]), beta=tuple(float(v) for v in prm["beta"]), scale=scale, clip=prm["clip"])
+    if want_stream:
+        ret["stream"] = dict(llr=s_llr, bits=s_bits)
+    if want_ext:
+        ret["ext"] = ext
+    if want_profile:
+        ret["half_err"] = half.long()
+    return ret
+
+
 INNER_KEYS = ("code", "patterns", "depth", "payload", "spread")
 
 
@@ -1158,10 +1278,16 @@ def resolve_inner(inner):
 FEC_KEYS = ("code", "t0", "max_iter", "alpha", "depth", "quant", "window", "iters", "test", "fixed", "outer")
 FEC_BLOCK_ONLY, FEC_SC_ONLY = ("max_iter", "depth", "quant"), ("window", "iters", "test", "fixed")
 FEC_STAIRCASE_KEYS = ("code", "window", "t0", "iters")
+FEC_TPC_KEYS = ("code", "t0", "iters", "patterns", "alpha", "beta", "scale", "clip")
 
 
 def check_fec(fec):
     """ValueError for a fec= dict that fec_figures would refuse (None passes): for a runner to call before it allocates or launches anything."""
+    if isinstance(fec, dict) and isinstance(fec.get("code"), ProductCode):
+        if set(fec) - set(FEC_TPC_KEYS):
+            raise ValueError(f"fec with a ProductCode takes {', '.join(FEC_TPC_KEYS)}; got {sorted(fec)}")
+        resolve_tpc(fec["code"], **{k: fec[k] for k in ("iters", "patterns", "alpha", "beta", "clip") if fec.get(k) is not None})
+        return
     if isinstance(fec, dict) and isinstance(fec.get("code"), StaircaseCode):
         if set(fec) - set(FEC_STAIRCASE_KEYS) - {"inner"} or fec.get("window") is None:
             raise ValueError(f"fec with a StaircaseCode takes {', '.join(FEC_STAIRCASE_KEYS)}, inner, window required; got {sorted(fec)}")
@@ -1204,8 +1330,11 @@ def fec_figures(llr, fec):
     is a ValueError there, but for inner = dict(code=HammingCode, patterns=4, depth=None, payload=None, spread=True): the concatenated scheme,
     chase_decode on the LLRs behind t0 and the staircase code on its payload stream from 0 (as many chains as fit the C K stream bits).  The
     staircase's dict comes back with BER_pre the inner decoder's -- the channel's, what a sweep's BER_pre_fec column means -- and the inner
-    decoder's dict under "inner"."""
+    decoder's dict under "inner".  With a ProductCode under code it is tpc_decode, the soft-decision turbo product decoder, under fec = dict(code,
+    t0, iters, patterns, alpha, beta, scale, clip; all but code optional); every other key is a ValueError there."""
     check_fec(fec)
+    if isinstance(fec["code"], ProductCode):
+        return tpc_decode(llr["llr"], llr["bits"], **{k: v for k, v in fec.items() if v is not None})
     if isinstance(fec["code"], StaircaseCode) and fec.get("inner") is not None:
         inner = resolve_inner(fec["inner"])
         first = chase_decode(llr["llr"], llr["bits"], inner["code"], t0=fec.get("t0", 0), depth=inner["depth"], patterns=inner["patterns"],
