@@ -102,6 +102,6 @@ def test_declared_and_exported():
     for poly in ("0x13", "0x25", "0x43", "0x89", "0x11D", "0x211", "0x409", "0x805", "0x1053", "0x201B"):
         assert poly in header
     assert "vaeq_bch_outer" in nat.EXPORTS and hasattr(nat.lib(), "vaeq_bch_outer")
-    assert "vaeq_bch.hip" in nat.SOURCES and "vaeq_ldpc.h" in nat.HEADERS
+    assert "vaeq_bch.hip" in nat.SOURCES and "vaeq_ldpc.h" in nat.HEADERS and "vaeq_fec.h" in nat.HEADERS
     for fn in ("vaeq_ldpc_decode", "vaeq_ldpc_decode_il", "vaeq_ldpc_decode_q"):  # the inner decoders stay beside it
         assert fn in nat.EXPORTS and hasattr(nat.lib(), fn)

@@ -76,7 +76,7 @@ def test_declared_and_exported():
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "vaeq.h")).read()
     assert "int vaeq_chase_decode(" in header
     assert "vaeq_chase_decode" in nat.EXPORTS and hasattr(nat.lib(), "vaeq_chase_decode")
-    assert "vaeq_chase.hip" in nat.SOURCES and "vaeq_ldpc.h" in nat.HEADERS
+    assert "vaeq_chase.hip" in nat.SOURCES and "vaeq_ldpc.h" in nat.HEADERS and "vaeq_fec.h" in nat.HEADERS
 
 
 def test_hamming_code():

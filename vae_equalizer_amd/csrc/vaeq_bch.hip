@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "vaeq.h"
+#include "vaeq_fec.h"
 #include "vaeq_launch.h"
 #include "vaeq_ldpc.h"
 
@@ -23,29 +24,8 @@ namespace vaeq {
 #ifndef VAEQ_BCH_WAVES
 #define VAEQ_BCH_WAVES 4                                       // waves per workgroup: 8 and 16 measured, DESIGN.md
 #endif
-constexpr int BCH_M_MIN = 4, BCH_M_MAX = 13, BCH_T = 16, BCH_WAVES = VAEQ_BCH_WAVES, BCH_NT = 64 * BCH_WAVES, BCH_IT = (1 << BCH_M_MAX) / 64;
+constexpr int BCH_M_MIN = GF_M_MIN, BCH_M_MAX = GF_M_MAX, BCH_T = 16, BCH_WAVES = VAEQ_BCH_WAVES, BCH_NT = 64 * BCH_WAVES, BCH_IT = (1 << BCH_M_MAX) / 64;
 constexpr int64_t BCH_GRID = 8192 / BCH_WAVES;
-
-// the primitive polynomial of GF(2^m), m = 4 .. 13, as a bit mask (include/vaeq.h)
-static inline uint32_t bch_poly(int m)
-{
-    static const uint32_t poly[BCH_M_MAX - BCH_M_MIN + 1] = {0x13, 0x25, 0x43, 0x89, 0x11D, 0x211, 0x409, 0x805, 0x1053, 0x201B};
-    return poly[m - BCH_M_MIN];
-}
-
-// the size of the union of the cyclotomic cosets of 1 .. 2t modulo 2^m - 1: the degree of the generator
-static inline int bch_parity(int m, int t)
-{
-    const int q = (1 << m) - 1;
-    bool seen[1 << BCH_M_MAX] = {};
-    int count = 0;
-    for (int j = 1; j <= 2 * t; j++)
-        for (int x = j % q; !seen[x]; x = 2 * x % q) {
-            seen[x] = true;
-            count++;
-        }
-    return count;
-}
 
 struct bch_args {
     long long N, t0, total;                                    // total = R C_o outer codewords
@@ -112,12 +92,7 @@ __global__ __launch_bounds__(BCH_NT) void bch_outer_kernel(const bch_args A, con
     }
     __syncthreads();
 
-    auto mul = [&](uint32_t a, uint32_t b) -> uint32_t {
-        uint32_t s = (uint32_t)LOG[a] + (uint32_t)LOG[b];
-        s = s >= q ? s - q : s;
-        const uint32_t v = EXP[s];
-        return a && b ? v : 0u;
-    };
+    auto mul = [&](uint32_t a, uint32_t b) { return gf_mul(EXP, LOG, q, a, b); };
 
     bch_scratch &sc = scratch[wave];
     const int nit = (n_o + 63) >> 6;
@@ -284,17 +259,15 @@ extern "C" int vaeq_bch_outer(int32_t R, int32_t C, int64_t N, int32_t w, int64_
     using namespace vaeq;
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!post || !bits || !out) return VAEQ_ERR_NULL;
-    if (R < 0 || C < 1 || (int64_t)R * C > 0x7fffffff || N < 1 || N > 0x3fffffff || w < 1 || w > LDPC_W || t0 < 0 || t0 > N || depth < 0 || depth > C ||
-        n < 2 || n > LDPC_NB * LDPC_Z)
-        return VAEQ_ERR_SHAPE;
+    if (!fec_frame_ok(R, C, N, w, t0) || (int64_t)R * C > 0x7fffffff || depth < 0 || depth > C || n < 2 || n > LDPC_NB * LDPC_Z) return VAEQ_ERR_SHAPE;
     const bool il = depth >= 1;
-    if (il ? t0 + (int64_t)C * ((n + w - 1) / w) > N : t0 * w + (int64_t)C * n > N * w) return VAEQ_ERR_SHAPE;
+    if (!fec_fit_ok(il, C, n, w, t0, N)) return VAEQ_ERR_SHAPE;
     if (K < 1 || K > n || m < BCH_M_MIN || m > BCH_M_MAX || t < 1 || t > BCH_T || n_o > (1 << m) - 1 || n_o <= bch_parity(m, t) || spread < 0 ||
         spread > 1 || post_i16 < 0 || post_i16 > 1 || C_o < 1 || (int64_t)R * C_o > 0x7fffffff)
         return VAEQ_ERR_SHAPE;
     if ((int64_t)C_o * n_o > (int64_t)C * K) return VAEQ_ERR_SHAPE;
     const bch_args A = {(long long)N, (long long)t0, (long long)R * C_o, (int)C, (int)w, (int)depth, (int)n, (int)K, (int)m, (int)t, (int)n_o, (int)C_o,
-                        (int)spread, (int)post_i16, bch_poly(m)};
+                        (int)spread, (int)post_i16, gf_poly(m)};
     const bool wide = (int64_t)C * n > 0x7fffffff || (int64_t)w * N > 0xffffffffll;
     const int64_t blocks = (A.total + BCH_WAVES - 1) / BCH_WAVES;
     const dim3 grid((unsigned)(blocks < BCH_GRID ? blocks : BCH_GRID)), block(BCH_NT);

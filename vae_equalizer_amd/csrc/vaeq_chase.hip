@@ -9,28 +9,25 @@
 // of every position in LDS.  One wave then decodes one codeword: lane l holds the positions l, l + 64, l + 128, l + 192.  The p least reliable
 // positions come from p wave-wide minima of the key |x| bits << 16 | j, after which their (position, column, |x|) are wave-uniform; lane T
 // evaluates test pattern T -- one table lookup and at most seven predicated additions -- and one more minimum over metric bits << 8 | T picks
-// the winner.  Counters are ballots and popcounts.  The payload stream leaves through a transposed byte tile in LDS (rows of 33 bytes: no bank
+// the winner.  That span is the text of vaeq_fec.h's chase_front, which vaeq_tpc.hip calls; it stands here in place because this kernel measured
+// 4 to 8 % slower through the call: a fix to one goes to the other.  Counters are ballots and popcounts.
+// The payload stream leaves through a transposed byte tile in LDS (rows of 33 bytes: no bank
 // conflict on either side), so that under either spread a wave's stores are runs of consecutive stream entries.  Everything leaves as plain
 // vector stores.  Every loop has a static bound.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "vaeq.h"
+#include "vaeq_fec.h"
 #include "vaeq_launch.h"
 #include "vaeq_ldpc.h"
 
 namespace vaeq {
 
-constexpr int CHASE_N = 256, CHASE_R = 10, CHASE_P = 6, CHASE_WAVES = 4, CHASE_NT = 64 * CHASE_WAVES, CHASE_SLOTS = CHASE_N / 64;
+constexpr int CHASE_WAVES = 4, CHASE_NT = 64 * CHASE_WAVES;
 constexpr int CHASE_TILE = 2048, CHASE_TW = 32, CHASE_ROW = 33;   // a tile: bits, codewords; a row of the stream tile in bytes (TW padded by one)
 constexpr int64_t CHASE_GRID = 2048;
-constexpr uint32_t CHASE_NONE = 0xffffu;
 static_assert(CHASE_NT == CHASE_N, "thread j of a workgroup files column j");
-
-struct chase_table {
-    uint16_t col[CHASE_N];
-};
-static_assert(sizeof(chase_table) <= 512, "the table travels in the kernel arguments");
 
 struct chase_args {
     long long N, t0, tiles;                                    // tiles = R tiles_run
@@ -46,25 +43,8 @@ static inline size_t chase_lds_bytes(int n, int K, bool want_stream)
     return 4 * pos + (want_stream ? ((size_t)K * CHASE_ROW + 3) / 4 * 4 : 0) + pos;
 }
 
-// op over the 64 lanes, the same value in every lane (and in a scalar register): inside a row of 16 lanes four DPP steps -- the neighbour in the
-// quad, the other pair, the other quad of the half row (row_half_mirror), the other half (row_mirror) -- then the four rows by readlane.  No
-// LDS round trip: a butterfly of __shfl_xor is six dependent ds_bpermute, and a codeword needs up to nine reductions one after another.
-template <class Op>
-__device__ __forceinline__ uint32_t chase_wave_reduce(uint32_t x, Op op)
-{
-    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, false));    // quad_perm [1, 0, 3, 2]
-    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, false));    // quad_perm [2, 3, 0, 1]
-    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xf, 0xf, false));   // row_half_mirror
-    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xf, 0xf, false));   // row_mirror
-    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 16);
-    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
-    return op(op(r0, r1), op(r2, r3));
-}
-__device__ __forceinline__ uint32_t chase_wave_min(uint32_t x) { return chase_wave_reduce(x, [](uint32_t a, uint32_t b) { return a < b ? a : b; }); }
-__device__ __forceinline__ uint32_t chase_wave_xor(uint32_t x) { return chase_wave_reduce(x, [](uint32_t a, uint32_t b) { return a ^ b; }); }
-
 template <bool IL>
-__global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, const chase_table tab, const float *__restrict__ llr,
+__global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, const fec_cols tab, const float *__restrict__ llr,
                                                          const int8_t *__restrict__ bits, int32_t *__restrict__ out,
                                                          float *__restrict__ llr_out, int8_t *__restrict__ bits_out)
 {
@@ -125,7 +105,7 @@ __global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, con
                 pre += __popcll(__ballot(e != 0));
                 erased += __popcll(__ballot(in && a == 0));
             }
-            s0 = chase_wave_xor(s0);
+            s0 = fec_wave_xor(s0);
 
             // the p least reliable positions: wave-uniform position, column and |x|
             uint32_t lp[CHASE_P], lc[CHASE_P];
@@ -139,11 +119,11 @@ __global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, con
                     uint32_t m = key[0];                               // by (|x|, j): the smallest |x| (its bits order as it does: it is never
 #pragma unroll
                     for (int k = 1; k < CHASE_SLOTS; k++) m = min(m, key[k]);   // negative), then the smallest position that has it
-                    m = chase_wave_min(m);
+                    m = fec_wave_min(m);
                     uint32_t at = CHASE_NONE;
 #pragma unroll
                     for (int k = CHASE_SLOTS - 1; k >= 0; k--) at = key[k] == m ? (uint32_t)(64 * k + lane) : at;
-                    lp[i] = chase_wave_min(at);
+                    lp[i] = fec_wave_min(at);
                     la[i] = __uint_as_float(m);
                     lc[i] = COL[lp[i]];
 #pragma unroll
@@ -168,12 +148,12 @@ __global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, con
             }
             const uint32_t av = TA[base + (int)min(v, (uint32_t)CHASE_N - 1u)] & 0x7fffffffu;
             metric += v != CHASE_NONE && !cancelled ? __uint_as_float(av) : 0.0f;
-            const uint32_t mine = cand ? __float_as_uint(metric) : ~0u, best = chase_wave_min(mine);   // by (metric, T)
+            const uint32_t mine = cand ? __float_as_uint(metric) : ~0u, best = fec_wave_min(mine);   // by (metric, T)
 
             int status = 2, nflip = 0;
             uint32_t flip = 0;                                     // bit k: slot k of this lane is flipped
             if (best != ~0u) {                                     // wave-uniform
-                const uint32_t Tw = chase_wave_min(mine == best ? T : CHASE_NONE), vw = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)Tw);
+                const uint32_t Tw = fec_wave_min(mine == best ? T : CHASE_NONE), vw = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)Tw);
 #pragma unroll
                 for (int k = 0; k < CHASE_SLOTS; k++) {
                     if (64 * k >= n) break;
@@ -228,19 +208,13 @@ extern "C" int vaeq_chase_decode(int32_t R, int32_t C, int64_t N, int32_t w, int
     using namespace vaeq;
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!cols_host || !llr || !bits || !out || !llr_out != !bits_out) return VAEQ_ERR_NULL;
-    if (R < 0 || C < 1 || N < 1 || N > 0x3fffffff || w < 1 || w > LDPC_W || t0 < 0 || t0 > N || depth < 0 || depth > C || n < 3 || n > CHASE_N ||
-        r < 2 || r > CHASE_R || p < 0 || p > CHASE_P || p > n || K < 1 || K > n || spread < 0 || spread > 1)
+    if (!fec_frame_ok(R, C, N, w, t0) || depth < 0 || depth > C || n < 3 || n > CHASE_N || r < 2 || r > CHASE_R || p < 0 || p > CHASE_P || p > n ||
+        K < 1 || K > n || spread < 0 || spread > 1)
         return VAEQ_ERR_SHAPE;
-    if (depth >= 1 ? t0 + (int64_t)C * ((n + w - 1) / w) > N : t0 * w + (int64_t)C * n > N * w) return VAEQ_ERR_SHAPE;
+    if (!fec_fit_ok(depth >= 1, C, n, w, t0, N)) return VAEQ_ERR_SHAPE;
     if ((int64_t)R * C > 0x7fffffff || (llr_out && (int64_t)C * K > 0x3fffffff)) return VAEQ_ERR_SHAPE;
-    chase_table tab = {};
-    bool seen[1 << CHASE_R] = {};
-    for (int j = 0; j < n; j++) {                              // distinct, non-zero, below 2^r
-        const int32_t c = cols_host[j];
-        if (c < 1 || c >= (1 << r) || seen[c]) return VAEQ_ERR_SHAPE;
-        seen[c] = true;
-        tab.col[j] = (uint16_t)c;
-    }
+    fec_cols tab;
+    if (!fec_cols_pack(cols_host, n, r, &tab)) return VAEQ_ERR_SHAPE;
     const int tw = chase_tile_words(n), tiles_run = (C + tw - 1) / tw;
     const chase_args A = {(long long)N, (long long)t0, (long long)R * tiles_run, (int)C, (int)w, (int)depth, (int)n, (int)r, (int)p, (int)K, (int)spread,
                           tw, tiles_run};

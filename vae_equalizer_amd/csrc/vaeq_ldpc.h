@@ -4,9 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vaeq_fec.h"
+
 namespace vaeq {
 
-constexpr int LDPC_MB = 8, LDPC_NB = 64, LDPC_ROW = 32, LDPC_Z = 512, LDPC_ITER = 100, LDPC_W = 64;
+constexpr int LDPC_MB = 8, LDPC_NB = 64, LDPC_ROW = 32, LDPC_Z = 512, LDPC_ITER = 100, LDPC_W = FEC_W;
 constexpr int64_t LDPC_STATE_MAX = 64 * 1024;
 
 // Row l: edges e < wt[l] in ascending block column, two per dword, edge e in bits 16 (e & 1) .. of dword e / 2 as column << 9 | shift.
@@ -159,17 +161,14 @@ static inline bool ldpc_dims_ok(int64_t mb, int64_t nb, int64_t Z)
     return mb >= 1 && mb <= LDPC_MB && nb >= 2 && nb <= LDPC_NB && Z >= 2 && Z <= LDPC_Z;
 }
 
-// The shape rules the two decoders share, behind the empty batch and the NULL pointers: il = the interleaver's fit rule t0 + C S <= N, else the
-// bit-packed one t0 w + C n <= N w; lds = the state of a codeword in bytes.
+// The shape rules the two decoders share, behind the empty batch and the NULL pointers: the frame and fit rules of vaeq_fec.h (il = the
+// interleaver's); lds = the state of a codeword in bytes.
 static inline bool ldpc_shape_ok(int64_t R, int64_t C, int64_t N, int64_t w, int64_t t0, int64_t depth, int64_t mb, int64_t nb, int64_t Z,
                                  int64_t max_iter, int64_t lds, bool il)
 {
-    if (R < 0 || C < 1 || N < 1 || N > 0x3fffffff || w < 1 || w > LDPC_W || t0 < 0 || t0 > N || max_iter < 1 || max_iter > LDPC_ITER ||
-        !ldpc_dims_ok(mb, nb, Z) || (il && (depth < 1 || depth > C)))
+    if (!fec_frame_ok(R, C, N, w, t0) || max_iter < 1 || max_iter > LDPC_ITER || !ldpc_dims_ok(mb, nb, Z) || (il && (depth < 1 || depth > C)))
         return false;
-    const int64_t n = nb * Z;
-    const bool fits = il ? t0 + C * ((n + w - 1) / w) <= N : t0 * w + C * n <= N * w;
-    return lds <= LDPC_STATE_MAX && fits && R * C <= 0x7fffffff;
+    return lds <= LDPC_STATE_MAX && fec_fit_ok(il, C, nb * Z, w, t0, N) && R * C <= 0x7fffffff;
 }
 
 }  // namespace vaeq

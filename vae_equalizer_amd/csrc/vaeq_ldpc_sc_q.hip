@@ -256,11 +256,10 @@ extern "C" int vaeq_ldpc_sc_decode_q(int32_t R, int32_t C, int64_t N, int32_t w,
     using namespace vaeq;
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!components_host || !llr || !bits || !out) return VAEQ_ERR_NULL;
-    if (R < 0 || C < 1 || N < 1 || N > 0x3fffffff || w < 1 || w > LDPC_W || t0 < 0 || t0 > N || iters < 1 || iters > LDPC_ITER ||
-        !sc_dims_ok(ms, mb, nb, Z, W) || Lc < 1 || Lc > SC_LC || T < 1 || T > W)
+    if (!fec_frame_ok(R, C, N, w, t0) || iters < 1 || iters > LDPC_ITER || !sc_dims_ok(ms, mb, nb, Z, W) || Lc < 1 || Lc > SC_LC || T < 1 || T > W)
         return VAEQ_ERR_SHAPE;
     const int64_t n_chain = (int64_t)Lc * nb * Z, lds = sc_q_state_bytes(ms, mb, nb, Z, W);
-    if (lds > LDPC_STATE_MAX || t0 * w + (int64_t)C * n_chain > N * w || (int64_t)R * C > 0x7fffffff || (int64_t)C * Lc > 0x7fffffff)
+    if (lds > LDPC_STATE_MAX || !fec_fit_ok(false, C, n_chain, w, t0, N) || (int64_t)R * C > 0x7fffffff || (int64_t)C * Lc > 0x7fffffff)
         return VAEQ_ERR_SHAPE;
     if (!ldpc_q_rule_ok(qbits, abits, scale, num, beta)) return VAEQ_ERR_SHAPE;
     sc_table tab;

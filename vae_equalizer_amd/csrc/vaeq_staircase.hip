@@ -15,37 +15,19 @@
 // of pair 1 is "L roots among the positions s .. 2 s - 1": the search never leaves the word.  L = 1 needs no search, its root is log Lambda_1.
 // A block enters through vaeq_ldpc.h's gather (consecutive lanes on consecutive symbols of a plane): its slot is cleared and every error bit
 // is an LDS atomic or into both copies -- errors are a percent of the bits.  A block's final state leaves when the window moves past it.
-// The table code repeats vaeq_bch.hip's: that file compiles to what it was.
+// The table code and the syndrome step repeat vaeq_bch.hip's: from one shared function both kernels compile to other code.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "vaeq.h"
+#include "vaeq_fec.h"
 #include "vaeq_launch.h"
 #include "vaeq_ldpc.h"
 
 namespace vaeq {
 
-constexpr int STC_M_MIN = 4, STC_M_MAX = 10, STC_T = 8, STC_S = 511, STC_L = 65535, STC_W = 32;
-
-static inline uint32_t stc_poly(int m)
-{
-    static const uint32_t poly[STC_M_MAX - STC_M_MIN + 1] = {0x13, 0x25, 0x43, 0x89, 0x11D, 0x211, 0x409};
-    return poly[m - STC_M_MIN];
-}
-
-// the size of the union of the cyclotomic cosets of 1 .. 2t modulo 2^m - 1: the degree of the generator
-static inline int stc_parity(int m, int t)
-{
-    const int q = (1 << m) - 1;
-    bool seen[1 << STC_M_MAX] = {};
-    int count = 0;
-    for (int j = 1; j <= 2 * t; j++)
-        for (int x = j % q; !seen[x]; x = 2 * x % q) {
-            seen[x] = true;
-            count++;
-        }
-    return count;
-}
+constexpr int STC_M_MIN = GF_M_MIN, STC_M_MAX = 10, STC_T = 8, STC_S = 511, STC_L = 65535, STC_W = 32;
+static_assert(STC_M_MAX <= GF_M_MAX, "the field comes from vaeq_fec.h");
 
 static inline bool stc_dims_ok(int64_t m, int64_t s, int64_t W)
 {
@@ -108,12 +90,7 @@ __global__ __launch_bounds__(512) void staircase_kernel(const stc_args A, const 
     for (int k = tid; k < 2 * ring * blk; k += NT) ROWS[k] = 0u;                                 // block 0 is all zero and stays so
     __syncthreads();
 
-    auto mul = [&](uint32_t a, uint32_t b) -> uint32_t {
-        uint32_t e = (uint32_t)LOG[a] + (uint32_t)LOG[b];
-        e = e >= q ? e - q : e;
-        const uint32_t v = EXP[e];
-        return a && b ? v : 0u;
-    };
+    auto mul = [&](uint32_t a, uint32_t b) { return gf_mul(EXP, LOG, q, a, b); };
 
     unsigned pre = 0, era = 0, nflip = 0, bad = 0;
     // block i (1 .. L) enters a cleared slot: the gather of the s^2 bits behind global bit chain0 + (i - 1) s^2
@@ -397,14 +374,14 @@ extern "C" int vaeq_staircase_decode(int32_t R, int32_t C, int64_t N, int32_t w,
     using namespace vaeq;
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!llr || !bits || !out) return VAEQ_ERR_NULL;
-    if (R < 0 || C < 1 || N < 1 || N > 0x3fffffff || w < 1 || w > LDPC_W || t0 < 0 || t0 > N || iters < 1 || iters > LDPC_ITER)
-        return VAEQ_ERR_SHAPE;
-    if (t < 1 || t > STC_T || !stc_dims_ok(m, s, W) || stc_parity(m, t) >= 2 * s || L < 1 || L > STC_L) return VAEQ_ERR_SHAPE;
-    // the fit rule t0 w + C n_chain <= N w without the product: C n_chain passes 2^63 (n_chain reaches 1.7e10, C 2^31 - 1); (N - t0) w < 2^36
+    if (!fec_frame_ok(R, C, N, w, t0) || iters < 1 || iters > LDPC_ITER) return VAEQ_ERR_SHAPE;
+    if (t < 1 || t > STC_T || !stc_dims_ok(m, s, W) || bch_parity(m, t) >= 2 * s || L < 1 || L > STC_L) return VAEQ_ERR_SHAPE;
+    // the bit-packed fit rule t0 w + C n_chain <= N w without the product, so not fec_fit_ok: C n_chain passes 2^63 (n_chain reaches 1.7e10,
+    // C 2^31 - 1); (N - t0) w < 2^36
     const int64_t n_chain = (int64_t)L * s * s, room = (N - t0) * w;
     if (stc_state_bytes(m, s, W) > LDPC_STATE_MAX || C > room / n_chain || (int64_t)R * C > 0x7fffffff) return VAEQ_ERR_SHAPE;
     const int P = L - W + 1 > 1 ? L - W + 1 : 1;
-    const stc_args A = {(long long)N, (long long)t0, (int)C, (int)w, (int)m, (int)s, (int)L, (int)W, (int)iters, P, stc_poly(m)};
+    const stc_args A = {(long long)N, (long long)t0, (int)C, (int)w, (int)m, (int)s, (int)L, (int)W, (int)iters, P, gf_poly(m)};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((int64_t)R * C)), block((unsigned)((s + 63) / 64 * 64));
     const size_t lds = (size_t)stc_state_bytes(m, s, W);

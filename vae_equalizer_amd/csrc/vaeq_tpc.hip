@@ -6,7 +6,7 @@
 // The mapping: one workgroup per block in flight, grid-stride over the R C blocks.  All threads gather the block once through ldpc_gather and
 // file r (clamped) and W (float32 each, row stride n2 | 1: a column walk changes bank at every step) and a byte TX bit | d << 1 per bit in LDS,
 // where they stay for all half-iterations.  In a half-iteration one wave decodes one word, lanes on positions (base + j stride: stride 1 along a
-// row, n2 | 1 along a column).  What chase_kernel does carries over: the p least reliable positions from p wave-wide minima of the key
+// row, n2 | 1 along a column).  vaeq_fec.h's chase_front does the Chase part: the p least reliable positions from p wave-wide minima of the key
 // |R| bits, lane T evaluates test pattern T, one more minimum over the metric bits picks the winner D.  The competitor search: every lane that
 // holds a candidate walks the at most p + 2 positions where its flips can differ from D's -- the p least reliable ones, its own syndrome position
 // and D's -- and, where they do differ, files its metric's bits with an LDS atomic minimum (non-negative floats order as unsigned integers) into a
@@ -21,24 +21,20 @@
 #include <stdint.h>
 
 #include "vaeq.h"
+#include "vaeq_fec.h"
 #include "vaeq_launch.h"
 #include "vaeq_ldpc.h"
 
 // Every float32 operation of the rule is rounded on its own.  The build contracts a * b + c into one fma by default, and HIP's __fmul_rn /
 // __fadd_rn are plain operators inside a header, which contract like any other: the rule's arithmetic is written with the operators of the
-// language behind this line, where nothing is fused.
+// language behind this line, where nothing is fused.  vaeq_fec.h stands before it and holds no product.
 #pragma clang fp contract(off)
 
 namespace vaeq {
 
-constexpr int TPC_N = 256, TPC_R = 10, TPC_P = 6, TPC_SLOTS = TPC_N / 64, TPC_ITERS = 16, TPC_HALF = 2 * TPC_ITERS;
+constexpr int TPC_ITERS = 16, TPC_HALF = 2 * TPC_ITERS;        // the words are the Chase front end's: n <= CHASE_N, r <= CHASE_R, p <= CHASE_P
 constexpr int TPC_WAVES_BIG = 16, TPC_WAVES_SMALL = 4, TPC_BIG_ABOVE = 4096;
 constexpr int64_t TPC_GRID = 1024, TPC_LDS_MAX = 156 * 1024;   // the dynamic block; the static counters below take under 1 KiB of the rest
-constexpr uint32_t TPC_NONE = 0xffffu;
-
-struct tpc_table {
-    uint16_t col[TPC_N];
-};
 
 struct tpc_args {
     long long N, t0, blocks;                                   // blocks = R C
@@ -46,7 +42,7 @@ struct tpc_args {
     float clip;
     float alpha[TPC_HALF], beta[TPC_HALF];
 };
-static_assert(sizeof(tpc_args) + 2 * sizeof(tpc_table) <= 2048, "the tables and the schedules travel in the kernel arguments");
+static_assert(sizeof(tpc_args) + 2 * sizeof(fec_cols) <= 2048, "the tables and the schedules travel in the kernel arguments");
 
 static inline int tpc_waves(int n1, int n2) { return n1 * n2 > TPC_BIG_ABOVE ? TPC_WAVES_BIG : TPC_WAVES_SMALL; }
 // r and W (float32) and the byte TX bit | d << 1 of every bit at the odd row stride, the competitor array of every wave, the two tables of
@@ -58,24 +54,8 @@ static inline int64_t tpc_state_bytes(int n1, int r1, int n2, int r2)
 }
 static inline bool tpc_dims_ok(int64_t n1, int64_t r1, int64_t n2, int64_t r2)
 {
-    return n1 >= 3 && n1 <= TPC_N && n2 >= 3 && n2 <= TPC_N && r1 >= 2 && r1 <= TPC_R && r2 >= 2 && r2 <= TPC_R;
+    return n1 >= 3 && n1 <= CHASE_N && n2 >= 3 && n2 <= CHASE_N && r1 >= 2 && r1 <= CHASE_R && r2 >= 2 && r2 <= CHASE_R;
 }
-
-// chase_kernel's reduction: four DPP steps inside a row of 16 lanes, then the four rows by readlane; the same value in every lane
-template <class Op>
-__device__ __forceinline__ uint32_t tpc_wave_reduce(uint32_t x, Op op)
-{
-    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, false));    // quad_perm [1, 0, 3, 2]
-    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, false));    // quad_perm [2, 3, 0, 1]
-    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xf, 0xf, false));   // row_half_mirror
-    x = op(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xf, 0xf, false));   // row_mirror
-    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 16);
-    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
-    return op(op(r0, r1), op(r2, r3));
-}
-__device__ __forceinline__ uint32_t tpc_wave_min(uint32_t x) { return tpc_wave_reduce(x, [](uint32_t a, uint32_t b) { return a < b ? a : b; }); }
-__device__ __forceinline__ uint32_t tpc_wave_xor(uint32_t x) { return tpc_wave_reduce(x, [](uint32_t a, uint32_t b) { return a ^ b; }); }
-__device__ __forceinline__ uint32_t tpc_wave_add(uint32_t x) { return tpc_wave_reduce(x, [](uint32_t a, uint32_t b) { return a + b; }); }
 
 // the soft input of a cell: one multiplication, one addition, never fused
 __device__ __forceinline__ float tpc_soft(float r, float alpha, float W)
@@ -94,16 +74,16 @@ __device__ __forceinline__ tpc_word_result tpc_word(const int lane, const int n,
                                                     const float beta, const float clip, const uint16_t *COL, const uint16_t *POS, const float *RR,
                                                     float *WW, uint8_t *DB, uint32_t *MC)
 {
-    uint32_t key[TPC_SLOTS];                                   // the bits of |R| of the positions not yet taken, all ones otherwise
-    float Rv[TPC_SLOTS];
+    uint32_t key[CHASE_SLOTS];                                 // the bits of |R| of the positions not yet taken, all ones otherwise
+    float Rv[CHASE_SLOTS];
     uint32_t err = 0, s0 = 0;                                  // bit k: slot k of this lane
 #pragma unroll
-    for (int k = 0; k < TPC_SLOTS; k++) {
+    for (int k = 0; k < CHASE_SLOTS; k++) {
         key[k] = ~0u;
         Rv[k] = 0.0f;
     }
 #pragma unroll
-    for (int k = 0; k < TPC_SLOTS; k++) {
+    for (int k = 0; k < CHASE_SLOTS; k++) {
         if (64 * k >= n) break;                                // wave-uniform: a slot no position falls into
         const int j = 64 * k + lane;
         const bool in = j < n;
@@ -115,82 +95,30 @@ __device__ __forceinline__ tpc_word_result tpc_word(const int lane, const int n,
         s0 ^= e ? (uint32_t)COL[jj] : 0u;
         if (in) MC[j] = ~0u;                                   // no competitor yet
     }
-    s0 = tpc_wave_xor(s0);
+    s0 = fec_wave_xor(s0);
 
-    // the p least reliable positions: wave-uniform position, column and |R|
-    uint32_t lp[TPC_P], lc[TPC_P];
-    float la[TPC_P];
-#pragma unroll
-    for (int i = 0; i < TPC_P; i++) {
-        lp[i] = TPC_NONE;
-        lc[i] = 0;
-        la[i] = 0.0f;
-        if (i < p) {                                           // wave-uniform; p <= n: a position is left
-            uint32_t m = key[0];
-#pragma unroll
-            for (int k = 1; k < TPC_SLOTS; k++) m = min(m, key[k]);
-            m = tpc_wave_min(m);
-            uint32_t at = TPC_NONE;
-#pragma unroll
-            for (int k = TPC_SLOTS - 1; k >= 0; k--) at = key[k] == m ? (uint32_t)(64 * k + lane) : at;
-            lp[i] = tpc_wave_min(at);
-            la[i] = __uint_as_float(m);
-            lc[i] = COL[lp[i]];
-#pragma unroll
-            for (int k = 0; k < TPC_SLOTS; k++) key[k] = (uint32_t)(64 * k + lane) == lp[i] ? ~0u : key[k];
-        }
-    }
-
-    // lane T: test pattern T
-    const uint32_t T = (uint32_t)lane;
-    uint32_t s = s0;
-#pragma unroll
-    for (int i = 0; i < TPC_P; i++) s ^= (T >> i) & 1u ? lc[i] : 0u;
-    const uint32_t v = s ? (uint32_t)POS[s] : TPC_NONE;        // s < 2^r: a xor of columns
-    const bool cand = T < (1u << p) && (s == 0 || v != TPC_NONE);
-    float metric = 0.0f;
-    bool cancelled = false;
-#pragma unroll
-    for (int i = 0; i < TPC_P; i++) {                          // x + (+0) = x for x >= 0: the predicated add is the specified sum
-        const bool in = (T >> i) & 1u, hit = in && lp[i] == v;
-        metric = metric + (in && !hit ? la[i] : 0.0f);
-        cancelled |= hit;
-    }
-    {
+    // the winner D; |R_v| of a syndrome position as the lane that owns v formed it
+    const chase_pick c = chase_front(key, s0, n, p, lane, COL, POS, [&](uint32_t v) {
         const int at = base + (int)min(v, (uint32_t)n - 1u) * stride;
-        const float av = fabsf(tpc_soft(RR[at], alpha, WW[at]));   // |R_v| as the lane that owns v formed it
-        metric = metric + (v != TPC_NONE && !cancelled ? av : 0.0f);
-    }
-    const uint32_t mine = cand ? __float_as_uint(metric) : ~0u, best = tpc_wave_min(mine);   // by (metric, T)
+        return fabsf(tpc_soft(RR[at], alpha, WW[at]));
+    });
+    const uint32_t T = c.T, v = c.v, Tw = c.Tw, vw = c.vw, mine = c.mine, best = c.best;
 
     tpc_word_result res = {2, 0, 0};
-    uint32_t flip = 0;                                         // bit k: slot k of this lane is flipped
     if (best != ~0u) {                                         // wave-uniform
-        const uint32_t Tw = tpc_wave_min(mine == best ? T : TPC_NONE), vw = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)Tw);
-        int nflip = 0;
-#pragma unroll
-        for (int k = 0; k < TPC_SLOTS; k++) {
-            if (64 * k >= n) break;
-            const uint32_t j = (uint32_t)(64 * k + lane);
-            uint32_t f = vw == j;                              // the symmetric difference of F_D and {v_D}
-#pragma unroll
-            for (int i = 0; i < TPC_P; i++) f ^= (uint32_t)(((Tw >> i) & 1u) && lp[i] == j);
-            flip |= f << k;
-            nflip += __popcll(__ballot(f != 0));
-        }
-        res.status = nflip ? 1 : 0;
+        res.status = c.nflip ? 1 : 0;
         // the competitors: where this lane's flips and D's differ.  Position lp[i] is flipped by T iff bit i of T xor (v == lp[i]); a v outside
         // the list is flipped by its own candidate alone
         __builtin_amdgcn_wave_barrier();
-        if (cand) {
-            bool v_listed = v == TPC_NONE, vw_listed = vw == TPC_NONE;
+        if (c.cand) {
+            bool v_listed = v == CHASE_NONE, vw_listed = vw == CHASE_NONE;
 #pragma unroll
-            for (int i = 0; i < TPC_P; i++) {
+            for (int i = 0; i < CHASE_P; i++) {
                 if (i < p) {
-                    const uint32_t mt = ((T >> i) & 1u) ^ (uint32_t)(v == lp[i]), md = ((Tw >> i) & 1u) ^ (uint32_t)(vw == lp[i]);
-                    if (mt != md) atomicMin(&MC[lp[i]], mine);
-                    v_listed |= v == lp[i];
-                    vw_listed |= vw == lp[i];
+                    const uint32_t mt = ((T >> i) & 1u) ^ (uint32_t)(v == c.lp[i]), md = ((Tw >> i) & 1u) ^ (uint32_t)(vw == c.lp[i]);
+                    if (mt != md) atomicMin(&MC[c.lp[i]], mine);
+                    v_listed |= v == c.lp[i];
+                    vw_listed |= vw == c.lp[i];
                 }
             }
             if (v != vw) {
@@ -200,10 +128,10 @@ __device__ __forceinline__ tpc_word_result tpc_word(const int lane, const int n,
         }
         __builtin_amdgcn_wave_barrier();
     }
-    err ^= flip;                                               // d
+    err ^= c.flip;                                             // d
     const float mD = __uint_as_float(best);
 #pragma unroll
-    for (int k = 0; k < TPC_SLOTS; k++) {
+    for (int k = 0; k < CHASE_SLOTS; k++) {
         if (64 * k >= n) break;
         const int j = 64 * k + lane;
         const bool in = j < n, d = (err >> k) & 1u;
@@ -227,7 +155,7 @@ __device__ __forceinline__ tpc_word_result tpc_word(const int lane, const int n,
 }
 
 template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void tpc_kernel(const tpc_args A, const tpc_table tab1, const tpc_table tab2, const float *__restrict__ llr,
+__global__ __launch_bounds__(64 * WAVES) void tpc_kernel(const tpc_args A, const fec_cols tab1, const fec_cols tab2, const float *__restrict__ llr,
                                                          const int8_t *__restrict__ bits, const float *__restrict__ scale,
                                                          int32_t *__restrict__ out, float *__restrict__ llr_out, int8_t *__restrict__ bits_out,
                                                          float *__restrict__ ext, int32_t *__restrict__ half_err)
@@ -243,7 +171,7 @@ __global__ __launch_bounds__(64 * WAVES) void tpc_kernel(const tpc_args A, const
     uint16_t *COL1 = reinterpret_cast<uint16_t *>(DB + (cells + 3) / 4 * 4), *COL2 = COL1 + n1;
     uint16_t *POS1 = COL1 + (n1 + n2 + 1) / 2 * 2, *POS2 = POS1 + (1 << A.r1);
 
-    for (int s = tid; s < (1 << A.r1) + (1 << A.r2); s += NT) POS1[s] = (uint16_t)TPC_NONE;
+    for (int s = tid; s < (1 << A.r1) + (1 << A.r2); s += NT) POS1[s] = (uint16_t)CHASE_NONE;
     __syncthreads();
     for (int j = tid; j < n1; j += NT) {                       // the columns are distinct: no two threads write one entry
         COL1[j] = tab1.col[j];
@@ -269,8 +197,8 @@ __global__ __launch_bounds__(64 * WAVES) void tpc_kernel(const tpc_args A, const
             WW[at] = 0.0f;
             DB[at] = (uint8_t)b;
         });
-        pre = (int)tpc_wave_add((uint32_t)pre);
-        erased = (int)tpc_wave_add((uint32_t)erased);
+        pre = (int)fec_wave_add((uint32_t)pre);
+        erased = (int)fec_wave_add((uint32_t)erased);
         if (lane == 0) {
             atomicAdd(&CNT[0], pre);
             atomicAdd(&CNT[1], erased);
@@ -307,7 +235,7 @@ __global__ __launch_bounds__(64 * WAVES) void tpc_kernel(const tpc_args A, const
                 const int base = colwise ? wd * ns : wd, stride = colwise ? 1 : ns;
                 uint32_t syn = 0;
 #pragma unroll
-                for (int k = 0; k < TPC_SLOTS; k++) {
+                for (int k = 0; k < CHASE_SLOTS; k++) {
                     if (64 * k >= olen) break;
                     const int j = 64 * k + lane;
                     const bool in = j < olen;
@@ -315,7 +243,7 @@ __global__ __launch_bounds__(64 * WAVES) void tpc_kernel(const tpc_args A, const
                     const uint32_t d = in ? (uint32_t)DB[base + jj * stride] >> 1 : 0u;
                     syn ^= d ? (uint32_t)OCOL[jj] : 0u;
                 }
-                bad |= tpc_wave_xor(syn) != 0;
+                bad |= fec_wave_xor(syn) != 0;
             }
             const int go_on = __syncthreads_or(bad);
             weight = *WT;
@@ -342,7 +270,7 @@ __global__ __launch_bounds__(64 * WAVES) void tpc_kernel(const tpc_args A, const
             }
             if (ext) ext[sbase + j] = WW[at];
         }
-        pay = (int)tpc_wave_add((uint32_t)pay);
+        pay = (int)fec_wave_add((uint32_t)pay);
         if (lane == 0) atomicAdd(&CNT[2], pay);
         __syncthreads();
         if (tid < 8) {
@@ -372,9 +300,8 @@ extern "C" int vaeq_tpc_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64
     using namespace vaeq;
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!cols1_host || !cols2_host || !llr || !bits || !alpha_host || !beta_host || !out || !llr_out != !bits_out) return VAEQ_ERR_NULL;
-    if (R < 0 || C < 1 || N < 1 || N > 0x3fffffff || w < 1 || w > LDPC_W || t0 < 0 || t0 > N || !tpc_dims_ok(n1, r1, n2, r2) || p < 0 ||
-        p > TPC_P || p > n1 || p > n2 || iters < 1 || iters > TPC_ITERS || !(clip > 0.0f) || !(clip <= 0x1p96f) || K1 < 1 || K1 > n1 || K2 < 1 ||
-        K2 > n2)
+    if (!fec_frame_ok(R, C, N, w, t0) || !tpc_dims_ok(n1, r1, n2, r2) || p < 0 || p > CHASE_P || p > n1 || p > n2 || iters < 1 || iters > TPC_ITERS ||
+        !(clip > 0.0f) || !(clip <= 0x1p96f) || K1 < 1 || K1 > n1 || K2 < 1 || K2 > n2)
         return VAEQ_ERR_SHAPE;
     tpc_args A = {(long long)N, (long long)t0, (long long)R * C, (int)C, (int)w, (int)n1, (int)r1, (int)n2, (int)r2, (int)p, (int)iters, (int)K1,
                   (int)K2, clip, {}, {}};
@@ -384,21 +311,11 @@ extern "C" int vaeq_tpc_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64
         if (!(A.alpha[h] >= 0.0f && A.alpha[h] <= 16.0f) || !(A.beta[h] >= 0.0f && A.beta[h] <= 3.402823466e38f)) return VAEQ_ERR_SHAPE;
     }
     const int64_t n = (int64_t)n1 * n2;                        // at most 2^16: C n stays below 2^47
-    if (t0 * w + (int64_t)C * n > N * w || (int64_t)R * C > 0x7fffffff || (llr_out && (int64_t)C * n > 0x3fffffff)) return VAEQ_ERR_SHAPE;
+    if (!fec_fit_ok(false, C, n, w, t0, N) || (int64_t)R * C > 0x7fffffff || (llr_out && (int64_t)C * n > 0x3fffffff)) return VAEQ_ERR_SHAPE;
     const int64_t lds = tpc_state_bytes(n1, r1, n2, r2);
     if (lds > TPC_LDS_MAX) return VAEQ_ERR_LDS;
-    tpc_table tab[2] = {};
-    for (int which = 0; which < 2; which++) {                  // distinct, non-zero, below 2^r
-        const int32_t *cols = which ? cols2_host : cols1_host;
-        const int len = which ? n2 : n1, r = which ? r2 : r1;
-        bool seen[1 << TPC_R] = {};
-        for (int j = 0; j < len; j++) {
-            const int32_t c = cols[j];
-            if (c < 1 || c >= (1 << r) || seen[c]) return VAEQ_ERR_SHAPE;
-            seen[c] = true;
-            tab[which].col[j] = (uint16_t)c;
-        }
-    }
+    fec_cols tab[2];
+    if (!fec_cols_pack(cols1_host, n1, r1, &tab[0]) || !fec_cols_pack(cols2_host, n2, r2, &tab[1])) return VAEQ_ERR_SHAPE;
     const dim3 grid((unsigned)(A.blocks < TPC_GRID ? A.blocks : TPC_GRID));
     const bool big = tpc_waves(n1, n2) == TPC_WAVES_BIG;
     return launch(big ? tpc_kernel<TPC_WAVES_BIG> : tpc_kernel<TPC_WAVES_SMALL>, grid, dim3(64 * (big ? TPC_WAVES_BIG : TPC_WAVES_SMALL)),
