@@ -180,15 +180,15 @@ def unrotate(LI, LQ, h, S):
     return [(LI, LQ), (S - LI, S - LQ), (LQ, S - LI), (S - LQ, LI)][h]
 
 
-def make_run(seed, N, n, shift, hyp, nu, var, n_err, gain=GAINS):
+def make_run(seed, N, n, shift, hyp, nu, var, n_err, gain=GAINS, P=None):
     """One run whose q AND y carry the TX levels (drawn from the shaped pmf, with n_err wrong symbols planted inside the window, each an axis
     error to a random other level) un-rotated by hyp and rolled by +shift.  q: top posterior 0.55 .. 0.9 at the received level, the rest spread
     over the other levels (none below 1e-3); y: the received level's amplitude plus up to +-0.2 of half the level spacing, times the
-    component's gain.  amp_mean = sum P_i |a_i|."""
+    component's gain.  amp_mean = sum P_i |a_i|.  P: the per-axis pmf where it is not pmf(n, nu) (zero entries allowed)."""
     rng = np.random.default_rng(seed)
     amp = amp_levels(n)
     S, u = n - 1, float(amp[1] - amp[0]) / 2
-    P = pmf(n, nu)
+    P = pmf(n, nu) if P is None else np.asarray(P, np.float64)
     lev = rng.choice(n, size=(2, N), p=P)
     tx = amp[lev].astype(np.float16)
     pool = window(N, shift)[1]

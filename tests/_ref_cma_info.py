@@ -146,10 +146,23 @@ def build_launch(name):
     return xs, ms
 
 
-def float32_deviation(x):
+def _radius_sum(rad, lo):
+    """cma_radius_factor's order in float32: rad[2][len(W_c)] radii of the window that starts at index lo; thread t adds its indices t, t + 256, ...
+    in turn, both polarisations of an index one after the other, then the threads are added."""
+    f = np.float32
+    per = np.zeros(256, f)
+    for i in range(rad.shape[-1]):
+        t = (lo + i) % 256
+        per[t] = f(f(per[t] + rad[0, i]) + rad[1, i])
+    return per.sum(dtype=f)
+
+
+def float32_deviation(x, ordered=False):
     """What the float32 format costs: the kernel's operation order (fac from float32 sums of float32 radii, the scaled sample, the soft demapper's
     exponent, a log-sum-exp per bit-wise set around its own maximum, per-symbol terms, mean) evaluated in numpy float32 under the model's hypothesis,
-    against the float64 model.  -> largest |AIR or GMI deviation| of the run in bit."""
+    against the float64 model.  ordered: the radii are summed per thread at stride 256 and then over the threads (the kernel's documented order:
+    what decides fac at short windows) and not by numpy's pairwise sum.  -> largest |AIR or GMI deviation| of the run in bit, None where
+    nothing is kept."""
     f = np.float32
     n, S = x["n"], x["n"] - 1
     b = int(round(np.log2(n)))
@@ -158,8 +171,11 @@ def float32_deviation(x):
     ya = E.align(np.asarray(x["y"], f), x["shift_c"], x["r_c"])
     W = window_c(N, x["shift_c"])
     t = np.asarray(x["tx"], f)[..., W]
-    st = np.sqrt((t[:, 0] * t[:, 0] + t[:, 1] * t[:, 1]).astype(f)).astype(f).sum(dtype=f)
-    sy = np.sqrt((ya[:, 0, W] * ya[:, 0, W] + ya[:, 1, W] * ya[:, 1, W]).astype(f)).astype(f).sum(dtype=f)
+    rt = np.sqrt((t[:, 0] * t[:, 0] + t[:, 1] * t[:, 1]).astype(f)).astype(f)
+    ry = np.sqrt((ya[:, 0, W] * ya[:, 0, W] + ya[:, 1, W] * ya[:, 1, W]).astype(f)).astype(f)
+    st, sy = (_radius_sum(rt, W.start), _radius_sum(ry, W.start)) if ordered else (rt.sum(dtype=f), ry.sum(dtype=f))
+    if sy == 0 or not m["kept"].any():
+        return None
     yn = ya.copy()
     yn[..., W] = (yn[..., W] * f(st / sy)).astype(f)
     amp, var, nusc, l2e = x["amp"].astype(f), x["var"].astype(f), f(x["nu_sc"]), f(1.4426950408889634)

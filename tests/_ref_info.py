@@ -119,7 +119,7 @@ def info_q(q, tx, P, shift, r, batch_len=None):
     """q-mode: q[2][2n][N] as stored (float32 values, evaluated in float64), tx[2][2][N], P[n], shift[2], r."""
     n = len(P)
     N = q.shape[-1]
-    lev = E.window(E.tx_levels(tx, n), shift, batch_len)
+    lev = E.window(tx_levels(tx, n), shift, batch_len)
     qa = _kept(np.asarray(q, np.float64), shift, r, batch_len).reshape(2, 2, n, -1)
     return _figures(qa, False, lev, P, n)
 
@@ -133,9 +133,14 @@ def info_y(y, tx, P, amp, nu_sc, var, shift, r, batch_len=None):
     z = -(y[:, :, None, :] - a[None, None, :, None]) ** 2 / (2 * np.asarray(var, np.float64)[:, None, None, None]) \
         - float(nu_sc) * (a ** 2)[None, None, :, None]
     z = z * np.log2(np.e)                                                     # [2][2][n][N], log2 of the unnormalised posterior
-    lev = E.window(E.tx_levels(tx, n), shift, batch_len)
+    lev = E.window(tx_levels(tx, n), shift, batch_len)
     za = _kept(z.reshape(2, 2 * n, -1), shift, r, batch_len).reshape(2, 2, n, -1)
     return _figures(za, True, lev, P, n)
+
+
+def tx_levels(tx, n):
+    """_ref_epilogue.tx_levels with info_tx_level's clamp to 0 .. n - 1 (a TX sample beyond the outer level is the outer level)."""
+    return np.clip(E.tx_levels(tx, n), 0, n - 1)
 
 
 # ------------------------------------------------------------------ inputs
@@ -160,14 +165,15 @@ def channel(seq, r, shift):
     return np.stack([np.roll(s[0], int(d[0]), axis=-1), np.roll(s[1], int(d[1]), axis=-1)])
 
 
-def make_run(seed, N, n, shift, r, hyp, batch_len, nu, var, n_err):
+def make_run(seed, N, n, shift, r, hyp, batch_len, nu, var, n_err, P=None):
     """One run whose q AND y carry the TX levels (with n_err[p] wrong symbols in polarisation p, each axis error to a random other level)
     under hypothesis hyp, rolled by shift and exchanged by r.  q: top posterior 0.55 .. 0.9 at the received level, the rest spread
-    over the other levels (none below 1e-3); y: the received level's amplitude plus up to a fifth of half the level spacing."""
+    over the other levels (none below 1e-3); y: the received level's amplitude plus up to a fifth of half the level spacing.  P: the per-axis
+    pmf the TX levels are drawn from and the run reports, where it is not pmf(n, nu) (zero entries allowed)."""
     rng = np.random.default_rng(seed)
     amp = E.amp_levels(n)
     S, u = n - 1, float(amp[1] - amp[0]) / 2
-    P = pmf(n, nu)
+    P = pmf(n, nu) if P is None else np.asarray(P, np.float64)
     lev = rng.choice(n, size=(2, 2, N), p=P)
     tx = amp[lev].astype(np.float16)
     pool = E.kept_indices(N, shift, batch_len)
@@ -242,7 +248,7 @@ def y_mode_float32_deviation(x):
             dd = (y[sp] - amp[i]).astype(f)
             z[sp, :, i] = (-((dd * dd).astype(f) * i2v + f(nusc * f(amp[i] * amp[i]))).astype(f) * l2e).astype(f)
     za = _kept(z.reshape(2, 2 * n, -1), x["shift"], x["r"], x["batch_len"]).reshape(2, 2, n, -1)
-    lev = E.window(E.tx_levels(x["tx"], n), x["shift"], x["batch_len"])
+    lev = E.window(tx_levels(x["tx"], n), x["shift"], x["batch_len"])
     K = za.shape[-1]
     if K == 0:
         return None
