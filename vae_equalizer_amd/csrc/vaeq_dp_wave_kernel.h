@@ -58,14 +58,36 @@
 
 namespace vaeq {
 
-// Sum of a tap-gradient component over the two 32-lane halves, for the half that keeps it: a0 belongs to the taps the lower half owns, a1 to the upper
-// half's; returns a0[lane] + a0[lane ^ 32] in the lower and a1[lane] + a1[lane ^ 32] in the upper half (in either form the lane's own part is one addend and
-// its partner's the other: IEEE addition commutes, the sums are bitwise the same).
-__device__ __forceinline__ float half_sum(float a0, float a1)
+// Sum of a complex tap gradient over the two 32-lane halves, for the half that keeps it, as the 8-byte pair (re, im) the Adam update goes on with: a0
+// belongs to the taps the lower half owns, a1 to the upper half's; returns a0[lane] + a0[lane ^ 32] in the lower and a1[lane] + a1[lane ^ 32] in the upper
+// half (the lane's own part is one addend and its partner's the other in either half: IEEE addition commutes, the sums are bitwise the same).  Per
+// component, v_permlane32_swap exchanges a0's upper half with a1's lower half: the lower lanes then hold (a0 own, a0 partner), the upper lanes
+// (a1 partner, a1 own).  The two swaps leave the addends in two aligned register pairs, so the sum is ONE v_pk_add_f32 and nothing is moved (left to
+// itself the optimiser pairs the four reals of a lane by what the update does with them first, and re-pairs them with v_mov before and after)
+__device__ __forceinline__ v2f half_sum2(v2f a0, v2f a1)
 {
-    // swap a0's upper half with a1's lower half: the lower lanes then hold (a0 own, a0 partner), the upper lanes (a1 partner, a1 own)
-    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a0), __builtin_bit_cast(unsigned, a1), false, false);
-    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+    const float a0x = a0.x, a0y = a0.y, a1x = a1.x, a1y = a1.y;   // (scalars first: __builtin_bit_cast of a vector element reads the vector's first bytes)
+    const auto rx = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a0x), __builtin_bit_cast(unsigned, a1x), false, false);
+    const auto ry = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a0y), __builtin_bit_cast(unsigned, a1y), false, false);
+    v2f r0 = {__builtin_bit_cast(float, (unsigned)rx[0]), __builtin_bit_cast(float, (unsigned)ry[0])};
+    v2f r1 = {__builtin_bit_cast(float, (unsigned)rx[1]), __builtin_bit_cast(float, (unsigned)ry[1])};
+    asm volatile("" : "+v"(r0), "+v"(r1));                 // pin: the addends stay 8-byte registers
+    return r0 + r1;
+}
+
+// adam_update_fast (vaeq_common.h) on the real and the imaginary part of a tap at once: the same operations with the same roundings, element by element
+// (what the scalar form contracts is spelled out), on pairs that are born aligned -- gradient, moments and tap each arrive as (re, im).  The optimiser
+// packs the scalar form too, but by operation: (g, v) x (0.001, 0.999), (g_re, g_im) - (m_re, m_im), ... -- two or three v_mov per packed instruction.
+__device__ __forceinline__ void adam_update_fast2(v2f &p, v2f &m, v2f &v, v2f g, float step_size, float rbc2s)
+{
+    m = __builtin_elementwise_fma(g - m, v2f{0.1f, 0.1f}, m);
+    v = v * 0.999f;
+    v = __builtin_elementwise_fma(0.001f * g, g, v);
+    // (the denominators as two scalar fmas, between the transcendentals that are scalar anyway: packed, the uniform rbc2s would be kept as a (rbc2s, rbc2s)
+    //  register pair from the first update of a step to the last, through the kernel's register peak)
+    const float d0 = fmaf(__builtin_amdgcn_sqrtf(v.x), rbc2s, 1e-8f), d1 = fmaf(__builtin_amdgcn_sqrtf(v.y), rbc2s, 1e-8f);
+    const v2f rd = {__builtin_amdgcn_rcpf(d0), __builtin_amdgcn_rcpf(d1)};
+    p = __builtin_elementwise_fma(-step_size * m, rd, p);
 }
 
 struct WaveLayout {
@@ -562,8 +584,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     constexpr bool PIPE = VAEQ_PIPE && FIXL;               // run-time layouts keep more addresses live: there one operand set,
     constexpr bool WIDE = FIXL;                            // ... 8 accumulator chains and one chi at a time in dL/dU (fits the register file)
     // B100: the baked B = 100 kernel on one wave, the shape that is measured step by step and whose bits are pinned (tests/test_dp_wave_bits_gpu.py).
-    // It alone takes six forms; every other instantiation keeps the plain one, instruction for instruction:
-    //  * the halves of the two tap gradients meet on v_permlane32_swap (half_sum: one swap + one add per kept value) instead of 16 ds_bpermute_b32
+    // It alone takes seven forms; every other instantiation keeps the plain one, instruction for instruction:
+    //  * the halves of the two tap gradients meet on v_permlane32_swap (half_sum2: one swap per kept value, one packed add per pair) instead of 16 ds_bpermute_b32
     //    through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms (profiles/r04/kernel_variants_ab.txt)
     //  * the next window's prefetch is issued without a branch around it (the launch's very last step fetches with every lane out of range: zeros, no
     //    memory access).  Behind the branch the four loads fed a phi: the backend copied their results right after the issue, behind
@@ -581,6 +603,10 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     //  * (M = 25) the FIR, dL/dU and the D convolution carry the cells that consecutive stages share in registers (CellCarry, pipe2_carry): 12 instead of
     //    14, 24 instead of 28 and 6 instead of 8 per-lane LDS reads per stage, every output's chain in its old order
     //    (profiles/r08/cell_carry_bound.txt, profiles/r08/kernel_variants_ab.txt)
+    //  * the step's five wave sums and two variance scans run as interleaved DPP chains whose masked steps are one instruction each (vaeq_wave.h: *_dpp_keep),
+    //    the half combines and both Adam updates work on (re, im) register pairs (half_sum2, adam_update_fast2), and every lane runs the updates, only what
+    //    leaves the lane being masked: 101 of the step's 1621 straight-line vector instructions were moves, selects and zeros for this
+    //    (profiles/r09/kernel_variants_ab.txt)
     constexpr bool B100 = BT == 100 && NW == 1;
     constexpr bool CARRY = B100 && M == 25 && PIPE && WIDE;
     constexpr int QAUX = B100 ? 2 : 0;                         // cache policy of the q stores
@@ -633,16 +659,19 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
         ownr = TapPairMap::owns(lane, M);
     }
     // Adam moments of the taps this lane owns live in LDS, one 64-lane row per quantity (touched twice per step; 16 VGPRs freed):
-    // rows 0-7: m, v of W[o=oc][p][k=tj] (re, im); rows 8-15: m, v of h[chi=oc][nu][.][j=tj]
+    // rows 0-7: m, v of W[o=oc][p][k=tj] (re, im); rows 8-15: m, v of h[chi=oc][nu][.][j=tj]; within each block of four rows [im][p]
     float *MOM = reinterpret_cast<float *>(sm + lay.MOM) + lane;
-#define mWr(p) MOM[(0 + (p)) * 64]
-#define mWi(p) MOM[(2 + (p)) * 64]
-#define vWr(p) MOM[(4 + (p)) * 64]
-#define vWi(p) MOM[(6 + (p)) * 64]
-#define mHr(p) MOM[(8 + (p)) * 64]
-#define mHi(p) MOM[(10 + (p)) * 64]
-#define vHr(p) MOM[(12 + (p)) * 64]
-#define vHi(p) MOM[(14 + (p)) * 64]
+    // (B = 100: the rows of a (re, im) pair are neighbours -- rows 2 p, 2 p + 1 of each block of four -- so that the two reads the backend fuses into one
+    //  ds_read2st64_b32 are the pair the update works on, adam_update_fast2)
+#define VAEQ_MOM(base, im, p) MOM[((base) + (BT == 100 && NW == 1 ? 2 * (p) + (im) : 2 * (im) + (p))) * 64]
+#define mWr(p) VAEQ_MOM(0, 0, p)
+#define mWi(p) VAEQ_MOM(0, 1, p)
+#define vWr(p) VAEQ_MOM(4, 0, p)
+#define vWi(p) VAEQ_MOM(4, 1, p)
+#define mHr(p) VAEQ_MOM(8, 0, p)
+#define mHi(p) VAEQ_MOM(8, 1, p)
+#define vHr(p) VAEQ_MOM(12, 0, p)
+#define vHi(p) VAEQ_MOM(12, 1, p)
     if (ownr) {
 #pragma unroll
         for (int p = 0; p < 2; p++) {
@@ -877,8 +906,17 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             // exclusive prefix sums PSv[nu][n], n = 0..B  (VS[nu][j] = PSv[hi+1] - PSv[lo])
             {
                 float inc[2];
+                if constexpr (B100) {
+                    // both scans at once, their masked steps one instruction each (wave_incl_scan2_dpp_keep).  No input is -0, so no partial sum is: vv is
+                    // +0 on a lane without the symbol and elsewhere the sum of two m2 = sum_i (q_i d_i) d_i, every term of which is >= +0 (q_i = exp2(.) rcp(.)
+                    // of positives is >= +0, (q d) d carries d's sign twice) added from +0 -- a sum of values >= +0 is >= +0
+                    inc[0] = vv[0][0] + vv[0][1];
+                    inc[1] = vv[1][0] + vv[1][1];
+                    wave_incl_scan2_dpp_keep(inc[0], inc[1]);
+                } else {
 #pragma unroll
-                for (int o = 0; o < 2; o++) inc[o] = wave_incl_scan_dpp(vv[o][0] + vv[o][1]);
+                    for (int o = 0; o < 2; o++) inc[o] = wave_incl_scan_dpp(vv[o][0] + vv[o][1]);
+                }
                 if constexpr (NW > 1) {                        // add the totals of the waves below (fixed order)
                     if (lane == 63) { RED[wv] = inc[0]; RED[NW + wv] = inc[1]; }
                     sync_lds<NW>();
@@ -1103,10 +1141,19 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                         }
                 }
             }
-            se0 = wave_sum_dpp(se0);
-            se1 = wave_sum_dpp(se1);
-            klsum = wave_sum_dpp(klsum);
-            if constexpr (NW > 1) {                            // totals over the run's waves, same order in every wave
+            float hv0 = 0.f, hv1 = 0.f;                        // B = 100: sum_{nu,j} |h[chi]|^2 VS
+            if constexpr (B100) {
+                // the step's five wave sums as interleaved chains, their masked steps one instruction each (wave_sum5_dpp_keep): the same additions in
+                // the same order as wave_sum_dpp, for every input
+                float ws[5] = {wave_sum_first(se0), wave_sum_first(se1), wave_sum_first(klsum), wave_sum_first(hq0, vsl), wave_sum_first(hq1, vsl)};
+                wave_sum5_dpp_keep(ws);
+                se0 = ws[0]; se1 = ws[1]; klsum = ws[2]; hv0 = ws[3]; hv1 = ws[4];
+            } else {
+                se0 = wave_sum_dpp(se0);
+                se1 = wave_sum_dpp(se1);
+                klsum = wave_sum_dpp(klsum);
+            }
+            if constexpr (NW > 1) {                          // totals over the run's waves, same order in every wave
                 if (lane == 0) { RED[16 + wv] = se0; RED[16 + NW + wv] = se1; RED[16 + 2 * NW + wv] = klsum; }
                 sync_lds<NW>();
                 se0 = RED[16]; se1 = RED[16 + NW]; klsum = RED[16 + 2 * NW];
@@ -1114,7 +1161,14 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 for (int w = 1; w < NW; w++) { se0 += RED[16 + w]; se1 += RED[16 + NW + w]; klsum += RED[16 + 2 * NW + w]; }
             }
             // C[chi] = sum|e|^2 + sum_{nu,j} |h|^2 VS   (lanes (j, nu) hold one term each for both chi; hq, vsl were read before the D loop)
-            const float C0 = se0 + wave_sum_dpp(hq0 * vsl), C1 = se1 + wave_sum_dpp(hq1 * vsl);
+            float C0, C1;
+            if constexpr (B100) {
+                C0 = se0 + hv0;
+                C1 = se1 + hv1;
+            } else {
+                C0 = se0 + wave_sum_dpp(hq0 * vsl);
+                C1 = se1 + wave_sum_dpp(hq1 * vsl);
+            }
             // C is uniform: hardware reciprocal / log2 (1 ulp: 6e-8 on the gradients' common scale, 1e-7 relative on the ELBO) instead of the IEEE
             // division and logf expansions (~60 instructions per step that every lane would execute for lane 0's two stores)
             const float gC0 = (float)nm * __builtin_amdgcn_rcpf(C0), gC1 = (float)nm * __builtin_amdgcn_rcpf(C1);
@@ -1128,6 +1182,8 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             }
             // prefix sums over j of H2[nu][j] = sum_chi gC[chi] |h[chi,nu,j]|^2  -> G_V by two lookups per symbol
             {
+                // (this scan keeps the form that adds a masked zero, at B = 100 too: gC = nm / C has the sign of C = sum |e|^2 + sum |h|^2 VS, and VS is a
+                //  DIFFERENCE of two scanned prefix sums -- nothing in the code rules out a C < 0, whose gC |h|^2 is -0 for a tap that is 0)
                 const float inc = half_incl_scan_dpp(gC0 * hq0 + gC1 * hq1);   // inclusive scan within each 32-lane half
                 if (owner) PSh[half * MP + tk + 1] = inc;
                 if (tk == 0) PSh[half * MP] = 0.f;
@@ -1151,7 +1207,13 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 // update after the loop starts with fewer exposed LDS round trips (wave 0 only)
                 float2 ph_h[2] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f)};
                 float ph_vs[2] = {0.f, 0.f};                   // (the moments stay in LDS until the update: this phase cannot spare eight more registers)
-                if (NW == 1 && ownr) {
+                // B = 100: EVERY lane reads and updates the cells its (oc, tj) names, and only what leaves the lane is masked (the tap's write to LDS, the
+                // state and debug stores): values defined on all lanes need no zeros for the lanes that own no tap (a v_mov 0 per value and step in front
+                // of the exec-masked update).  A lane without a tap reads cells inside the LDS allocation (tj <= M + 1: at most two cells past a row) and
+                // updates the moments of its OWN column of MOM, which nothing else reads: that column is never initialised, so such a lane runs Adam on
+                // whatever the LDS holds (NaN included) and the result is discarded with it.  The bound on tj is TapPairMap's: M = 25 only
+                static_assert(!B100 || TP, "B = 100: every lane updates -- the cells a lane without a tap names are inside the LDS allocation for TapPairMap (M = 25) only");
+                if (B100 || (NW == 1 && ownr)) {
 #pragma unroll
                     for (int v = 0; v < 2; v++) {
                         ph_h[v] = Ht[(oc * 2 + v) * MP + tj];
@@ -1220,19 +1282,37 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                     }
                 }
                 VAEQ_XSTAMP(1);
-                float2 acc[2][2];
-#pragma unroll
-                for (int chi = 0; chi < 2; chi++)
-#pragma unroll
-                    for (int v = 0; v < 2; v++) acc[chi][v] = cfinc(ca[chi][v]);             // e * conj(U)
-                // combine the two halves; lane (j, half) keeps chi = half
                 if constexpr (B100) {
+                    // the halves meet as (re, im) pairs and the update stays on pairs (half_sum2, adam_update_fast2); every lane (see ph_h above)
+                    v2f sum[2];
 #pragma unroll
-                    for (int v = 0; v < 2; v++) {               // (both entries get the kept sum: the selects below pick either)
-                        acc[0][v].x = acc[1][v].x = half_sum(acc[0][v].x, acc[1][v].x);
-                        acc[0][v].y = acc[1][v].y = half_sum(acc[0][v].y, acc[1][v].y);
+                    for (int v = 0; v < 2; v++) sum[v] = half_sum2(cfinc2(ca[0][v]), cfinc2(ca[1][v]));   // e * conj(U) of the kept chi
+                    VAEQ_XSTAMP(2);
+                    const float g = oc ? gC1 : gC0;
+#pragma unroll
+                    for (int v = 0; v < 2; v++) {
+                        v2f hh = {ph_h[v].x, ph_h[v].y};
+                        const v2f gh = g * __builtin_elementwise_fma(2.0f * hh, v2f{ph_vs[v], ph_vs[v]}, -2.0f * sum[v]);
+                        if (!a.no_update) {
+                            v2f mo = {mHr(v), mHi(v)}, vo = {vHr(v), vHi(v)};
+                            adam_update_fast2(hh, mo, vo, gh, ssH, bc2s);
+                            mHr(v) = mo.x; mHi(v) = mo.y;
+                            vHr(v) = vo.x; vHi(v) = vo.y;
+                        }
+                        hnew[v] = f2(hh);
+                        // the last step's gradient leaves here (not behind P5, next to dL/dw's): four registers less through P4b, the kernel's register peak
+                        if (a.dbg_gW && ownr && f == a.n_frames - 1 && s == a.steps - 1) {
+                            a.dbg_gh[gbase + ((oc * 2 + v) * 2 + 0) * M + tj] = gh.x;
+                            a.dbg_gh[gbase + ((oc * 2 + v) * 2 + 1) * M + tj] = gh.y;
+                        }
                     }
                 } else {
+                    float2 acc[2][2];
+#pragma unroll
+                    for (int chi = 0; chi < 2; chi++)
+#pragma unroll
+                        for (int v = 0; v < 2; v++) acc[chi][v] = cfinc(ca[chi][v]);             // e * conj(U)
+                    // combine the two halves; lane (j, half) keeps chi = half
 #pragma unroll
                     for (int chi = 0; chi < 2; chi++)
 #pragma unroll
@@ -1240,38 +1320,39 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                             acc[chi][v].x += __shfl_xor(acc[chi][v].x, 32, 64);
                             acc[chi][v].y += __shfl_xor(acc[chi][v].y, 32, 64);
                         }
-                }
-                if constexpr (NW > 1) {                        // waves 1.. hand their partial sums to wave 0 (read after the next barrier)
+                    if constexpr (NW > 1) {                        // waves 1.. hand their partial sums to wave 0 (read after the next barrier)
 #pragma unroll
-                    for (int v = 0; v < 2; v++) {
-                        hacc[v] = half ? acc[1][v] : acc[0][v];
-                        if (wv > 0) {
-                            XG[((wv - 1) * 4 + 2 * v + 0) * 64 + lane] = hacc[v].x;
-                            XG[((wv - 1) * 4 + 2 * v + 1) * 64 + lane] = hacc[v].y;
+                        for (int v = 0; v < 2; v++) {
+                            hacc[v] = half ? acc[1][v] : acc[0][v];
+                            if (wv > 0) {
+                                XG[((wv - 1) * 4 + 2 * v + 0) * 64 + lane] = hacc[v].x;
+                                XG[((wv - 1) * 4 + 2 * v + 1) * 64 + lane] = hacc[v].y;
+                            }
                         }
                     }
-                }
-                VAEQ_XSTAMP(2);
-                if (NW == 1 && ownr) {
-                    const float g = oc ? gC1 : gC0;
+                    VAEQ_XSTAMP(2);
+                    if (NW == 1 && ownr) {
+                        const float g = oc ? gC1 : gC0;
 #pragma unroll
-                    for (int v = 0; v < 2; v++) {
-                        const float2 ac = half ? acc[1][v] : acc[0][v];
-                        const float2 hh = ph_h[v];
-                        const float vs = ph_vs[v];
-                        ghr[v] = g * (-2.0f * ac.x + 2.0f * hh.x * vs);
-                        ghi[v] = g * (-2.0f * ac.y + 2.0f * hh.y * vs);
-                        hnew[v] = hh;
-                        if (!a.no_update) {
-                            adam_update_fast(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
-                            adam_update_fast(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
+                        for (int v = 0; v < 2; v++) {
+                            const float2 ac = half ? acc[1][v] : acc[0][v];
+                            const float2 hh = ph_h[v];
+                            const float vs = ph_vs[v];
+                            ghr[v] = g * (-2.0f * ac.x + 2.0f * hh.x * vs);
+                            ghi[v] = g * (-2.0f * ac.y + 2.0f * hh.y * vs);
+                            hnew[v] = hh;
+                            if (!a.no_update) {
+                                adam_update_fast(hnew[v].x, mHr(v), vHr(v), ghr[v], ssH, bc2s);
+                                adam_update_fast(hnew[v].y, mHi(v), vHi(v), ghi[v], ssH, bc2s);
+                            }
                         }
                     }
                 }
             }
 
-            asm volatile("" : "+v"(hnew[0].x), "+v"(hnew[0].y), "+v"(hnew[1].x), "+v"(hnew[1].y), "+v"(ghr[0]), "+v"(ghr[1]), "+v"(ghi[0]),
-                         "+v"(ghi[1]));                        // pin (see P1)
+            if constexpr (B100) asm volatile("" : "+v"(hnew[0].x), "+v"(hnew[0].y), "+v"(hnew[1].x), "+v"(hnew[1].y));   // pin (see P1)
+            else asm volatile("" : "+v"(hnew[0].x), "+v"(hnew[0].y), "+v"(hnew[1].x), "+v"(hnew[1].y), "+v"(ghr[0]), "+v"(ghr[1]), "+v"(ghi[0]),
+                              "+v"(ghi[1]));
             // prefetch the next window now: the q/y stores of this step were issued half a step ago and have drained, so the wait
             // for these loads at the top of the next step does not also wait for fresh stores (vmcnt retires in order)
             {
@@ -1355,7 +1436,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
             float gwr[2] = {0, 0}, gwi[2] = {0, 0};
             {
                 float pw_w[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, pw_m[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, pw_v[2][2] = {{0.f, 0.f}, {0.f, 0.f}};   // as for Adam(h)
-                if (ownr) {
+                if (B100 || ownr) {                          // (B = 100: every lane, see Adam(h))
 #pragma unroll
                     for (int p = 0; p < 2; p++) {
                         const float *wq = reinterpret_cast<const float *>(&Wt[p * M + tj]) + oc * 2;
@@ -1422,18 +1503,35 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                     }
                 }
                 VAEQ_XSTAMP(5);
-                float2 acc[2][2];
-#pragma unroll
-                for (int o = 0; o < 2; o++)
-#pragma unroll
-                    for (int pp = 0; pp < 2; pp++) acc[o][pp] = cfinc(ca[o][pp]);            // gy * conj(x)
                 if constexpr (B100) {
+                    // as for dL/dh: the halves meet as (re, im) pairs, lane (k, half) keeps o = half, and every lane runs the update on pairs; the tap's and
+                    // the moments' writes to LDS are the owner's alone (a lane without a tap names a cell that another lane owns)
+                    v2f sum[2];
 #pragma unroll
-                    for (int p = 0; p < 2; p++) {               // lane (k, half) keeps o = half (see dL/dh)
-                        acc[0][p].x = acc[1][p].x = half_sum(acc[0][p].x, acc[1][p].x);
-                        acc[0][p].y = acc[1][p].y = half_sum(acc[0][p].y, acc[1][p].y);
+                    for (int p = 0; p < 2; p++) sum[p] = half_sum2(cfinc2(ca[0][p]), cfinc2(ca[1][p]));   // gy * conj(x)
+                    VAEQ_XSTAMP(6);
+#pragma unroll
+                    for (int p = 0; p < 2; p++) {
+                        gwr[p] = sum[p].x;
+                        gwi[p] = sum[p].y;
+                        if (!a.no_update) {
+                            v2f w = {pw_w[p][0], pw_w[p][1]}, mo = {pw_m[p][0], pw_m[p][1]}, vo = {pw_v[p][0], pw_v[p][1]};
+                            adam_update_fast2(w, mo, vo, sum[p], ssW, bc2s);
+                            if (ownr) {
+                                float *wq = reinterpret_cast<float *>(&Wt[p * M + tj]) + oc * 2;
+                                wq[0] = w.x;
+                                wq[1] = w.y;
+                                mWr(p) = mo.x; mWi(p) = mo.y;
+                                vWr(p) = vo.x; vWi(p) = vo.y;
+                            }
+                        }
                     }
                 } else {
+                    float2 acc[2][2];
+#pragma unroll
+                    for (int o = 0; o < 2; o++)
+#pragma unroll
+                        for (int pp = 0; pp < 2; pp++) acc[o][pp] = cfinc(ca[o][pp]);            // gy * conj(x)
 #pragma unroll
                     for (int o = 0; o < 2; o++)
 #pragma unroll
@@ -1441,41 +1539,41 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                             acc[o][p].x += __shfl_xor(acc[o][p].x, 32, 64);
                             acc[o][p].y += __shfl_xor(acc[o][p].y, 32, 64);
                         }
-                }
-                if constexpr (NW > 1) {                        // as for dL/dh: wave 0 adds the other waves' parts after the barrier
+                    if constexpr (NW > 1) {                        // as for dL/dh: wave 0 adds the other waves' parts after the barrier
 #pragma unroll
-                    for (int p = 0; p < 2; p++) {
-                        const float2 ac = half ? acc[1][p] : acc[0][p];
-                        if (wv > 0) {
-                            XG[((wv - 1) * 4 + 2 * p + 0) * 64 + lane] = ac.x;
-                            XG[((wv - 1) * 4 + 2 * p + 1) * 64 + lane] = ac.y;
-                        }
-                    }
-                    sync_lds<NW>();
-                }
-                VAEQ_XSTAMP(6);
-                if (ownr) {
-#pragma unroll
-                    for (int p = 0; p < 2; p++) {
-                        float2 ac = half ? acc[1][p] : acc[0][p];
-                        if constexpr (NW > 1) {
-#pragma unroll
-                            for (int w = 0; w < NW - 1; w++) {
-                                ac.x += XG[(w * 4 + 2 * p + 0) * 64 + lane];
-                                ac.y += XG[(w * 4 + 2 * p + 1) * 64 + lane];
+                        for (int p = 0; p < 2; p++) {
+                            const float2 ac = half ? acc[1][p] : acc[0][p];
+                            if (wv > 0) {
+                                XG[((wv - 1) * 4 + 2 * p + 0) * 64 + lane] = ac.x;
+                                XG[((wv - 1) * 4 + 2 * p + 1) * 64 + lane] = ac.y;
                             }
                         }
-                        gwr[p] = ac.x;
-                        gwi[p] = ac.y;
-                        if (!a.no_update) {
-                            float *wq = reinterpret_cast<float *>(&Wt[p * M + tj]) + oc * 2;
-                            float wr = pw_w[p][0], wi = pw_w[p][1];
-                            adam_update_fast(wr, pw_m[p][0], pw_v[p][0], gwr[p], ssW, bc2s);
-                            adam_update_fast(wi, pw_m[p][1], pw_v[p][1], gwi[p], ssW, bc2s);
-                            wq[0] = wr;
-                            wq[1] = wi;
-                            mWr(p) = pw_m[p][0]; mWi(p) = pw_m[p][1];
-                            vWr(p) = pw_v[p][0]; vWi(p) = pw_v[p][1];
+                        sync_lds<NW>();
+                    }
+                    VAEQ_XSTAMP(6);
+                    if (ownr) {
+#pragma unroll
+                        for (int p = 0; p < 2; p++) {
+                            float2 ac = half ? acc[1][p] : acc[0][p];
+                            if constexpr (NW > 1) {
+#pragma unroll
+                                for (int w = 0; w < NW - 1; w++) {
+                                    ac.x += XG[(w * 4 + 2 * p + 0) * 64 + lane];
+                                    ac.y += XG[(w * 4 + 2 * p + 1) * 64 + lane];
+                                }
+                            }
+                            gwr[p] = ac.x;
+                            gwi[p] = ac.y;
+                            if (!a.no_update) {
+                                float *wq = reinterpret_cast<float *>(&Wt[p * M + tj]) + oc * 2;
+                                float wr = pw_w[p][0], wi = pw_w[p][1];
+                                adam_update_fast(wr, pw_m[p][0], pw_v[p][0], gwr[p], ssW, bc2s);
+                                adam_update_fast(wi, pw_m[p][1], pw_v[p][1], gwi[p], ssW, bc2s);
+                                wq[0] = wr;
+                                wq[1] = wi;
+                                mWr(p) = pw_m[p][0]; mWi(p) = pw_m[p][1];
+                                vWr(p) = pw_v[p][0]; vWi(p) = pw_v[p][1];
+                            }
                         }
                     }
                 }
@@ -1485,8 +1583,10 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
                 for (int p = 0; p < 2; p++) {
                     a.dbg_gW[gbase + (oc * 4 + p) * M + tj] = gwr[p];
                     a.dbg_gW[gbase + (oc * 4 + 2 + p) * M + tj] = gwi[p];
-                    a.dbg_gh[gbase + ((oc * 2 + p) * 2 + 0) * M + tj] = ghr[p];
-                    a.dbg_gh[gbase + ((oc * 2 + p) * 2 + 1) * M + tj] = ghi[p];
+                    if constexpr (!B100) {                     // (B = 100: stored in P4a)
+                        a.dbg_gh[gbase + ((oc * 2 + p) * 2 + 0) * M + tj] = ghr[p];
+                        a.dbg_gh[gbase + ((oc * 2 + p) * 2 + 1) * M + tj] = ghi[p];
+                    }
                 }
             }
             sync_lds<NW>();
@@ -1518,6 +1618,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
         }
     }
     if (gl == 0 && !a.no_update) a.step[run] = step;
+#undef VAEQ_MOM
 #undef mWr
 #undef mWi
 #undef vWr

@@ -267,6 +267,58 @@ __device__ __forceinline__ float wave_incl_scan_dpp(float v)  // inclusive prefi
     return s;
 }
 
+// The same sums and scans with every row- or bank-masked step as ONE instruction, v_add_f32_dpp v, v, v <ctrl> <masks> with the destination tied to the
+// input: a lane the masks switch off keeps v where the forms above compute v + 0 -- from update_dpp(0, ...) the backend makes v_mov_b32 t, 0 +
+// v_mov_b32_dpp t, v + v_add_f32 v, v, t, because it may not fold x + 0 into x (x = -0).  Several independent chains are interleaved in one asm
+// statement: the hazard recognizer does not look inside one, so the two wait states a DPP read of a just-written VGPR needs are spelled out -- the leading
+// s_nop 4 covers whatever wrote the inputs (or, as a VALU instruction, EXEC), and between two steps of a chain stand the other chains' steps (plus s_nop 0 where there is only one other).
+// What FOLLOWS such a statement is the compiler's again: it sees the statement's outputs as written by it and places the wait state that the v_readlane of
+// wave_sum5_dpp_keep needs behind a VALU write of its source (an s_nop 0 or an independent instruction behind the statement, as the listing shows).
+// Used by the baked B = 100 DP kernel alone; every other kernel keeps the forms above.
+#define VAEQ_DPPK(i, ctrl) "v_add_f32_dpp %" #i ", %" #i ", %" #i " " ctrl "\n\t"
+#define VAEQ_DPPK2(ctrl) VAEQ_DPPK(0, ctrl) VAEQ_DPPK(1, ctrl)
+#define VAEQ_DPPK5(ctrl) VAEQ_DPPK2(ctrl) VAEQ_DPPK(2, ctrl) VAEQ_DPPK(3, ctrl) VAEQ_DPPK(4, ctrl)
+#define VAEQ_DPP_FULL " row_mask:0xf bank_mask:0xf"
+// First step of wave_sum_dpp (quad_perm:[1,0,3,2]) on a value / on a product a b.  The caller of wave_sum5_dpp_keep does it: where a product feeds
+// wave_sum_dpp the backend contracts its first addition, v + dpp(v) with v = a b, into fma(a, b, dpp(round(a b))) -- part of the pinned bits, spelled out here.
+__device__ __forceinline__ float wave_sum_first(float v) { return v + dpp_f<0xB1>(v); }
+__device__ __forceinline__ float wave_sum_first(float a, float b) { return __builtin_fmaf(a, b, dpp_f<0xB1>(a * b)); }
+// Steps 2..6 of wave_sum_dpp on five chains at once (v[k]: after wave_sum_first), the sums in v[k] (uniform).  The same additions in the same order
+// as wave_sum_dpp for EVERY input: a row that a masked step switches off is never read again on the way to lane 63 (rows 0 and 2 are read by
+// row_bcast:15 before it, row 1 by row_bcast:31 after it added row 0 into it, and only row 3's last lane leaves).
+__device__ __forceinline__ void wave_sum5_dpp_keep(float (&v)[5])
+{
+    asm("s_nop 4\n\t"
+        VAEQ_DPPK5("quad_perm:[2,3,0,1]" VAEQ_DPP_FULL)
+        VAEQ_DPPK5("row_half_mirror" VAEQ_DPP_FULL)
+        VAEQ_DPPK5("row_mirror" VAEQ_DPP_FULL)
+        VAEQ_DPPK5("row_bcast:15 row_mask:0xa bank_mask:0xf")
+        VAEQ_DPPK5("row_bcast:31 row_mask:0xc bank_mask:0xf")
+        : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]));
+#pragma unroll
+    for (int k = 0; k < 5; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[k]), 63));
+}
+// wave_incl_scan_dpp of two values at once.  A switched-off lane keeps its partial sum s instead of s + 0: the same bits unless s is -0 (-0 + 0 = +0).
+// For inputs that are never -0 (only -0 + -0 is -0) no partial sum is: the caller shows that of its inputs.
+__device__ __forceinline__ void wave_incl_scan2_dpp_keep(float &a, float &b)
+{
+    float s0 = a + dpp_f<0x111>(a), s1 = b + dpp_f<0x111>(b);                  // row_shr:1 .. 3: full masks, as in row_incl_scan_dpp
+    s0 += dpp_f<0x112>(a); s1 += dpp_f<0x112>(b);
+    s0 += dpp_f<0x113>(a); s1 += dpp_f<0x113>(b);
+    asm("s_nop 4\n\t"
+        VAEQ_DPPK2("row_shr:4 row_mask:0xf bank_mask:0xe") "s_nop 0\n\t"
+        VAEQ_DPPK2("row_shr:8 row_mask:0xf bank_mask:0xc") "s_nop 0\n\t"
+        VAEQ_DPPK2("row_bcast:15 row_mask:0xa bank_mask:0xf") "s_nop 0\n\t"
+        VAEQ_DPPK2("row_bcast:31 row_mask:0xc bank_mask:0xf")
+        : "+v"(s0), "+v"(s1));
+    a = s0;
+    b = s1;
+}
+#undef VAEQ_DPPK
+#undef VAEQ_DPPK2
+#undef VAEQ_DPPK5
+#undef VAEQ_DPP_FULL
+
 __device__ __forceinline__ float wave_incl_scan(float v, int lane)                    // inclusive prefix sum over lanes
 {
 #pragma unroll
