@@ -13,8 +13,8 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("VAEQ_LIB") or os.path.join(_PKG, "libvaeq_hip.so")   # VAEQ_LIB: A/B builds of the kernels (tools/build_variant.sh)
-SOURCES = ["vaeq_dp.hip", "vaeq_dp_wave.hip", "vaeq_dp_wave_mw.hip", "vaeq_dp_wave_mw8.hip", "vaeq_dp_wave_bk.hip", "vaeq_dp_wave_b128.hip", "vaeq_dp_wave_fl.hip", "vaeq_awgn.hip", "vaeq_awgn_wave.hip", "vaeq_misc.hip", "vaeq_ops.hip", "vaeq_nn.hip", "vaeq_nn_ops.hip", "vaeq_cma.hip", "vaeq_awgn_cma.hip", "vaeq_awgn_dfe.hip", "vaeq_epilogue.hip", "vaeq_epilogue_info.hip", "vaeq_cma_info.hip", "vaeq_awgn_info.hip", "vaeq_awgn_track_info.hip", "vaeq_epilogue_llr.hip", "vaeq_awgn_llr.hip", "vaeq_cma_llr.hip", "vaeq_awgn_track_llr.hip", "vaeq_ldpc.hip", "vaeq_ldpc_q.hip", "vaeq_ldpc_sc.hip", "vaeq_ldpc_sc_q.hip", "vaeq_bch.hip", "vaeq_staircase.hip", "vaeq_chase.hip", "vaeq_tpc.hip", "vaeq_gen.hip"]
-HEADERS = ["vaeq_common.h", "vaeq_launch.h", "vaeq_wave.h", "vaeq_validate.h", "vaeq_dp_wave_kernel.h", "vaeq_gen_fused.h", "vaeq_epilogue_lds.h", "vaeq_epilogue_keep.h", "vaeq_info.h", "vaeq_llr.h", "vaeq_noise.h", "vaeq_awgn_eval.h", "vaeq_nn_dev.h", "vaeq_nn_enc_backward_body.h", "vaeq_ldpc.h", "vaeq_ldpc_sc.h", "vaeq_fec.h"]
+SOURCES = ["vaeq_dp.hip", "vaeq_dp_wave.hip", "vaeq_dp_wave_mw.hip", "vaeq_dp_wave_mw8.hip", "vaeq_dp_wave_bk.hip", "vaeq_dp_wave_b128.hip", "vaeq_dp_wave_fl.hip", "vaeq_awgn.hip", "vaeq_awgn_wave.hip", "vaeq_misc.hip", "vaeq_ops.hip", "vaeq_nn.hip", "vaeq_nn_ops.hip", "vaeq_cma.hip", "vaeq_awgn_cma.hip", "vaeq_awgn_dfe.hip", "vaeq_epilogue.hip", "vaeq_epilogue_info.hip", "vaeq_cma_info.hip", "vaeq_awgn_info.hip", "vaeq_awgn_track_info.hip", "vaeq_epilogue_llr.hip", "vaeq_awgn_llr.hip", "vaeq_cma_llr.hip", "vaeq_awgn_track_llr.hip", "vaeq_ldpc.hip", "vaeq_ldpc_sc.hip", "vaeq_bch.hip", "vaeq_staircase.hip", "vaeq_chase.hip", "vaeq_tpc.hip", "vaeq_gen.hip"]
+HEADERS = ["vaeq_common.h", "vaeq_launch.h", "vaeq_wave.h", "vaeq_validate.h", "vaeq_dp_wave_kernel.h", "vaeq_gen_fused.h", "vaeq_epilogue_lds.h", "vaeq_epilogue_keep.h", "vaeq_info.h", "vaeq_llr.h", "vaeq_noise.h", "vaeq_awgn_eval.h", "vaeq_nn_dev.h", "vaeq_nn_enc_backward_body.h", "vaeq_ldpc.h", "vaeq_ldpc_rule.h", "vaeq_ldpc_sc.h", "vaeq_fec.h"]
 _LIB = None
 
 

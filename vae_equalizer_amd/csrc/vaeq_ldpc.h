@@ -1,5 +1,6 @@
-// vaeq_ldpc.h -- what the float32 decoder (vaeq_ldpc.hip) and the fixed-point decoder (vaeq_ldpc_q.hip) share: the envelope, the table of shifts
-// as it travels in the kernel arguments, its packer, the edge walker of a check and the gather of a codeword from the frame (both forms).
+// vaeq_ldpc.h -- what belongs to a quasi-cyclic block code (vaeq_ldpc.hip), whichever arithmetic decodes it (vaeq_ldpc_rule.h): the envelope, the
+// table of shifts as it travels in the kernel arguments, its packer, the edge walker of a check and the gather of a codeword from the frame
+// (both forms; the window decoders and the outer BCH decoder use the gather's map too).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -161,7 +162,7 @@ static inline bool ldpc_dims_ok(int64_t mb, int64_t nb, int64_t Z)
     return mb >= 1 && mb <= LDPC_MB && nb >= 2 && nb <= LDPC_NB && Z >= 2 && Z <= LDPC_Z;
 }
 
-// The shape rules the two decoders share, behind the empty batch and the NULL pointers: the frame and fit rules of vaeq_fec.h (il = the
+// The shape rules the block decoders share, behind the empty batch and the NULL pointers: the frame and fit rules of vaeq_fec.h (il = the
 // interleaver's); lds = the state of a codeword in bytes.
 static inline bool ldpc_shape_ok(int64_t R, int64_t C, int64_t N, int64_t w, int64_t t0, int64_t depth, int64_t mb, int64_t nb, int64_t Z,
                                  int64_t max_iter, int64_t lds, bool il)

@@ -1,10 +1,8 @@
-// vaeq_ldpc_sc.h -- what the float32 window decoder (vaeq_ldpc_sc.hip) and the fixed-point one (vaeq_ldpc_sc_q.hip) share: the envelope of a
-// spatially coupled chain, its table as it travels in the kernel arguments, the packer, the mask of the edges a truncated row really has and
-// the edge walker over the ring of column blocks; and what the two fixed-point kernels (vaeq_ldpc_q.hip, vaeq_ldpc_sc_q.hip) share: the
-// integer rule, the median of three and the conditional negation.
+// vaeq_ldpc_sc.h -- what belongs to a spatially coupled chain (vaeq_ldpc_sc.hip), whichever arithmetic decodes it: the envelope, the host's
+// shape rules, the table as it travels in the kernel arguments, the packer, the mask of the edges a truncated row really has and the edge
+// walker over the ring of column blocks.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -95,30 +93,21 @@ static inline bool sc_pack(int ms, int mb, int nb, int Z, int Lc, const int32_t 
     return true;
 }
 
-// the median of three: the clamp to [lo, hi] of x, and the second smallest of (m1, m2, a) when m1 <= m2
-__device__ __forceinline__ int ldpc_med3(int a, int b, int c)
+// the ring of a window in bytes: bytes(n_values, n_checks) is the arithmetic's state size (vaeq_ldpc_rule.h); call it behind sc_dims_ok
+static inline int64_t sc_ring_bytes(int64_t (*bytes)(int64_t, int64_t), int64_t ms, int64_t mb, int64_t nb, int64_t Z, int64_t W)
 {
-    int r;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
+    return bytes((W + ms) * nb * Z, W * mb * Z);
 }
 
-// x negated when bit e of sg is set
-__device__ __forceinline__ int ldpc_q_signed(int x, uint32_t sg, int e)
+// The shape rules the two window decoders share, behind the empty batch and the NULL pointers: the frame rule of vaeq_fec.h and the chain's
+// own, then the state, the fit of C chains of Lc nb Z bits each, bit-packed, and the index ranges.
+static inline bool sc_shape_ok(int64_t R, int64_t C, int64_t N, int64_t w, int64_t t0, int64_t ms, int64_t mb, int64_t nb, int64_t Z, int64_t Lc,
+                               int64_t W, int64_t T, int64_t iters, int64_t (*bytes)(int64_t, int64_t))
 {
-    const int mask = -(int)((sg >> e) & 1u);
-    return (x ^ mask) - mask;
-}
-
-struct ldpc_q_rule {
-    float scale;
-    int cmax, lmax, num, beta;                                 // Cmax = Mmax = 2^(qbits-1) - 1, Lmax = 2^(abits-1) - 1
-};
-
-// the quantiser's rules of vaeq_ldpc_decode_q and vaeq_ldpc_sc_decode_q (include/vaeq.h)
-inline bool ldpc_q_rule_ok(int64_t qbits, int64_t abits, float scale, int64_t num, int64_t beta)
-{
-    return !(qbits < 2 || qbits > 8 || abits < qbits || abits > 15 || !(scale > 0.f) || !isfinite(scale) || num < 1 || num > 8 || beta < 0 || beta > 127);
+    if (!fec_frame_ok(R, C, N, w, t0) || iters < 1 || iters > LDPC_ITER || !sc_dims_ok(ms, mb, nb, Z, W) || Lc < 1 || Lc > SC_LC || T < 1 || T > W)
+        return false;
+    return sc_ring_bytes(bytes, ms, mb, nb, Z, W) <= LDPC_STATE_MAX && fec_fit_ok(false, C, Lc * nb * Z, w, t0, N) && R * C <= 0x7fffffff &&
+           C * Lc <= 0x7fffffff;
 }
 
 }  // namespace vaeq

@@ -721,6 +721,43 @@ def _ldpc_fit(N, w, n, t0, depth):
     return (N - int(t0)) // -(-n // w) if n > 0 and w > 0 else 0
 
 
+def _ldpc_rule(alpha, quant):
+    """alpha= and quant= of ldpc_decode and ldpc_sc_decode -> (alpha with its default, the resolved quant dict or None)."""
+    if quant is not None:
+        if alpha is not None:
+            raise ValueError("alpha belongs to the float decoder; the fixed-point one is normalised by quant['num'] and quant['beta']")
+        quant = resolve_quant(quant)
+    return (0.75 if alpha is None else alpha), quant
+
+
+def _ldpc_frame(llr, bits):
+    """llr and bits of one shape [R,2,2b,N] or [R,w,N] -> (dev, R, N, w, llr[R,w,N], bits[R,w,N]), both contiguous."""
+    if llr.shape != bits.shape or llr.dim() not in (3, 4):
+        raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
+    R, N = llr.shape[0], llr.shape[-1]
+    llr = llr.reshape(R, -1, N).contiguous()
+    return llr.device, R, N, llr.shape[1], llr, bits.reshape(R, -1, N).contiguous()
+
+
+def _ldpc_count(given, what, N, w, n, t0, depth):
+    """The codewords (chains) of a run: as given, or the most that fit behind t0, which must be one at least."""
+    if given is not None:
+        return int(given)
+    C_ = _ldpc_fit(N, w, n, t0, depth)
+    if C_ < 1:
+        raise ValueError(f"no {what} of {n} bits fits into {N - int(t0)} symbols of {w} bits")
+    return C_
+
+
+def _ldpc_figures(out, C_, n):
+    """The dict both decoders return, from out[R, C, >= 5] int32 -> (out as int64, dict)."""
+    o = out.long()
+    tot = torch.full((out.shape[0],), float(max(C_ * n, 1)), dtype=torch.float64, device=out.device)   # a tensor divisor: a true division, not a product with 1 / tot
+    return o, dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
+                   BER_post=(o[..., 2].sum(1).double() / tot).float(), BER_pre=(o[..., 3].sum(1).double() / tot).float(),
+                   FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float())
+
+
 def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, want_post=False, depth=None, quant=None, outer=None):
     """Post-FEC figures of per-bit LLRs on the device (vaeq_ldpc_decode): layered normalized min-sum towards the syndrome of the TX bits (no
     encoder).  llr f32 and bits int8 of one shape, [R,2,2b,N] (dp_epilogue_llr / cma_epilogue_llr with label_bits) or [R,w,N] (awgn_llr,
@@ -740,20 +777,10 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, 
     every codeword."""
     if outer is not None:
         outer = resolve_outer(outer, code)
-    if quant is not None:
-        if alpha is not None:
-            raise ValueError("alpha belongs to the float decoder; the fixed-point one is normalised by quant['num'] and quant['beta']")
-        quant = resolve_quant(quant)
-    alpha = 0.75 if alpha is None else alpha
-    if llr.shape != bits.shape or llr.dim() not in (3, 4):
-        raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
-    dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
-    llr = llr.reshape(R, -1, N).contiguous()
-    bits = bits.reshape(R, -1, N).contiguous()
-    w, n = llr.shape[1], code.n
-    C_ = int(codewords) if codewords is not None else _ldpc_fit(N, w, n, t0, depth)
-    if codewords is None and C_ < 1:
-        raise ValueError(f"no codeword of {n} bits fits into {N - int(t0)} symbols of {w} bits")
+    alpha, quant = _ldpc_rule(alpha, quant)
+    dev, R, N, w, llr, bits = _ldpc_frame(llr, bits)
+    n = code.n
+    C_ = _ldpc_count(codewords, "codeword", N, w, n, t0, depth)
     out = torch.empty(R, max(C_, 0), 5, dtype=torch.int32, device=dev)
     post = torch.empty(R, max(C_, 0), n, dtype=torch.float32 if quant is None else torch.int16, device=dev) if want_post or outer is not None else None
     with torch.cuda.device(dev):
@@ -766,11 +793,7 @@ def ldpc_decode(llr, bits, code, t0=0, codewords=None, max_iter=20, alpha=None, 
             nat.check(nat.lib().vaeq_ldpc_decode(R, C_, N, w, int(t0), *head, float(alpha), *tail), "vaeq_ldpc_decode")
         else:
             nat.check(nat.lib().vaeq_ldpc_decode_il(R, C_, N, w, int(t0), int(depth), *head, float(alpha), *tail), "vaeq_ldpc_decode_il")
-    o = out.long()
-    tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)   # a tensor divisor: a true division, not a product with 1 / tot
-    ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
-               BER_post=(o[..., 2].sum(1).double() / tot).float(), BER_pre=(o[..., 3].sum(1).double() / tot).float(),
-               FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float())
+    _, ret = _ldpc_figures(out, C_, n)
     if want_post:
         ret["post"] = post
     if quant is not None:
@@ -841,21 +864,11 @@ def ldpc_sc_decode(llr, bits, code, window, t0=0, chains=None, iters=10, alpha=N
         raise ValueError(f"ldpc_sc_decode takes an ScLdpcCode, got {code!r}")
     if outer is not None:
         outer = resolve_outer(outer, code)
-    if quant is not None:
-        if alpha is not None:
-            raise ValueError("alpha belongs to the float decoder; the fixed-point one is normalised by quant['num'] and quant['beta']")
-        quant = resolve_quant(quant)
-    alpha = 0.75 if alpha is None else alpha
+    alpha, quant = _ldpc_rule(alpha, quant)
     test = code.ms + 1 if test is None else test
-    if llr.shape != bits.shape or llr.dim() not in (3, 4):
-        raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
-    dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
-    llr = llr.reshape(R, -1, N).contiguous()
-    bits = bits.reshape(R, -1, N).contiguous()
-    w, n = llr.shape[1], code.n
-    C_ = int(chains) if chains is not None else _ldpc_fit(N, w, n, t0, None)
-    if chains is None and C_ < 1:
-        raise ValueError(f"no chain of {n} bits fits into {N - int(t0)} symbols of {w} bits")
+    dev, R, N, w, llr, bits = _ldpc_frame(llr, bits)
+    n = code.n
+    C_ = _ldpc_count(chains, "chain", N, w, n, t0, None)
     P = max(1, code.L + code.ms - int(window) + 1)
     Cn = max(C_, 0)
     out = torch.empty(R, Cn, 6, dtype=torch.int32, device=dev)
@@ -873,11 +886,8 @@ def ldpc_sc_decode(llr, bits, code, window, t0=0, chains=None, iters=10, alpha=N
                       "vaeq_ldpc_sc_decode_q")
         else:
             nat.check(nat.lib().vaeq_ldpc_sc_decode(*head, float(alpha), *tail), "vaeq_ldpc_sc_decode")
-    o = out.long()
-    tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)
-    ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4],
-               BER_post=(o[..., 2].sum(1).double() / tot).float(), BER_pre=(o[..., 3].sum(1).double() / tot).float(),
-               FER=((o[..., 2] > 0).sum(1).double() / torch.full_like(tot, float(max(C_, 1)))).float(), iters_max=o[..., 5], positions=P)
+    o, ret = _ldpc_figures(out, C_, n)
+    ret.update(iters_max=o[..., 5], positions=P)
     if want_post:
         ret["post"] = post
     if want_profile:
