@@ -975,6 +975,60 @@ int vaeq_tpc_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0,
                     int32_t K1, int32_t K2, int32_t *out, float *llr_out, int8_t *bits_out, float *ext, int32_t *half_err, void *stream);
 int64_t vaeq_tpc_lds_bytes(int32_t n1, int32_t r1, int32_t n2, int32_t r2);
 
+/* The two Chase decoders over (extended) double-error-correcting BCH words, the components of the soft-decision product codes that 100G line
+ * cards shipped and of today's open-FEC family: minimum distance 6 with the parity bit, against 4 of an extended Hamming word (no reference
+ * counterpart).  Everything that is not said here is vaeq_chase_decode's and vaeq_tpc_decode's, word for word.
+ * The code: vaeq_bch_outer's narrow-sense primitive binary BCH code over GF(2^m) with designed correction t = 2 -- the same polynomials, position
+ * p belongs to alpha^p -- shortened to n_i inner bits, followed, where ext == 1, by one overall parity bit at position u = n_i: n = n_i + ext.
+ * m in 4 .. 8, parity(m, 2) = 2 m < n_i <= 2^m - 1, so n <= 256; k = n_i - 2 m.  m = 7, n = 128, ext = 1 is the extended (128, 113) word, m = 8,
+ * n = 256, ext = 1 the (256, 239) word.  Only t = 2: t >= 3 has no closed-form locator of this size and is out of scope.
+ * The rule for one word, in the place of vaeq_chase_decode's lines "patterns" and "metric"; input, positions (the parity position takes part
+ * like any other), winner, the three statuses, out[R][C][6], the payload stream, depth, spread and K are that call's:
+ *   patterns   T = 0 .. 2^p - 1:  F_T = { l_i : bit i of T };  x = e xor F_T.  The inner part of x, its positions below n_i, is decided by
+ *              vaeq_bch_outer's rule with t = 2 and n_o = n_i: status 0 gives V = {}; status 1 gives V, the unique set of one or two positions
+ *              below n_i with the same S_1 .. S_4; status 2: T has no candidate.  If ext, u is flipped iff the weight of x over all n positions
+ *              plus |V| is odd.  The candidate flips Phi_T = F_T delta V delta {u if flipped} (symmetric differences): e xor Phi_T is a codeword
+ *              of the extended code, and |Phi_T| <= p + 3.
+ *   metric     of a candidate: from +0.0f, add a_j over Phi_T one float32 addition at a time -- first its members among l_0 .. l_(p-1) in
+ *              ascending i, then the others in ascending position (at most three; u, the largest position, last).  The metric is a function
+ *              of the set alone.  (Predicated additions of +0.0f are the same sum, as above.)
+ * (In closed form: S_1 = S_3 = 0: V = {}.  S_1 = 0 alone: no candidate.  S_3 = S_1^3: V = {log S_1}.  Otherwise V = {log(S_1 y), log(S_1 y +
+ * S_1)} for a root y of y^2 + y = (S_3 + S_1^3) / S_1^3, no candidate where there is none.  A position >= n_i: no candidate.)
+ * Status 0 is the case exactly when S_1 = S_3 = 0 and, if ext, the weight of e is even; the code is not perfect, so status 2 is reached at full length too.
+ * vaeq_chase_bch_decode is vaeq_chase_decode with (m, n, ext) in the place of (n, r, cols_host): the same kernel body, the exp, log and
+ * half-solve tables of GF(2^m) (3 2^m uint16) built in LDS in the place of the columns, and lane T decides pattern T by the closed form.
+ * Refusals, all before any HIP call and in vaeq_chase_decode's order: R == 0 is VAEQ_OK; a NULL llr, bits or out, or exactly one of llr_out and
+ * bits_out, is VAEQ_ERR_NULL; then VAEQ_ERR_SHAPE for the tensor rules, depth outside 0 .. C, m outside 4 .. 8, ext outside 0 .. 1, n - ext
+ * outside 2 m + 1 .. 2^m - 1, p outside 0 .. min(6, n), K outside 1 .. n, spread outside 0 .. 1, the fit rule, R C > 0x7fffffff and C K >
+ * 0x3fffffff when a stream is asked for. */
+int vaeq_chase_bch_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t m, int32_t n, int32_t ext,
+                          const float *llr, const int8_t *bits, int32_t p, int32_t K, int32_t spread, int32_t *out, float *llr_out,
+                          int8_t *bits_out, void *stream);
+
+/* vaeq_tpc_decode over two such codes: the column code (m1, n1, ext1) and the row code (m2, n2, ext2), which may differ in all three.  The rule is
+ * vaeq_tpc_decode's word for word with "one word" the rule above; the soft input, the competitors (a candidate competes at j where j lies in the
+ * symmetric difference of Phi_T and Phi_D; a plain minimum; beta where none competes), the clamps, the schedules, the counters, the stream, ext
+ * and half_err are unchanged.  The stop test asks that no word of h had status 2 and that every word of the other direction has S_1 = S_3 = 0
+ * on d and, if that code is extended, even weight.
+ * Bounds as there.  A metric now adds at most 9 magnitudes (p + 3) of at most 17 clip, so with clip <= 2^96 every metric stays below 2^104 and
+ * every difference below 2^105: no infinity and no NaN arises.
+ * The same kernel body; a lane's competitor walk takes at most p + 5 places: the listed positions, its own up to two unlisted located
+ * positions, the winner's, and the parity position.  vaeq_tpc_bch_lds_bytes(m1, n1, ext1, m2, n2, ext2) = 8 n1 (n2 | 1) + n1 (n2 | 1) padded
+ * to a word + 4 waves max(n1, n2) + 6 2^m1 + (6 2^m2 if m2 != m1: one field, one set of tables), under the same bound of 156 KiB.  The extended
+ * (128, 113)^2 block holds 157 568 bytes.  The (256, 239)^2 block does not fit -- 9 bytes per bit are 590 KB -- and is out of scope: it needs a
+ * state outside LDS or a narrower one.  Also out of scope: a product of one Hamming and one BCH component, braided or staircase-shaped soft
+ * decoding, a fixed-point form, an encoder.  That call returns VAEQ_ERR_SHAPE outside the envelope of either code and VAEQ_ERR_LDS above the bound.
+ * Refusals, all before any HIP call and in vaeq_tpc_decode's order: R == 0 is VAEQ_OK; a NULL llr, bits, alpha_host, beta_host or out, or
+ * exactly one of llr_out and bits_out, is VAEQ_ERR_NULL; then VAEQ_ERR_SHAPE for the tensor rules, the envelope of either code (as above), p
+ * outside 0 .. min(6, n1, n2), iters, clip, the schedules, K1 outside 1 .. n1, K2 outside 1 .. n2, the fit rule, R C > 0x7fffffff, and C n >
+ * 0x3fffffff when a stream is asked for; last VAEQ_ERR_LDS for a state above the bound. */
+int vaeq_tpc_bch_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0,
+                        int32_t m1, int32_t n1, int32_t ext1, int32_t m2, int32_t n2, int32_t ext2,
+                        const float *llr, const int8_t *bits, int32_t p, int32_t iters,
+                        const float *alpha_host, const float *beta_host, const float *scale, float clip,
+                        int32_t K1, int32_t K2, int32_t *out, float *llr_out, int8_t *bits_out, float *ext, int32_t *half_err, void *stream);
+int64_t vaeq_tpc_bch_lds_bytes(int32_t m1, int32_t n1, int32_t ext1, int32_t m2, int32_t n2, int32_t ext2);
+
 int vaeq_version(void);
 const char *vaeq_strerror(int code);
 

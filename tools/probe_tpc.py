@@ -7,6 +7,12 @@
 
 --out is written anew by every run; the committed file is the run with the defaults.
 
+    python tools/probe_tpc.py --bch [--bers 0,0.01,0.02] [--bch-bers 0,0.03,0.045] [--out profiles/tpc_bch/probe.txt]
+
+--bch measures vaeq_tpc_bch_decode on the extended (128, 113)^2 code of double-error-correcting BCH words at --bch-bers (chosen with model (1) of
+tests/_ref_ebch.py: clean, a level where every block converges, one past the threshold) behind the table above, taken again in the same session
+as the yardstick, and closes with the ratio of the two per block and half-iteration.
+
 The LLRs are synthetic BPSK + AWGN LLRs generated on the device from a seed, as tools/probe_chase.py makes them: random TX bits, y = (1 - 2 b) +
 sigma noise with sigma chosen so that Q(1 / sigma) is the level's bit error rate, llr = 2 y / sigma^2; at level 0 there is no noise and sigma is
 the next level's.  Per level, after a warm-up call, --rounds calls between device events (host wrapper + kernel): median / min / max, with the scale
@@ -37,23 +43,46 @@ def main():
     ap.add_argument("--patterns", type=int, default=4)
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tpc", "probe.txt"))
+    ap.add_argument("--bch", action="store_true")
+    ap.add_argument("--bch-bers", default="0,0.03,0.045")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "tpc_bch" if a.bch else "tpc", "probe.txt")
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
     w, R, N = 12, a.runs, a.symbols
-    code = engine.ProductCode(engine.hamming_code(7), engine.hamming_code(7))
-    C_ = N * w // code.n
     copy_gbs = bench.stream_copy_gbs(dev)
     floor_ms = 5 * R * w * N / (copy_gbs * 1e9) * 1e3
-    lines = [f"# vaeq_tpc_decode: {R} runs x {C_} blocks of the extended ({code.row.n}, {code.row.k})^2 product code, n = {code.n}, w = {w}, {N} "
+    llr = torch.empty(R, w, N, dtype=torch.float32, device=dev)
+    lines, per_half = [], []
+    tables = [(engine.ProductCode(engine.hamming_code(7), engine.hamming_code(7)), "vaeq_tpc_decode", a.bers)]
+    if a.bch:
+        tables.append((engine.ProductCode(engine.ebch_code(7), engine.ebch_code(7)), "vaeq_tpc_bch_decode", a.bch_bers))
+    for code, name, bers in tables:
+        per_half.append(table(a, code, name, bers, llr, g, copy_gbs, floor_ms, lines))
+    if a.bch:
+        ratio = [round(b / h, 3) for h, b in zip(*per_half)]
+        line = json.dumps(dict(us_per_block_half_iteration_hamming=per_half[0], us_per_block_half_iteration_bch=per_half[1], bch_over_hamming=ratio,
+                               note="level by level: clean, converging, past the threshold; the levels differ between the codes"))
+        print(line, flush=True)
+        lines.append(line)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def table(a, code, name, bers, llr, g, copy_gbs, floor_ms, lines):
+    """One code's table into lines -> us per block and half-iteration, level by level."""
+    dev, (R, w, N) = llr.device, llr.shape
+    C_ = N * w // code.n
+    first, per_half = len(lines), []
+    lines += [f"# {name}: {R} runs x {C_} blocks of the extended ({code.row.n}, {code.row.k})^2 product code, n = {code.n}, w = {w}, {N} "
              f"symbols, patterns {a.patterns}, at most {2 * a.iters} half-iterations, Pyndiah's schedules, clip 2^60; "
              f"{torch.cuda.get_device_name(dev)}",
              f"# copy bandwidth (vaeq_stream_copy, read + write): {copy_gbs:.0f} GB/s; llr and bits once: 5 x {R} x {w} x {N} B = "
              f"{5 * R * w * N / 1e9:.3f} GB -> floor {floor_ms:.3f} ms"]
-    print("\n".join(lines), flush=True)
-    llr = torch.empty(R, w, N, dtype=torch.float32, device=dev)
-    bers = [float(x) for x in a.bers.split(",")]
+    print("\n".join(lines[first:]), flush=True)
+    bers = [float(x) for x in bers.split(",")]
     for k, ber in enumerate(bers):
         noisy = ber if ber > 0 else min(b for b in bers if b > 0)
         sigma = 1.0 / statistics.NormalDist().inv_cdf(1.0 - noisy)
@@ -82,10 +111,9 @@ def main():
                                us_per_block_half_iteration=round(t["median_ms"] * 1e3 / (R * C_ * fig["half_iterations_per_block"]), 4), **fig))
         print(line, flush=True)
         lines.append(line)
+        per_half.append(round(t["median_ms"] * 1e3 / (R * C_ * fig["half_iterations_per_block"]), 4))
         del bits
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    return per_half
 
 
 if __name__ == "__main__":

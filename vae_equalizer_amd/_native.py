@@ -114,7 +114,7 @@ EXPORTS = ["vaeq_dp_train", "vaeq_dp_step_debug", "vaeq_dp_lds_bytes", "vaeq_dp_
            "vaeq_cma_epilogue_llr", "vaeq_awgn_track_llr", "vaeq_ldpc_decode", "vaeq_ldpc_lds_bytes", "vaeq_ldpc_decode_il",
            "vaeq_ldpc_decode_q", "vaeq_ldpc_q_lds_bytes", "vaeq_bch_outer", "vaeq_ldpc_sc_decode", "vaeq_ldpc_sc_lds_bytes",
            "vaeq_ldpc_sc_decode_q", "vaeq_ldpc_sc_q_lds_bytes", "vaeq_staircase_decode", "vaeq_staircase_lds_bytes", "vaeq_chase_decode",
-           "vaeq_tpc_decode", "vaeq_tpc_lds_bytes"]
+           "vaeq_tpc_decode", "vaeq_tpc_lds_bytes", "vaeq_chase_bch_decode", "vaeq_tpc_bch_decode", "vaeq_tpc_bch_lds_bytes"]
 
 
 def lib():
@@ -209,6 +209,14 @@ def lib():
                                       + [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 3 + [C.c_float] + [C.c_int32] * 2 + [C.c_void_p] * 6)
         L.vaeq_tpc_lds_bytes.restype = C.c_int64
         L.vaeq_tpc_lds_bytes.argtypes = [C.c_int32] * 4
+        L.vaeq_chase_bch_decode.restype = C.c_int
+        L.vaeq_chase_bch_decode.argtypes = ([C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 2
+                                            + [C.c_int32] * 3 + [C.c_void_p] * 4)
+        L.vaeq_tpc_bch_decode.restype = C.c_int
+        L.vaeq_tpc_bch_decode.argtypes = ([C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 2
+                                          + [C.c_int32] * 2 + [C.c_void_p] * 3 + [C.c_float] + [C.c_int32] * 2 + [C.c_void_p] * 6)
+        L.vaeq_tpc_bch_lds_bytes.restype = C.c_int64
+        L.vaeq_tpc_bch_lds_bytes.argtypes = [C.c_int32] * 6
         L.vaeq_awgn_track_info.restype = C.c_int
         L.vaeq_awgn_track_info.argtypes = [C.c_int32, C.c_int64, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p] * 9
         L.vaeq_awgn_dfe_soft.restype = C.c_int

@@ -11,6 +11,8 @@
 // evaluates test pattern T -- one table lookup and at most seven predicated additions -- and one more minimum over metric bits << 8 | T picks
 // the winner.  That span is the text of vaeq_fec.h's chase_front, which vaeq_tpc.hip calls; it stands here in place because this kernel measured
 // 4 to 8 % slower through the call: a fix to one goes to the other.  Counters are ballots and popcounts.
+// vaeq_chase_bch_decode is the same kernel with CODE = ebch_code: the exp, log and half-solve tables of GF(2^m) in the place of the columns and
+// positions, and that span replaced by a call of vaeq_fec.h's ebch_front; the gather, the tiles, the counters and the stream are written once.
 // The payload stream leaves through a transposed byte tile in LDS (rows of 33 bytes: no bank
 // conflict on either side), so that under either spread a wave's stores are runs of consecutive stream entries.  Everything leaves as plain
 // vector stores.  Every loop has a static bound.
@@ -43,13 +45,16 @@ static inline size_t chase_lds_bytes(int n, int K, bool want_stream)
     return 4 * pos + (want_stream ? ((size_t)K * CHASE_ROW + 3) / 4 * 4 : 0) + pos;
 }
 
-template <bool IL>
-__global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, const fec_cols tab, const float *__restrict__ llr,
+// CODE: fec_cols, a single-error-correcting code by its columns, or ebch_code, an (extended) t = 2 BCH code by its field (vaeq_chase_bch_decode).
+// The two share everything but the tables and the span from the list to the flips.
+template <bool IL, class CODE>
+__global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, const CODE tab, const float *__restrict__ llr,
                                                          const int8_t *__restrict__ bits, int32_t *__restrict__ out,
                                                          float *__restrict__ llr_out, int8_t *__restrict__ bits_out)
 {
     extern __shared__ __align__(16) unsigned char chase_lds[];
-    __shared__ uint16_t COL[CHASE_N], POS[1 << CHASE_R];
+    constexpr bool BCH = std::is_same<CODE, ebch_code>::value;
+    __shared__ uint16_t COL[CHASE_N], POS[1 << CHASE_R];       // (not referenced, and so not allocated, where BCH)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = A.n, p = A.p, K = A.K, C = A.C, w = A.w;
     const int ns = n | 1, npos = A.tw * ns + CHASE_N;
@@ -57,12 +62,19 @@ __global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, con
     uint8_t *ST = chase_lds + 4 * (size_t)npos;                // the stream tile: row i, CHASE_ROW bytes, holds TX bit | decided bit << 1 of payload bit i
     uint8_t *TT = ST + (llr_out ? ((size_t)K * CHASE_ROW + 3) / 4 * 4 : 0);
 
-    for (int s = tid; s < (1 << CHASE_R); s += CHASE_NT) POS[s] = (uint16_t)CHASE_NONE;
-    __syncthreads();
-    {   // CHASE_NT == CHASE_N: thread j owns column j; the columns are distinct, so no two threads write one entry
-        const uint32_t c = tid < n ? tab.col[tid] : 0u;
-        COL[tid] = (uint16_t)c;
-        if (tid < n) POS[c] = (uint16_t)tid;
+    ebch_tables tb = {};
+    if constexpr (BCH) {
+        __shared__ uint16_t TABLES[3 << EBCH_M_MAX];           // exp, log and half-solve of GF(2^m)
+        ebch_build(TABLES, tab.m, tab.poly, tid, CHASE_NT);
+        tb = ebch_view(TABLES, tab);
+    } else {
+        for (int s = tid; s < (1 << CHASE_R); s += CHASE_NT) POS[s] = (uint16_t)CHASE_NONE;
+        __syncthreads();
+        {   // CHASE_NT == CHASE_N: thread j owns column j; the columns are distinct, so no two threads write one entry
+            const uint32_t c = tid < n ? tab.col[tid] : 0u;
+            COL[tid] = (uint16_t)c;
+            if (tid < n) POS[c] = (uint16_t)tid;
+        }
     }
     __syncthreads();
 
@@ -101,70 +113,80 @@ __global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, con
                 key[k] = in ? a : ~0u;
                 err |= e << k;
                 txb |= (in ? (uint32_t)TT[base + j] : 0u) << k;
-                s0 ^= e ? (uint32_t)COL[j] : 0u;
+                if constexpr (BCH) s0 ^= e ? ebch_col(tb, (uint32_t)(in ? j : 0)) : 0u;
+                else s0 ^= e ? (uint32_t)COL[j] : 0u;
                 pre += __popcll(__ballot(e != 0));
                 erased += __popcll(__ballot(in && a == 0));
             }
             s0 = fec_wave_xor(s0);
 
-            // the p least reliable positions: wave-uniform position, column and |x|
-            uint32_t lp[CHASE_P], lc[CHASE_P];
-            float la[CHASE_P];
-#pragma unroll
-            for (int i = 0; i < CHASE_P; i++) {
-                lp[i] = CHASE_NONE;
-                lc[i] = 0;
-                la[i] = 0.0f;
-                if (i < p) {                                       // wave-uniform; p <= n: a position is left
-                    uint32_t m = key[0];                               // by (|x|, j): the smallest |x| (its bits order as it does: it is never
-#pragma unroll
-                    for (int k = 1; k < CHASE_SLOTS; k++) m = min(m, key[k]);   // negative), then the smallest position that has it
-                    m = fec_wave_min(m);
-                    uint32_t at = CHASE_NONE;
-#pragma unroll
-                    for (int k = CHASE_SLOTS - 1; k >= 0; k--) at = key[k] == m ? (uint32_t)(64 * k + lane) : at;
-                    lp[i] = fec_wave_min(at);
-                    la[i] = __uint_as_float(m);
-                    lc[i] = COL[lp[i]];
-#pragma unroll
-                    for (int k = 0; k < CHASE_SLOTS; k++) key[k] = (uint32_t)(64 * k + lane) == lp[i] ? ~0u : key[k];
-                }
-            }
-
-            // lane T: test pattern T
-            const uint32_t T = (uint32_t)lane;
-            uint32_t s = s0;
-#pragma unroll
-            for (int i = 0; i < CHASE_P; i++) s ^= (T >> i) & 1u ? lc[i] : 0u;
-            const uint32_t v = s ? (uint32_t)POS[s] : CHASE_NONE;  // s < 2^r: a xor of columns
-            const bool cand = T < (1u << p) && (s == 0 || v != CHASE_NONE);
-            float metric = 0.0f;
-            bool cancelled = false;
-#pragma unroll
-            for (int i = 0; i < CHASE_P; i++) {                    // x + (+0) = x for x >= 0: the predicated add is the specified sum
-                const bool in = (T >> i) & 1u, hit = in && lp[i] == v;
-                metric += in && !hit ? la[i] : 0.0f;
-                cancelled |= hit;
-            }
-            const uint32_t av = TA[base + (int)min(v, (uint32_t)CHASE_N - 1u)] & 0x7fffffffu;
-            metric += v != CHASE_NONE && !cancelled ? __uint_as_float(av) : 0.0f;
-            const uint32_t mine = cand ? __float_as_uint(metric) : ~0u, best = fec_wave_min(mine);   // by (metric, T)
-
             int status = 2, nflip = 0;
             uint32_t flip = 0;                                     // bit k: slot k of this lane is flipped
-            if (best != ~0u) {                                     // wave-uniform
-                const uint32_t Tw = fec_wave_min(mine == best ? T : CHASE_NONE), vw = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)Tw);
+            if constexpr (BCH) {
+                const ebch_pick c = ebch_front(key, s0, n, p, lane, tb, [&](uint32_t v) {
+                    return __uint_as_float(TA[base + (int)min(v, (uint32_t)n - 1u)] & 0x7fffffffu);
+                });
+                flip = c.flip;
+                nflip = c.nflip;
+                status = c.best == ~0u ? 2 : nflip ? 1 : 0;
+            } else {
+                // the p least reliable positions: wave-uniform position, column and |x|
+                uint32_t lp[CHASE_P], lc[CHASE_P];
+                float la[CHASE_P];
 #pragma unroll
-                for (int k = 0; k < CHASE_SLOTS; k++) {
-                    if (64 * k >= n) break;
-                    const uint32_t j = (uint32_t)(64 * k + lane);
-                    uint32_t f = vw == j;                          // the symmetric difference of F_T and {v}
+                for (int i = 0; i < CHASE_P; i++) {
+                    lp[i] = CHASE_NONE;
+                    lc[i] = 0;
+                    la[i] = 0.0f;
+                    if (i < p) {                                       // wave-uniform; p <= n: a position is left
+                        uint32_t m = key[0];                               // by (|x|, j): the smallest |x| (its bits order as it does: it is never
 #pragma unroll
-                    for (int i = 0; i < CHASE_P; i++) f ^= (uint32_t)(((Tw >> i) & 1u) && lp[i] == j);
-                    flip |= f << k;
-                    nflip += __popcll(__ballot(f != 0));
+                        for (int k = 1; k < CHASE_SLOTS; k++) m = min(m, key[k]);   // negative), then the smallest position that has it
+                        m = fec_wave_min(m);
+                        uint32_t at = CHASE_NONE;
+#pragma unroll
+                        for (int k = CHASE_SLOTS - 1; k >= 0; k--) at = key[k] == m ? (uint32_t)(64 * k + lane) : at;
+                        lp[i] = fec_wave_min(at);
+                        la[i] = __uint_as_float(m);
+                        lc[i] = COL[lp[i]];
+#pragma unroll
+                        for (int k = 0; k < CHASE_SLOTS; k++) key[k] = (uint32_t)(64 * k + lane) == lp[i] ? ~0u : key[k];
+                    }
                 }
-                status = nflip ? 1 : 0;
+
+                // lane T: test pattern T
+                const uint32_t T = (uint32_t)lane;
+                uint32_t s = s0;
+#pragma unroll
+                for (int i = 0; i < CHASE_P; i++) s ^= (T >> i) & 1u ? lc[i] : 0u;
+                const uint32_t v = s ? (uint32_t)POS[s] : CHASE_NONE;  // s < 2^r: a xor of columns
+                const bool cand = T < (1u << p) && (s == 0 || v != CHASE_NONE);
+                float metric = 0.0f;
+                bool cancelled = false;
+#pragma unroll
+                for (int i = 0; i < CHASE_P; i++) {                    // x + (+0) = x for x >= 0: the predicated add is the specified sum
+                    const bool in = (T >> i) & 1u, hit = in && lp[i] == v;
+                    metric += in && !hit ? la[i] : 0.0f;
+                    cancelled |= hit;
+                }
+                const uint32_t av = TA[base + (int)min(v, (uint32_t)CHASE_N - 1u)] & 0x7fffffffu;
+                metric += v != CHASE_NONE && !cancelled ? __uint_as_float(av) : 0.0f;
+                const uint32_t mine = cand ? __float_as_uint(metric) : ~0u, best = fec_wave_min(mine);   // by (metric, T)
+
+                if (best != ~0u) {                                     // wave-uniform
+                    const uint32_t Tw = fec_wave_min(mine == best ? T : CHASE_NONE), vw = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)Tw);
+#pragma unroll
+                    for (int k = 0; k < CHASE_SLOTS; k++) {
+                        if (64 * k >= n) break;
+                        const uint32_t j = (uint32_t)(64 * k + lane);
+                        uint32_t f = vw == j;                          // the symmetric difference of F_T and {v}
+#pragma unroll
+                        for (int i = 0; i < CHASE_P; i++) f ^= (uint32_t)(((Tw >> i) & 1u) && lp[i] == j);
+                        flip |= f << k;
+                        nflip += __popcll(__ballot(f != 0));
+                    }
+                    status = nflip ? 1 : 0;
+                }
             }
             err ^= flip;
             int post = 0, pay_post = 0;
@@ -199,6 +221,28 @@ __global__ __launch_bounds__(CHASE_NT) void chase_kernel(const chase_args A, con
     }
 }
 
+// The rules both entry points share behind the code's own: the frame, depth, p, K, spread, that depth's fit rule and the counts.
+static inline bool chase_rules_ok(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t n, int32_t p, int32_t K, int32_t spread,
+                                  bool want_stream)
+{
+    return fec_frame_ok(R, C, N, w, t0) && depth >= 0 && depth <= C && p >= 0 && p <= CHASE_P && p <= n && K >= 1 && K <= n && spread >= 0 &&
+           spread <= 1 && fec_fit_ok(depth >= 1, C, n, w, t0, N) && (int64_t)R * C <= 0x7fffffff && !(want_stream && (int64_t)C * K > 0x3fffffff);
+}
+
+// r: the columns' width of a single-error-correcting code, m of a BCH one
+template <class CODE>
+static inline int chase_launch(const CODE &code, int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t n, int32_t r, int32_t p,
+                               int32_t K, int32_t spread, const float *llr, const int8_t *bits, int32_t *out, float *llr_out, int8_t *bits_out,
+                               void *stream)
+{
+    const int tw = chase_tile_words(n), tiles_run = (C + tw - 1) / tw;
+    const chase_args A = {(long long)N, (long long)t0, (long long)R * tiles_run, (int)C, (int)w, (int)depth, (int)n, (int)r, (int)p, (int)K, (int)spread,
+                          tw, tiles_run};
+    const dim3 grid((unsigned)(A.tiles < CHASE_GRID ? A.tiles : CHASE_GRID)), block(CHASE_NT);
+    return launch(depth >= 1 ? chase_kernel<true, CODE> : chase_kernel<false, CODE>, grid, block, chase_lds_bytes(n, K, llr_out != nullptr),
+                  reinterpret_cast<hipStream_t>(stream), A, code, llr, bits, out, llr_out, bits_out);
+}
+
 }  // namespace vaeq
 
 extern "C" int vaeq_chase_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t n, int32_t r,
@@ -208,17 +252,20 @@ extern "C" int vaeq_chase_decode(int32_t R, int32_t C, int64_t N, int32_t w, int
     using namespace vaeq;
     if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
     if (!cols_host || !llr || !bits || !out || !llr_out != !bits_out) return VAEQ_ERR_NULL;
-    if (!fec_frame_ok(R, C, N, w, t0) || depth < 0 || depth > C || n < 3 || n > CHASE_N || r < 2 || r > CHASE_R || p < 0 || p > CHASE_P || p > n ||
-        K < 1 || K > n || spread < 0 || spread > 1)
+    if (n < 3 || n > CHASE_N || r < 2 || r > CHASE_R || !chase_rules_ok(R, C, N, w, t0, depth, n, p, K, spread, llr_out != nullptr))
         return VAEQ_ERR_SHAPE;
-    if (!fec_fit_ok(depth >= 1, C, n, w, t0, N)) return VAEQ_ERR_SHAPE;
-    if ((int64_t)R * C > 0x7fffffff || (llr_out && (int64_t)C * K > 0x3fffffff)) return VAEQ_ERR_SHAPE;
     fec_cols tab;
     if (!fec_cols_pack(cols_host, n, r, &tab)) return VAEQ_ERR_SHAPE;
-    const int tw = chase_tile_words(n), tiles_run = (C + tw - 1) / tw;
-    const chase_args A = {(long long)N, (long long)t0, (long long)R * tiles_run, (int)C, (int)w, (int)depth, (int)n, (int)r, (int)p, (int)K, (int)spread,
-                          tw, tiles_run};
-    const dim3 grid((unsigned)(A.tiles < CHASE_GRID ? A.tiles : CHASE_GRID)), block(CHASE_NT);
-    return launch(depth >= 1 ? chase_kernel<true> : chase_kernel<false>, grid, block, chase_lds_bytes(n, K, llr_out != nullptr),
-                  reinterpret_cast<hipStream_t>(stream), A, tab, llr, bits, out, llr_out, bits_out);
+    return chase_launch(tab, R, C, N, w, t0, depth, n, r, p, K, spread, llr, bits, out, llr_out, bits_out, stream);
+}
+
+extern "C" int vaeq_chase_bch_decode(int32_t R, int32_t C, int64_t N, int32_t w, int64_t t0, int32_t depth, int32_t m, int32_t n, int32_t ext,
+                                     const float *llr, const int8_t *bits, int32_t p, int32_t K, int32_t spread, int32_t *out, float *llr_out,
+                                     int8_t *bits_out, void *stream)
+{
+    using namespace vaeq;
+    if (R == 0) return VAEQ_OK;                                // an empty batch owns no memory: its pointers may be NULL
+    if (!llr || !bits || !out || !llr_out != !bits_out) return VAEQ_ERR_NULL;
+    if (!ebch_ok(m, n, ext) || !chase_rules_ok(R, C, N, w, t0, depth, n, p, K, spread, llr_out != nullptr)) return VAEQ_ERR_SHAPE;
+    return chase_launch(ebch_make(m, n, ext), R, C, N, w, t0, depth, n, m, p, K, spread, llr, bits, out, llr_out, bits_out, stream);
 }

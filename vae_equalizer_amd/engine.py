@@ -1100,8 +1100,40 @@ def hamming_code(m, extended=True, n=None):
     return HammingCode((j << 1) | 1 if extended else j + 1, m + 1 if extended else m)
 
 
+class EbchCode:
+    """An (extended) double-error-correcting BCH code for chase_decode and ProductCode (vaeq_chase_bch_decode): vaeq_bch_outer's narrow-sense
+    primitive binary BCH code over GF(2^m) with designed correction t = 2, shortened to n_i inner bits and, where `extended`, followed by one
+    overall parity bit: n = n_i + extended (default the full length, 2^m - 1 + extended).  .m, .n, .n_i, .extended, .k = n_i - 2 m,
+    .rate = k / n.  EbchCode(7) is the extended (128, 113) word, d = 6.  ValueError outside the envelope: m in 4 .. 8, 2 m < n_i <= 2^m - 1.
+    t = 3 and beyond are out of scope."""
+
+    def __init__(self, m, n=None, extended=True):
+        import numbers
+        if not isinstance(m, numbers.Integral) or isinstance(m, bool) or (n is not None and (not isinstance(n, numbers.Integral) or isinstance(n, bool))):
+            raise ValueError(f"EbchCode takes integers, got m={m!r}, n={n!r}")
+        if not 4 <= int(m) <= 8:
+            raise ValueError(f"EbchCode: m in 4 .. 8, got {m!r}")
+        ext = int(bool(extended))
+        m, n = int(m), (1 << int(m)) - 1 + ext if n is None else int(n)
+        if not 2 * m < n - ext <= (1 << m) - 1:
+            raise ValueError(f"EbchCode(m={m}, extended={bool(ext)}): n in {2 * m + 1 + ext} .. {(1 << m) - 1 + ext}, got {n}")
+        self.m, self.n, self.n_i, self.extended = m, n, n - ext, bool(ext)
+        self.k = self.n_i - 2 * m
+        self.rate = self.k / self.n
+
+    def __repr__(self):
+        return f"EbchCode(m={self.m}, n={self.n}, extended={self.extended})"
+
+
+def ebch_code(m, extended=True, n=None):
+    """The EbchCode over GF(2^m), shortened to n bits in all (the parity bit included), in the style of hamming_code: ebch_code(5) is the extended
+    (32, 21) word, ebch_code(4, extended=False) the (15, 7) code, ebch_code(8, n=201) the inner 200 bits of the (255, 239) code and a parity bit."""
+    return EbchCode(m, n, extended)
+
+
 def chase_decode(llr, bits, code, t0=0, codewords=None, depth=None, patterns=4, payload=None, spread=True, want_stream=False):
-    """The soft-in / hard-out inner decoder in front of the hard-decision FEC (vaeq_chase_decode): Chase decoding of the HammingCode `code` over
+    """The soft-in / hard-out inner decoder in front of the hard-decision FEC (vaeq_chase_decode; vaeq_chase_bch_decode where `code` is an
+    EbchCode, whose test patterns are completed by bounded-distance decoding of up to two errors and the parity bit): Chase decoding of `code` over
     per-bit LLRs against the TX bits (no encoder: the rule acts on the error pattern).  llr, bits, t0, depth and the bit map as for ldpc_decode with
     n = code.n; codewords: per run, default the most that fit behind t0.  patterns = p in 0 .. min(6, n): the 2^p test patterns over the p least
     reliable positions, each completed by syndrome decoding; the candidate with the smallest sum of |llr| over its flips wins.  p = 0 is plain
@@ -1112,8 +1144,8 @@ def chase_decode(llr, bits, code, t0=0, codewords=None, depth=None, patterns=4, 
     undetected[R] (status 0 with pre_err > 0) int64).  want_stream: stream = dict(llr[R,1,C K] f32, bits[R,1,C K] int8), the decided payload
     bits as +-1.0 and their TX bits, codeword after codeword or, with spread, bit-interleaved over the run (payload bit i of codeword c at
     i C + c): a valid input of every decoder here with t0 = 0, which is how staircase_decode runs behind this one."""
-    if not isinstance(code, HammingCode):
-        raise ValueError(f"chase_decode takes a HammingCode, got {code!r}")
+    if not isinstance(code, (HammingCode, EbchCode)):
+        raise ValueError(f"chase_decode takes a HammingCode or an EbchCode, got {code!r}")
     if llr.shape != bits.shape or llr.dim() not in (3, 4):
         raise ValueError(f"expected llr and bits of one shape [R,2,2b,N] or [R,w,N], got {tuple(llr.shape)}, {tuple(bits.shape)}")
     dev, R, N = llr.device, llr.shape[0], llr.shape[-1]
@@ -1130,10 +1162,15 @@ def chase_decode(llr, bits, code, t0=0, codewords=None, depth=None, patterns=4, 
     out = torch.empty(R, Cn, 6, dtype=torch.int32, device=dev)
     s_llr = torch.empty(R, 1, Cn * K, dtype=torch.float32, device=dev) if want_stream else None
     s_bits = torch.empty(R, 1, Cn * K, dtype=torch.int8, device=dev) if want_stream else None
+    tail = (nat.ptr(llr), nat.ptr(bits, torch.int8), int(patterns), K, int(bool(spread)), nat.ptr(out, torch.int32), nat.ptr(s_llr),
+            nat.ptr(s_bits, torch.int8), nat.current_stream(dev))
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_chase_decode(R, C_, N, w, int(t0), 0 if depth is None else int(depth), n, code.r, code.cols.ctypes.data_as(C.c_void_p),
-                                              nat.ptr(llr), nat.ptr(bits, torch.int8), int(patterns), K, int(bool(spread)), nat.ptr(out, torch.int32),
-                                              nat.ptr(s_llr), nat.ptr(s_bits, torch.int8), nat.current_stream(dev)), "vaeq_chase_decode")
+        if isinstance(code, EbchCode):
+            nat.check(nat.lib().vaeq_chase_bch_decode(R, C_, N, w, int(t0), 0 if depth is None else int(depth), code.m, n, int(code.extended), *tail),
+                      "vaeq_chase_bch_decode")
+        else:
+            nat.check(nat.lib().vaeq_chase_decode(R, C_, N, w, int(t0), 0 if depth is None else int(depth), n, code.r,
+                                                  code.cols.ctypes.data_as(C.c_void_p), *tail), "vaeq_chase_decode")
     o = out.long()
     tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)
     ret = dict(status=o[..., 0], pre_err=o[..., 1], bit_err=o[..., 2], nflip=o[..., 3], erased=o[..., 4], pay_err=o[..., 5],
@@ -1149,15 +1186,20 @@ def chase_decode(llr, bits, code, t0=0, codewords=None, depth=None, patterns=4, 
 class ProductCode:
     """A product code for tpc_decode: blocks of col.n x row.n bits whose columns are words of the HammingCode `col` and whose rows are words of
     the HammingCode `row`.  .col, .row, .n = col.n row.n, .k = col.k row.k, .rate = k / n.  ValueError for anything but two HammingCodes, or a
-    block whose state passes the LDS bound of vaeq_tpc_decode (include/vaeq.h; the extended (128, 120)^2 block fits)."""
+    block whose state passes the LDS bound of vaeq_tpc_decode (include/vaeq.h; the extended (128, 120)^2 block fits).  Or two EbchCodes, which
+    may differ in m, n and extended (vaeq_tpc_bch_decode; the extended (128, 113)^2 block fits, the (256, 239)^2 block does not).  .bch says which.
+    One code of each kind is a ValueError: a mixed product is out of scope."""
 
     def __init__(self, col, row):
-        if not isinstance(col, HammingCode) or not isinstance(row, HammingCode):
-            raise ValueError(f"ProductCode takes two HammingCodes, got {col!r} and {row!r}")
+        self.bch = isinstance(col, EbchCode) and isinstance(row, EbchCode)
+        if not self.bch and (not isinstance(col, HammingCode) or not isinstance(row, HammingCode)):
+            raise ValueError(f"ProductCode takes two HammingCodes or two EbchCodes, got {col!r} and {row!r}")
         self.col, self.row = col, row
         self.n, self.k = col.n * row.n, col.k * row.k
         self.rate = self.k / self.n
-        if nat.lib().vaeq_tpc_lds_bytes(col.n, col.r, row.n, row.r) < 0:
+        fits = (nat.lib().vaeq_tpc_bch_lds_bytes(col.m, col.n, int(col.extended), row.m, row.n, int(row.extended)) if self.bch
+                else nat.lib().vaeq_tpc_lds_bytes(col.n, col.r, row.n, row.r))
+        if fits < 0:
             raise ValueError(f"ProductCode: the state of a block of {col.n} x {row.n} bits does not fit the LDS of a CU (vaeq_tpc_lds_bytes)")
 
 
@@ -1207,7 +1249,8 @@ def tpc_decode(llr, bits, code, t0=0, blocks=None, iters=4, patterns=4, alpha=No
                want_stream=False, want_ext=False, want_profile=False):
     """Post-FEC figures of per-bit LLRs behind a soft-decision turbo product code on the device (vaeq_tpc_decode): Chase-Pyndiah decoding of the
     ProductCode `code`, rows in the even half-iterations and columns in the odd ones, at most 2 iters of them, each word by a Chase decoder over
-    2^patterns test patterns whose competing candidates give the extrinsic values.  llr, bits, t0 and the bit map as for ldpc_decode with
+    2^patterns test patterns whose competing candidates give the extrinsic values (vaeq_tpc_bch_decode where the code holds two EbchCodes: the same
+    rule over double-error-correcting words).  llr, bits, t0 and the bit map as for ldpc_decode with
     n = code.n; blocks: per run, default the most that fit behind t0.  No encoder: the rule is stated on the LLRs towards the TX bits.
     alpha, beta: 2 iters values per half-iteration, default Pyndiah's schedules (0, .2, .3, .5, .7, .9, 1, 1 and .2, .4, .6, .8, 1, 1, continued
     with 1).  scale: per run ([R] tensor or a number), the unit of beta; default the float32 mean of |llr| over the run's tensor, non-finite
@@ -1243,13 +1286,16 @@ def tpc_decode(llr, bits, code, t0=0, blocks=None, iters=4, patterns=4, alpha=No
     ext = torch.empty(R, Cn, n, dtype=torch.float32, device=dev) if want_ext else None
     half = torch.empty(R, Cn, H, dtype=torch.int32, device=dev) if want_profile else None
     K1, K2 = prm["payload"]
+    tail = (nat.ptr(llr), nat.ptr(bits, torch.int8), prm["patterns"], prm["iters"], prm["alpha"].ctypes.data_as(C.c_void_p),
+            prm["beta"].ctypes.data_as(C.c_void_p), nat.ptr(scale) if R else None, prm["clip"], K1, K2, nat.ptr(out, torch.int32), nat.ptr(s_llr),
+            nat.ptr(s_bits, torch.int8), nat.ptr(ext), nat.ptr(half, torch.int32), nat.current_stream(dev))
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vaeq_tpc_decode(R, C_, N, w, int(t0), code.col.n, code.col.r, code.col.cols.ctypes.data_as(C.c_void_p), code.row.n,
-                                            code.row.r, code.row.cols.ctypes.data_as(C.c_void_p), nat.ptr(llr), nat.ptr(bits, torch.int8),
-                                            prm["patterns"], prm["iters"], prm["alpha"].ctypes.data_as(C.c_void_p),
-                                            prm["beta"].ctypes.data_as(C.c_void_p), nat.ptr(scale) if R else None, prm["clip"], K1, K2,
-                                            nat.ptr(out, torch.int32), nat.ptr(s_llr), nat.ptr(s_bits, torch.int8), nat.ptr(ext),
-                                            nat.ptr(half, torch.int32), nat.current_stream(dev)), "vaeq_tpc_decode")
+        if code.bch:
+            nat.check(nat.lib().vaeq_tpc_bch_decode(R, C_, N, w, int(t0), code.col.m, code.col.n, int(code.col.extended), code.row.m, code.row.n,
+                                                    int(code.row.extended), *tail), "vaeq_tpc_bch_decode")
+        else:
+            nat.check(nat.lib().vaeq_tpc_decode(R, C_, N, w, int(t0), code.col.n, code.col.r, code.col.cols.ctypes.data_as(C.c_void_p), code.row.n,
+                                                code.row.r, code.row.cols.ctypes.data_as(C.c_void_p), *tail), "vaeq_tpc_decode")
     o = out.long()
     tot = torch.full((R,), float(max(C_ * n, 1)), dtype=torch.float64, device=dev)
     ret = dict(iters=o[..., 0], ok=o[..., 1], bit_err=o[..., 2], pre_err=o[..., 3], erased=o[..., 4], pay_err=o[..., 5], nstat2=o[..., 6],
@@ -1270,12 +1316,12 @@ INNER_KEYS = ("code", "patterns", "depth", "payload", "spread")
 
 
 def resolve_inner(inner):
-    """The inner= dict(code=HammingCode, patterns=4, depth=None, payload=None, spread=True) of a fec= with a StaircaseCode, its defaults filled in.
-    ValueError for an unknown key, a missing code or one that is no HammingCode, patterns outside 0 .. min(6, n), a payload outside 1 .. n (or a
+    """The inner= dict(code=HammingCode or EbchCode, patterns=4, depth=None, payload=None, spread=True) of a fec= with a StaircaseCode, its defaults
+    filled in.  ValueError for an unknown key, a missing code or one of another kind, patterns outside 0 .. min(6, n), a payload outside 1 .. n (or a
     code without a payload bit where none is given), a depth below 1."""
     import numbers
-    if not isinstance(inner, dict) or set(inner) - set(INNER_KEYS) or not isinstance(inner.get("code"), HammingCode):
-        raise ValueError(f"inner takes a dict of {', '.join(INNER_KEYS)} with a HammingCode under code; got {sorted(inner) if isinstance(inner, dict) else inner!r}")
+    if not isinstance(inner, dict) or set(inner) - set(INNER_KEYS) or not isinstance(inner.get("code"), (HammingCode, EbchCode)):
+        raise ValueError(f"inner takes a dict of {', '.join(INNER_KEYS)} with a HammingCode or an EbchCode under code; got {sorted(inner) if isinstance(inner, dict) else inner!r}")
     code = inner["code"]
     patterns, payload, depth = inner.get("patterns", 4), inner.get("payload"), inner.get("depth")
     payload = code.k if payload is None else payload
@@ -1337,11 +1383,12 @@ def fec_figures(llr, fec):
     fixed, outer; code and window required): max_iter, depth and quant are a ValueError there, as window, iters, test and fixed are with an
     LdpcCode.  fixed = dict(bits, ...), quant's format, is the window decoder's quant=: fixed point, vaeq_ldpc_sc_decode_q.  With a StaircaseCode
     under code it is staircase_decode, hard-decision FEC, under fec = dict(code, window, t0, iters; code and window required); every other key
-    is a ValueError there, but for inner = dict(code=HammingCode, patterns=4, depth=None, payload=None, spread=True): the concatenated scheme,
+    is a ValueError there, but for inner = dict(code=HammingCode or EbchCode, patterns=4, depth=None, payload=None, spread=True): the concatenated scheme,
     chase_decode on the LLRs behind t0 and the staircase code on its payload stream from 0 (as many chains as fit the C K stream bits).  The
     staircase's dict comes back with BER_pre the inner decoder's -- the channel's, what a sweep's BER_pre_fec column means -- and the inner
-    decoder's dict under "inner".  With a ProductCode under code it is tpc_decode, the soft-decision turbo product decoder, under fec = dict(code,
-    t0, iters, patterns, alpha, beta, scale, clip; all but code optional); every other key is a ValueError there."""
+    decoder's dict under "inner".  With a ProductCode (of two HammingCodes or of two EbchCodes) under code it is tpc_decode, the soft-decision turbo
+    product decoder, under fec = dict(code, t0, iters, patterns, alpha, beta, scale, clip; all but code optional); every other key is a
+    ValueError there."""
     check_fec(fec)
     if isinstance(fec["code"], ProductCode):
         return tpc_decode(llr["llr"], llr["bits"], **{k: v for k, v in fec.items() if v is not None})
