@@ -164,6 +164,36 @@ struct CellCarry {
 static_assert(CellCarry::fir_exact(100, 25), "B = 100: the FIR / dL/dU stages must carry exactly the cells the next stage would have read, inside x / e");
 static_assert(CellCarry::d3_exact(100, 25), "B = 100: the D stages must carry exactly the mu cells the next stage would have read, inside U");
 
+// The taps of the FIR and dL/dU loops arrive as 16-byte reads (lds4), two neighbouring taps each: the FIR's tap k is the float4 Wt[p][k]; a dL/dU stage g
+// reads the pairs (4g, 4g + 1), (4g + 2, 4g + 3) of four Ht rows.  (The D loop keeps its 8-byte tap reads: measured, 16-byte reads there add nothing to
+// the other two)
+// Aligned by construction: wave_layout rounds every array up to 16 bytes, so lay.W and lay.H are multiples of 16 for every shape, and a pair starts at
+// the even tap 4g (+ 2).  What can fail is held here: every Ht row starts 16-byte aligned only if its MP = M + 1 taps of 8 bytes are an even number, and
+// no pair may leave its row (the last one ends at tap 4 (G - 1) + 3 <= M - 1; the left-over tap stays an 8-byte read).
+struct Tap16 {
+    static constexpr bool exact(int M) { return (M + 1) % 2 == 0 && 4 * (M / 4 - 1) + 3 <= M - 1; }
+};
+static_assert(Tap16::exact(25), "M = 25: every Ht row must start 16-byte aligned and every 16-byte tap read must end inside its row");
+
+// MACs whose tap is one half of a 16-byte read (lds4).  The low pair is left to the compiler; the high pair takes the explicit form (cmac16), or the backend
+// copies its second dword before the broadcast.  (All MACs of a loop as asm statements is no alternative: the hazard recognizer cannot look into a statement
+// and puts an s_nop 0 between two of them wherever it cannot rule out a forwarding hazard -- two per trip in the dL/dU loop.)
+template <bool FIRST, bool HI>
+__device__ __forceinline__ void cmacf_half(cacc &c, v2f t, v2f v)
+{
+    if constexpr (HI) cmacf16<FIRST>(c, t, v);
+    else cmacf<FIRST>(c, t, v);
+}
+// the two taps a, b of one 16-byte read (its low and its high pair) on one sample.  BOTH: the low pair's MAC in the explicit form too -- the FIR loop needs
+// it (left to the compiler, the low pairs that live across the loop's back edge are split into dwords and copied: four v_mov_b32 at the end of every trip)
+template <bool FIRST, bool BOTH = false>
+__device__ __forceinline__ void mac2(cacc (&c)[2], v2f a, v2f b, v2f x)
+{
+    cmacf_half<FIRST, BOTH>(c[0], a, x);
+    cmacf_half<FIRST, true>(c[1], b, x);
+}
+template <int N> using tapc = std::integral_constant<int, N>;
+
 // pair_fir (below) for the baked B = 100 kernel: the same stages, but stage g >= 1 takes its first two sample cells from the registers of stage g - 1
 // (12 reads per 32 packed FMAs instead of 14) and the left-over tap its first cell from the last stage's.  Every output keeps its terms, their order and
 // its even / odd sub-chains; stage 0 is pair_fir's, statement for statement (it decides which first product is rounded on its own).
@@ -171,11 +201,11 @@ template <int M, bool INIT>
 __device__ __forceinline__ void pair_fir_carry(cacc (&acc)[2][2], cacc (&acc2)[2][2], const float2 *xp, int Lph, const float4 *wq)
 {
     constexpr int G = M / 4;
-    auto tapA = [&](int k) -> v2f { return lds2(reinterpret_cast<const float2 *>(wq + k)); };
-    auto tapB = [&](int k) -> v2f { return lds2(reinterpret_cast<const float2 *>(wq + k) + 1); };
+    // tap k = the float4 (wr[o0], wi[o0], wr[o1], wi[o1]): one 16-byte read, its halves (o = 0, o = 1) feeding the MACs in place (mac2)
+    auto tap = [&](int k, v2f &a, v2f &b) { const v4f q = lds4(wq + k); a = lo2(q); b = hi2(q); };
     auto taps = [&](int g, v2f (&r)[14]) {
 #pragma unroll
-        for (int t = 0; t < 4; t++) { r[6 + 2 * t] = tapA(4 * g + t); r[7 + 2 * t] = tapB(4 * g + t); }
+        for (int t = 0; t < 4; t++) tap(4 * g + t, r[6 + 2 * t], r[7 + 2 * t]);
     };
     auto loadF = [&](v2f (&r)[14]) {
         r[0] = lds2(xp); r[1] = lds2(xp + Lph); r[2] = lds2(xp + 2 * Lph); r[3] = lds2(xp + 3 * Lph); r[4] = lds2(xp + 1); r[5] = lds2(xp + Lph + 1);
@@ -184,25 +214,33 @@ __device__ __forceinline__ void pair_fir_carry(cacc (&acc)[2][2], cacc (&acc2)[2
     auto loadM = [&](int g, v2f (&r)[14]) { r[2] = lds2(xp + g + 2 * Lph); r[3] = lds2(xp + g + 3 * Lph); taps(g, r); };
     auto loadL = [&](int g, v2f (&r)[14]) { r[4] = lds2(xp + g + 1); r[5] = lds2(xp + g + Lph + 1); };
     auto fma0 = [&](const v2f (&r)[14]) {
-        cmacf<INIT>(acc[0][0], r[6], r[0]); cmacf<INIT>(acc[0][1], r[7], r[0]); cmacf<INIT>(acc[1][0], r[6], r[2]); cmacf<INIT>(acc[1][1], r[7], r[2]);
-        cmacf<INIT>(acc2[0][0], r[8], r[1]); cmacf<INIT>(acc2[0][1], r[9], r[1]); cmacf<INIT>(acc2[1][0], r[8], r[3]); cmacf<INIT>(acc2[1][1], r[9], r[3]);
-        cmac(acc[0][0], r[10], r[2]); cmac(acc[0][1], r[11], r[2]); cmac(acc[1][0], r[10], r[4]); cmac(acc[1][1], r[11], r[4]);
-        cmac(acc2[0][0], r[12], r[3]); cmac(acc2[0][1], r[13], r[3]); cmac(acc2[1][0], r[12], r[5]); cmac(acc2[1][1], r[13], r[5]);
+        // INIT: a chain starts as the sum of two products, taps 0 and 2 (acc2: 1 and 3).  The backend contracts that sum as fma(first, round(second)): the SECOND
+        // product is the one rounded alone (pinned bits), so the explicit form multiplies it first and adds the first term to it
+        if constexpr (INIT) {
+            mac2<true, true>(acc[0], r[10], r[11], r[2]); mac2<true, true>(acc[1], r[10], r[11], r[4]);
+            mac2<true, true>(acc2[0], r[12], r[13], r[3]); mac2<true, true>(acc2[1], r[12], r[13], r[5]);
+        }
+        mac2<false, true>(acc[0], r[6], r[7], r[0]); mac2<false, true>(acc[1], r[6], r[7], r[2]);
+        mac2<false, true>(acc2[0], r[8], r[9], r[1]); mac2<false, true>(acc2[1], r[8], r[9], r[3]);
+        if constexpr (!INIT) {
+            mac2<false, true>(acc[0], r[10], r[11], r[2]); mac2<false, true>(acc[1], r[10], r[11], r[4]);
+            mac2<false, true>(acc2[0], r[12], r[13], r[3]); mac2<false, true>(acc2[1], r[12], r[13], r[5]);
+        }
     };
     auto stage = [&](const v2f (&r)[14], const v2f (&p)[14], auto mid) {          // p[4], p[5]: this stage's cells j = 0, 1
-        cmac(acc[0][0], r[6], p[4]); cmac(acc[0][1], r[7], p[4]); cmac(acc2[0][0], r[8], p[5]); cmac(acc2[0][1], r[9], p[5]);
+        mac2<false, true>(acc[0], r[6], r[7], p[4]); mac2<false, true>(acc2[0], r[8], r[9], p[5]);
         // (volatile: stays in front of the loads into p[4], p[5])
         asm volatile("" : "+v"(acc[0][0].a), "+v"(acc[0][0].b), "+v"(acc[0][1].a), "+v"(acc[0][1].b), "+v"(acc2[0][0].a), "+v"(acc2[0][0].b),
                      "+v"(acc2[0][1].a), "+v"(acc2[0][1].b));
         mid();
-        cmac(acc[1][0], r[6], r[2]); cmac(acc[1][1], r[7], r[2]); cmac(acc2[1][0], r[8], r[3]); cmac(acc2[1][1], r[9], r[3]);
-        cmac(acc[0][0], r[10], r[2]); cmac(acc[0][1], r[11], r[2]); cmac(acc[1][0], r[10], r[4]); cmac(acc[1][1], r[11], r[4]);
-        cmac(acc2[0][0], r[12], r[3]); cmac(acc2[0][1], r[13], r[3]); cmac(acc2[1][0], r[12], r[5]); cmac(acc2[1][1], r[13], r[5]);
+        mac2<false, true>(acc[1], r[6], r[7], r[2]); mac2<false, true>(acc2[1], r[8], r[9], r[3]);
+        mac2<false, true>(acc[0], r[10], r[11], r[2]); mac2<false, true>(acc[1], r[10], r[11], r[4]);
+        mac2<false, true>(acc2[0], r[12], r[13], r[3]); mac2<false, true>(acc2[1], r[12], r[13], r[5]);
     };
     constexpr int k = 4 * G;                                                       // the left-over tap (even: into acc)
     v2f ta, tb, xb;
-    auto pre = [&]() { ta = tapA(k); tb = tapB(k); xb = lds2(xp + ((k + 2) & 3) * Lph + ((k + 2) >> 2)); };
-    auto post = [&](const v2f (&r)[14]) { cmac(acc[0][0], ta, r[4]); cmac(acc[0][1], tb, r[4]); cmac(acc[1][0], ta, xb); cmac(acc[1][1], tb, xb); };
+    auto pre = [&]() { tap(k, ta, tb); xb = lds2(xp + ((k + 2) & 3) * Lph + ((k + 2) >> 2)); };
+    auto post = [&](const v2f (&r)[14]) { mac2<false, true>(acc[0], ta, tb, r[4]); mac2<false, true>(acc[1], ta, tb, xb); };
     pipe2_carry<14>(G, loadF, loadM, loadL, fma0, stage, pre, post);
 }
 
@@ -259,9 +297,12 @@ __device__ __forceinline__ void pair_du(cacc (&acc)[2][2][2], const float2 *ep, 
 {
     constexpr int G = M / 4;
     // operands of one chi for taps 4g..4g+3: 6 samples c' = 4g..4g+5 and the 4 taps of the rows nu = 0, 1 -- 14 independent LDS reads, 32 packed FMAs
-    auto load1 = [&](int chi, int g, v2f *x) {
+    auto cells = [&](int chi, int g, v2f *x) {
         const float2 *xg = ep + chi * 4 * Lph + g;
         x[0] = lds2(xg); x[1] = lds2(xg + Lph); x[2] = lds2(xg + 2 * Lph); x[3] = lds2(xg + 3 * Lph); x[4] = lds2(xg + 1); x[5] = lds2(xg + Lph + 1);
+    };
+    auto load1 = [&](int chi, int g, v2f *x) {
+        cells(chi, g, x);
 #pragma unroll
         for (int t = 0; t < 4; t++) { x[6 + 2 * t] = lds2(ht + (chi * 2 + 0) * MP + 4 * g + t); x[7 + 2 * t] = lds2(ht + (chi * 2 + 1) * MP + 4 * g + t); }
     };
@@ -275,15 +316,35 @@ __device__ __forceinline__ void pair_du(cacc (&acc)[2][2][2], const float2 *ep, 
         // 24 reads per 64 packed FMAs instead of 28), the left-over tap its first cell from the last stage's.  Every chain keeps its terms and their order
         // (tap 4g .. 4g + 3); stage 0 is the plain one, statement for statement.  Per chi -- the carry restarts where the array changes
         static_assert(MERGE && M % 4 == 1, "the carried form is the merged one, with one tap left over");
-        auto loadF = [&](v2f (&r)[28]) { load1(0, 0, r); load1(1, 0, r + 14); };
+        // The taps 4g .. 4g + 3 of a row are two 16-byte aligned pairs (Tap16): two 16-byte reads per row, their halves feeding the MACs in place
+        auto taps = [&](int chi, int g, v2f *x) {
+#pragma unroll
+            for (int nu = 0; nu < 2; nu++)
+#pragma unroll
+                for (int t = 0; t < 4; t += 2) {
+                    const v4f q = lds4(ht + (chi * 2 + nu) * MP + 4 * g + t);
+                    x[6 + nu + 2 * t] = lo2(q); x[8 + nu + 2 * t] = hi2(q);
+                }
+        };
+        // tap 4g + t of both rows on both symbols (s0, s1: their cells); the odd taps are the high pairs of their reads
+        auto fmat = [&](int chi, const v2f *x, auto tc, auto first, v2f s0, v2f s1) {
+            constexpr int t = decltype(tc)::value;
+            constexpr bool F = decltype(first)::value, HI = t & 1;
+            cmacf_half<F, HI>(acc[chi][0][0], x[6 + 2 * t], s0); cmacf_half<F, HI>(acc[chi][0][1], x[7 + 2 * t], s0);
+            cmacf_half<F, HI>(acc[chi][1][0], x[6 + 2 * t], s1); cmacf_half<F, HI>(acc[chi][1][1], x[7 + 2 * t], s1);
+        };
+        auto fmao = [&](int chi, const v2f *x, auto tc, auto first) { fmat(chi, x, tc, first, x[decltype(tc)::value], x[decltype(tc)::value + 2]); };   // its own cells
+        auto loadF = [&](v2f (&r)[28]) {
+#pragma unroll
+            for (int chi = 0; chi < 2; chi++) { cells(chi, 0, r + 14 * chi); taps(chi, 0, r + 14 * chi); }
+        };
         auto loadM = [&](int g, v2f (&r)[28]) {
 #pragma unroll
             for (int chi = 0; chi < 2; chi++) {
                 const float2 *xg = ep + chi * 4 * Lph + g;
                 v2f *x = r + 14 * chi;
                 x[2] = lds2(xg + 2 * Lph); x[3] = lds2(xg + 3 * Lph);
-#pragma unroll
-                for (int t = 0; t < 4; t++) { x[6 + 2 * t] = lds2(ht + (chi * 2 + 0) * MP + 4 * g + t); x[7 + 2 * t] = lds2(ht + (chi * 2 + 1) * MP + 4 * g + t); }
+                taps(chi, g, x);
             }
         };
         auto loadL = [&](int g, v2f (&r)[28]) {
@@ -291,21 +352,18 @@ __device__ __forceinline__ void pair_du(cacc (&acc)[2][2][2], const float2 *ep, 
             for (int chi = 0; chi < 2; chi++) { r[14 * chi + 4] = lds2(ep + chi * 4 * Lph + g + 1); r[14 * chi + 5] = lds2(ep + chi * 4 * Lph + g + Lph + 1); }
         };
         auto fma0 = [&](const v2f (&r)[28]) {
-            fma1(0, r, 0, std::true_type{}); fma1(1, r + 14, 0, std::true_type{});
-#pragma unroll
-            for (int t = 1; t < 4; t++) { fma1(0, r, t, std::false_type{}); fma1(1, r + 14, t, std::false_type{}); }
+            // a chain starts as the sum of the products of taps 0 and 1, which the backend contracts as fma(tap 0, round(tap 1)): the product of tap 1 (the high
+            // pair, explicit form) is the one rounded alone (pinned bits), so it comes first and tap 0's term is added to it
+            fmao(0, r, tapc<1>{}, std::true_type{}); fmao(1, r + 14, tapc<1>{}, std::true_type{});
+            fmao(0, r, tapc<0>{}, std::false_type{}); fmao(1, r + 14, tapc<0>{}, std::false_type{});
+            fmao(0, r, tapc<2>{}, std::false_type{}); fmao(1, r + 14, tapc<2>{}, std::false_type{});
+            fmao(0, r, tapc<3>{}, std::false_type{}); fmao(1, r + 14, tapc<3>{}, std::false_type{});
         };
         auto stage = [&](const v2f (&r)[28], const v2f (&p)[28], auto) {           // p[14 chi + 4], p[14 chi + 5]: this stage's cells j = 0, 1
-#pragma unroll
-            for (int t = 0; t < 2; t++)
-#pragma unroll
-                for (int chi = 0; chi < 2; chi++) {
-                    const v2f *x = r + 14 * chi;
-                    cmac(acc[chi][0][0], x[6 + 2 * t], p[14 * chi + 4 + t]); cmac(acc[chi][0][1], x[7 + 2 * t], p[14 * chi + 4 + t]);
-                    cmac(acc[chi][1][0], x[6 + 2 * t], x[t + 2]); cmac(acc[chi][1][1], x[7 + 2 * t], x[t + 2]);
-                }
-#pragma unroll
-            for (int t = 2; t < 4; t++) { fma1(0, r, t, std::false_type{}); fma1(1, r + 14, t, std::false_type{}); }
+            fmat(0, r, tapc<0>{}, std::false_type{}, p[4], r[2]); fmat(1, r + 14, tapc<0>{}, std::false_type{}, p[14 + 4], r[14 + 2]);
+            fmat(0, r, tapc<1>{}, std::false_type{}, p[5], r[3]); fmat(1, r + 14, tapc<1>{}, std::false_type{}, p[14 + 5], r[14 + 3]);
+            fmao(0, r, tapc<2>{}, std::false_type{}); fmao(1, r + 14, tapc<2>{}, std::false_type{});
+            fmao(0, r, tapc<3>{}, std::false_type{}); fmao(1, r + 14, tapc<3>{}, std::false_type{});
         };
         constexpr int k = 4 * G;                                                   // the left-over tap
         v2f ta[2], tb[2], xb[2];
@@ -584,7 +642,7 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     constexpr bool PIPE = VAEQ_PIPE && FIXL;               // run-time layouts keep more addresses live: there one operand set,
     constexpr bool WIDE = FIXL;                            // ... 8 accumulator chains and one chi at a time in dL/dU (fits the register file)
     // B100: the baked B = 100 kernel on one wave, the shape that is measured step by step and whose bits are pinned (tests/test_dp_wave_bits_gpu.py).
-    // It alone takes seven forms; every other instantiation keeps the plain one, instruction for instruction:
+    // It alone takes eight forms; every other instantiation keeps the plain one, instruction for instruction:
     //  * the halves of the two tap gradients meet on v_permlane32_swap (half_sum2: one swap per kept value, one packed add per pair) instead of 16 ds_bpermute_b32
     //    through __shfl_xor(., 32) per step: the same two addends per sum, bitwise the same taps; 8.09 -> 7.91 ms (profiles/r04/kernel_variants_ab.txt)
     //  * the next window's prefetch is issued without a branch around it (the launch's very last step fetches with every lane out of range: zeros, no
@@ -607,6 +665,10 @@ __global__ __launch_bounds__(64 * NW, VAEQ_WPS) void dp_wave_kernel(const vaeq_d
     //    the half combines and both Adam updates work on (re, im) register pairs (half_sum2, adam_update_fast2), and every lane runs the updates, only what
     //    leaves the lane being masked: 101 of the step's 1621 straight-line vector instructions were moves, selects and zeros for this
     //    (profiles/r09/kernel_variants_ab.txt)
+    //  * (M = 25) the taps of the FIR and dL/dU loops arrive as 16-byte reads, two neighbouring taps each (lds4, Tap16: the float4 of a FIR tap, an aligned pair
+    //    of an Ht row), and the MACs on a read's high pair (FIR: on both pairs) are the two v_pk_fma_f32 the backend emits for them anyway, written out with their op_sel (cmac16), so
+    //    that no dword is copied on the way: 100 instead of 200 tap reads per wave-step for the same LDS cycles, every output's chain in its old order
+    //    (profiles/r10/kernel_variants_ab.txt)
     constexpr bool B100 = BT == 100 && NW == 1;
     constexpr bool CARRY = B100 && M == 25 && PIPE && WIDE;
     constexpr int QAUX = B100 ? 2 : 0;                         // cache policy of the q stores

@@ -83,6 +83,35 @@ __device__ __forceinline__ v2f lds2(const float *p) { return *(lds_cv2f *)p; }
 typedef const volatile __attribute__((address_space(3))) float lds_cvf;
 __device__ __forceinline__ float ldsv(const float *p) { return *(lds_cvf *)p; }
 __device__ __forceinline__ float2 f2(v2f v) { return make_float2(v.x, v.y); }
+// Two TAPS that are 16-byte aligned neighbours in LDS, read from a wave-uniform address as ONE ds_read_b128 (volatile: never split, never fused): the same
+// four LDS cycles as the two ds_read_b64, half the instructions the wave issues and half the entries against the 4-bit lgkmcnt.  lo2 / hi2 are the two
+// 8-byte halves of the result where the read put them (subregisters, no copy).  A packed FMA can broadcast either dword of either half (op_sel on the
+// even-aligned pair), but the backend copies the 4th dword with a v_mov_b32 before it does: cmac16 / cmul16 / cmacf16 are cmac / cmul / cmacf with the
+// two instructions the backend emits for them spelled out, operand for operand -- d = t.x v + d with op_sel_hi:[0,1,1], d = t.y v + d with
+// op_sel:[1,0,0] -- so that a half of a 16-byte read feeds them in place.  The product that starts a chain is the matching v_pk_mul_f32.  Same operations
+// in the same order as the C++ forms, hence the same bits.  Used by the baked B = 100, M = 25 DP kernel alone.
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef const volatile __attribute__((address_space(3))) v4f lds_cv4f;
+__device__ __forceinline__ v4f lds4(const float4 *p) { return *(lds_cv4f *)p; }
+__device__ __forceinline__ v4f lds4(const float2 *p) { return *(lds_cv4f *)p; }
+__device__ __forceinline__ v2f lo2(v4f q) { return __builtin_shufflevector(q, q, 0, 1); }
+__device__ __forceinline__ v2f hi2(v4f q) { return __builtin_shufflevector(q, q, 2, 3); }
+__device__ __forceinline__ void cmac16(cacc &c, v2f t, v2f v)
+{
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(c.a) : "v"(t), "v"(v));
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0]" : "+v"(c.b) : "v"(t), "v"(v));
+}
+__device__ __forceinline__ void cmul16(cacc &c, v2f t, v2f v)
+{
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(c.a) : "v"(t), "v"(v));
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0]" : "=v"(c.b) : "v"(t), "v"(v));
+}
+template <bool FIRST>
+__device__ __forceinline__ void cmacf16(cacc &c, v2f t, v2f v)
+{
+    if constexpr (FIRST) cmul16(c, t, v);
+    else cmac16(c, t, v);
+}
 // lds2 where the kernel can afford it (V), an ordinary load (free to fuse / reorder: fewer live registers) where it is register-starved
 template <bool V>
 __device__ __forceinline__ v2f lds2_if(const float2 *p)
