@@ -169,7 +169,7 @@ def test_ldpc_decode_outer_on_real_llrs(depth, quant):
 
 def test_fec_figures_in_chunks(monkeypatch):
     """With OUTER_POST_BYTES small enough for one run per chunk (three chunks at R = 3), fec_figures returns the unchunked figures."""
-    from vae_equalizer_amd import engine as E
+    from vae_equalizer_amd import fec as E                     # the module fec_figures resolves ldpc_decode and OUTER_POST_BYTES in
     name, w, t0 = "array-3-6-7", 12, 11
     shifts, Z = M.CODES[name]
     llr, bits = M.case(name, w, t0, 2)

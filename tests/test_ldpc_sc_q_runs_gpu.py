@@ -60,15 +60,15 @@ def test_check_fec_takes_fixed_with_an_sc_code_only():
 def test_fec_figures_sizes_its_chunks_by_the_int16_post(monkeypatch):
     """With an outer code fec_figures walks the runs in chunks whose post stays within OUTER_POST_BYTES: 2 bytes per value with fixed, 4 without,
     and the figures are those of one call either way."""
-    from vae_equalizer_amd import engine
+    from vae_equalizer_amd import engine, fec as fec_module     # fec_figures resolves ldpc_sc_decode and OUTER_POST_BYTES in fec
     from vae_equalizer_amd.engine import BchCode
     llr, bits = (torch.from_numpy(x).cuda() for x in S.grid_case(12, 8, 7, 1))
     fec = dict(_fec(t0=7, iters=1), outer=dict(code=BchCode(7, 2)))
     whole = engine.fec_figures(dict(llr=llr, bits=bits), fec)
     calls = []
-    real = engine.ldpc_sc_decode
-    monkeypatch.setattr(engine, "ldpc_sc_decode", lambda L, *a, **kw: (calls.append(L.shape[0]), real(L, *a, **kw))[1])
-    monkeypatch.setattr(engine, "OUTER_POST_BYTES", 2 * S.C_ * N_CHAIN * 2)       # room for the int16 post of two runs, the float32 post of one
+    real = fec_module.ldpc_sc_decode
+    monkeypatch.setattr(fec_module, "ldpc_sc_decode", lambda L, *a, **kw: (calls.append(L.shape[0]), real(L, *a, **kw))[1])
+    monkeypatch.setattr(fec_module, "OUTER_POST_BYTES", 2 * S.C_ * N_CHAIN * 2)   # room for the int16 post of two runs, the float32 post of one
     parts = engine.fec_figures(dict(llr=llr, bits=bits), fec)
     assert calls == [2, 1]
     calls.clear()

@@ -68,7 +68,7 @@ n1 = (lmmse_filter_order - 1) // 2 + 1
 N_SHIFT_LMMSE, N_SHIFT_DFE = 21, 24                    # find_shift_symb lags (:280, :292)
 
 info_metrics = False    # True: main() also returns the info dicts of both curves (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp)
-fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=engine.BchCode, ...) puts engine.bch_outer behind it, and the .mat also gains BER_outer and FER_outer; code=engine.ScLdpcCode takes window, iters and test in place of max_iter, depth and quant and decodes with engine.ldpc_sc_decode): main() also returns engine.ldpc_decode's figures of both curves' LLRs
+fec_metrics = None      # dict(code=fec.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=fec.BchCode, ...) puts fec.bch_outer behind it, and the .mat also gains BER_outer and FER_outer; code=fec.ScLdpcCode takes window, iters and test in place of max_iter, depth and quant and decodes with fec.ldpc_sc_decode): main() also returns fec.ldpc_decode's figures of both curves' LLRs
 base_seed = None        # int -> reproducible frames (the reference's stream under the same seed); None = like the reference
 generator = None        # None: "hip" (on-device generator vaeq_gen_awgn) for unseeded sweeps, "numpy" (reference-faithful host simulator) when base_seed is set
 
@@ -194,16 +194,17 @@ def run_dfe_batch(SNRs, num_epochs, N_valid, mod="64-QAM", h_orig=None, nu=0.027
     (engine.awgn_dfe_soft) at shift_dfe, demapped at var = 10^(-SNR/10), the VAE-LE's of the same SNR (func_VAELE_MQAM_shaping.py:272).
     With want_llr also llr_mmse and llr_dfe, each dict(llr[num_snr, num_epochs, 2b, N_valid] f32, bits[num_snr, num_epochs, 2b, N_valid] int8,
     hyp[num_snr, num_epochs]) ON THE DEVICE: engine.awgn_track_llr on the same two tracks, shifts, edge and var under the hypothesis of
-    awgn_track_info on them (want_info's call, when that is on), and engine.label_bits of the TX data.  All frames go through one launch, so
+    awgn_track_info on them (want_info's call, when that is on), and fec.label_bits of the TX data.  All frames go through one launch, so
     all of them are returned; the two dicts share one bits tensor: num_snr x num_epochs x 2b x N_valid x (2 x 4 + 1) bytes (64-QAM, 15 SNRs x
     10 epochs x 10 000 symbols: 81 MB).
     Every other output is the same with and without it.
-    With fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) also fec_mmse and fec_dfe ON THE DEVICE: engine.ldpc_decode's
+    With fec = dict(code=fec.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) also fec_mmse and fec_dfe ON THE DEVICE: fec.ldpc_decode's
     figures of those LLRs (computed for it; llr_* itself is returned only with want_llr), all num_snr x num_epochs frames as the run axis of one
     call per curve: the counters [num_snr, num_epochs, C], the rates [num_snr, num_epochs].  A quant=dict(bits, scale=None, app_bits=None, num=6, beta=0) in fec decodes in
     fixed point (vaeq_ldpc_decode_q; no alpha then).  A bad fec dict is a ValueError before anything is allocated or launched."""
     from .dp_runs import default_device, fresh_seed, resolve_generator
-    from .engine import awgn_dfe, awgn_dfe_soft, awgn_lmmse_eval, awgn_track_info, awgn_track_llr, check_fec, fec_figures, label_bits
+    from .engine import awgn_dfe, awgn_dfe_soft, awgn_lmmse_eval, awgn_track_info, awgn_track_llr
+    from .fec import check_fec, fec_figures, label_bits
     check_fec(fec)
     need_llr = want_llr or fec is not None
     device = default_device() if device is None else torch.device(device)

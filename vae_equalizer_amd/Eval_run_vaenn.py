@@ -24,7 +24,7 @@ savePATH = ""
 base_seed = None        # int -> reproducible runs; None = like the reference
 info_metrics = False    # True: the .mat gains GMI, NGMI, AIR (bit per 2-D symbol) and BER (pre-FEC), each shaped like SER
 generator = "hip"       # "hip": on-device channel model; "numpy": host restatement per run
-fec_metrics = None      # dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=engine.BchCode, ...) puts engine.bch_outer behind it, and the .mat also gains BER_outer and FER_outer): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords; with code=engine.ScLdpcCode, which takes window, iters and test in place of max_iter, depth and quant: mean over the chains of a chain's total iteration count, and FER is the share of chains with errors) of the last validation's LLRs, each shaped like SER without its last axis
+fec_metrics = None      # dict(code=fec.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None, quant=None, outer=None; quant=dict(bits=5) decodes in fixed point and takes no alpha; outer=dict(code=fec.BchCode, ...) puts fec.bch_outer behind it, and the .mat also gains BER_outer and FER_outer): the .mat gains BER_post, FER, BER_pre_fec and fec_iters (mean over codewords; with code=fec.ScLdpcCode, which takes window, iters and test in place of max_iter, depth and quant: mean over the chains of a chain's total iteration count, and FER is the share of chains with errors) of the last validation's LLRs, each shaped like SER without its last axis
 INFO_KEYS = ("GMI", "NGMI", "AIR", "BER")
 
 

@@ -5,7 +5,8 @@ import torch
 
 from . import channel as ch
 from .dp_runs import _host_pool, fresh_seed
-from .engine import INFO_FLOAT, INFO_INT, check_fec, fec_figures
+from .engine import INFO_FLOAT, INFO_INT
+from .fec import check_fec, fec_figures
 
 
 def check_generator(generator):
@@ -29,8 +30,8 @@ def run_awgn_epochs(R, device, num_epochs, epe, N_train, N_valid, train, validat
               unseeded runs share numpy's global stream and stay sequential).
     Epoch e is evaluated when e % epe == 0 and e // epe < num_epochs // epe (:308-318).  Nothing is read back before the end unless verbose.
     Returns SER_valid[R, num_epochs // epe] (CPU float32); with want_info (SER_valid, info), info[k][R, num_epochs // epe] on the CPU.
-    want_llr / fec (engine.fec_figures' dict): (SER_valid, info or None, extras) with extras["llr"] = the last evaluated validation's llr dict
-    (only with want_llr) and extras["fec"] = engine.ldpc_decode's figures of it (only with fec), both on the device.  A quant dict in fec decodes in fixed point (vaeq_ldpc_decode_q).  A bad fec dict is a
+    want_llr / fec (fec.fec_figures' dict): (SER_valid, info or None, extras) with extras["llr"] = the last evaluated validation's llr dict
+    (only with want_llr) and extras["fec"] = fec.ldpc_decode's figures of it (only with fec), both on the device.  A quant dict in fec decodes in fixed point (vaeq_ldpc_decode_q).  A bad fec dict is a
     ValueError before anything is allocated or launched."""
     check_generator(generator)
     check_fec(fec)

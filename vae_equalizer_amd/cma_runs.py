@@ -15,7 +15,8 @@ from . import channel as ch
 from . import epilogue as epi
 from . import shared_funcs as sfun
 from .dp_runs import INFO_FLOAT, INFO_INT, DPRun, _host_pool, check_one_symb_rate, default_device, fresh_seed, resolve_generator  # noqa: F401
-from .engine import check_fec, cma, cpe, fec_figures, soft_demap
+from .engine import cma, cpe, soft_demap
+from .fec import check_fec, fec_figures
 
 N_CUT = 10   # symbols cut at both frame ends before the phase estimation (func_CMA_DP_MQAM_shaping.py:26,39)
 
@@ -25,8 +26,9 @@ def cma_frame_epilogue(out_const, data, amp, nu_sc, var, P=None, want_llr=False)
     (vaeq_cpe) + the two-stage epilogue in one HIP launch (vaeq_cma_epilogue; q is never materialised).  P[R,n] (the runs' per-axis pmf): also
     "info" = engine.cma_epilogue_info on the same y and the alignment just found (AIR, GMI, NGMI, BER, kept, sym_err, bit_err, hyp, each [R,2]).
     want_llr (needs P): also "llr" = dict(llr[R,2,2b,K-20] f32, bits[R,2,2b,K-20] int8, hyp[R,2]) on the device: engine.cma_epilogue_llr on the
-    same y and alignment under that info call's hypothesis, and engine.label_bits of the cut TX reference."""
-    from .engine import cma_epilogue, cma_epilogue_info, cma_epilogue_llr, label_bits
+    same y and alignment under that info call's hypothesis, and fec.label_bits of the cut TX reference."""
+    from .engine import cma_epilogue, cma_epilogue_info, cma_epilogue_llr
+    from .fec import label_bits
     y = cpe(out_const[..., N_CUT:-N_CUT].contiguous())                          # :39
     d = data[..., N_CUT:-N_CUT]
     res = cma_epilogue(y, d, amp, nu_sc, var)                                   # :40-52
@@ -72,9 +74,9 @@ def run_cma_batch(runs, mode, mod, sps, M_est, batch_len, N_train_max, num_frame
                like run_dp_batch's: engine.cma_epilogue_info after every frame's epilogue, on the runs' PCS pmf rows.
     want_llr:  also dict(llr[R,2,2b,N'] f32, bits[R,2,2b,N'] int8, hyp[R,2]) under "llr", on the device, for the LAST frame only, like
                run_dp_batch's (N' = N_train_max - 20, the [10:-10] cut the epilogue gets): engine.cma_epilogue_llr on that frame's alignment
-               under the winning hypothesis of one cma_epilogue_info call (want_info's, when that is on), and engine.label_bits of the cut TX
+               under the winning hypothesis of one cma_epilogue_info call (want_info's, when that is on), and fec.label_bits of the cut TX
                reference.  Every other output is the same with and without it.
-    fec:       dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75): also engine.ldpc_decode's figures of the LAST frame's LLRs (the pass
+    fec:       dict(code=fec.LdpcCode, t0=0, max_iter=20, alpha=0.75): also fec.ldpc_decode's figures of the LAST frame's LLRs (the pass
                want_llr runs; "llr" itself is returned only with want_llr) under "fec", on the device.  None: no output changes.
                quant=dict(bits, scale=None, app_bits=None, num=6, beta=0) in it decodes in fixed point (vaeq_ldpc_decode_q: what the scale of
                the LLRs costs after FEC; no alpha then).  A bad fec dict is a ValueError before anything is allocated or launched."""

@@ -15,7 +15,8 @@ import torch
 
 from . import channel as ch
 from . import shared_funcs as sfun
-from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info, dp_epilogue_llr, check_fec, fec_figures, label_bits  # noqa: F401
+from .engine import INFO_FLOAT, INFO_INT, DPEngine, dp_epilogue, dp_epilogue_compact, dp_epilogue_info, dp_epilogue_llr  # noqa: F401
+from .fec import check_fec, fec_figures, label_bits
 
 
 @dataclass
@@ -122,8 +123,8 @@ def run_dp_batch(runs, mod, sps, M_est, batch_len, N_frame_max, num_frames, flex
     want_llr:  also dict(llr[R,2,2b,N_out] f32, bits[R,2,2b,N_out] int8, hyp[R,2]) under "llr", on the device, for the LAST frame only (a whole
                sweep's LLRs would be tens of GB): engine.dp_epilogue_llr on that frame's soft-demapper alignment under the winning hypothesis
                of one dp_epilogue_info call (want_info's, when that is on) -- from q when the frame's q is materialised, from y otherwise --
-               and engine.label_bits of the frame's TX reference.  Every other output is the same with and without it.
-    fec:       dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75): also engine.ldpc_decode's figures of the LAST frame's LLRs (the pass
+               and fec.label_bits of the frame's TX reference.  Every other output is the same with and without it.
+    fec:       dict(code=fec.LdpcCode, t0=0, max_iter=20, alpha=0.75): also fec.ldpc_decode's figures of the LAST frame's LLRs (the pass
                want_llr runs; "llr" itself is returned only with want_llr) under "fec", on the device.  None: no output changes.
                quant=dict(bits, scale=None, app_bits=None, num=6, beta=0) in it decodes in fixed point (vaeq_ldpc_decode_q: what the scale of
                the LLRs costs after FEC; no alpha then).  A bad fec dict is a ValueError before anything is allocated or launched.

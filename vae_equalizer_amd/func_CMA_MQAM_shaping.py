@@ -9,7 +9,8 @@ import torch
 from . import channel as ch
 from .awgn_runs import check_generator, first_run, run_awgn_epochs
 from .dp_runs import default_device, resolve_generator
-from .engine import awgn_cma, awgn_cma_validate, awgn_track_info, awgn_track_llr, check_fec, label_bits
+from .engine import awgn_cma, awgn_cma_validate, awgn_track_info, awgn_track_llr
+from .fec import check_fec, label_bits
 from .func_VAELE_MQAM_shaping import SER_symb, awgn_batch_tables, awgn_tables  # noqa: F401  (SER_symb: identical text in both reference modules)
 
 rcfir, rrcfir = ch.rcfir, ch.rrcfir
@@ -101,8 +102,8 @@ def run_awgn_cma_batch(runs, mod, sps, M_est, N_valid, N_train, num_epochs, epe,
     demapped at var = 10^(-SNR/10), the VAE-LE's of the same sweep point (func_VAELE_MQAM_shaping.py:272).
     want_llr / fec: (SER_valid, info or None, extras), for the LAST evaluated validation only and on the device: with want_llr extras["llr"] =
     dict(llr[R,2b,N_valid] f32 = engine.awgn_track_llr on that validation's CPE output and shift, at the var and edge 11 of the info call and
-    under its hyp, bits int8 = engine.label_bits of its TX data, hyp[R]); with fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75,
-    depth=None) extras["fec"] = engine.ldpc_decode's figures of those LLRs. A quant=dict(bits, ...) in fec decodes in fixed point (vaeq_ldpc_decode_q).  Both off: no output changes."""
+    under its hyp, bits int8 = fec.label_bits of its TX data, hyp[R]); with fec = dict(code=fec.LdpcCode, t0=0, max_iter=20, alpha=0.75,
+    depth=None) extras["fec"] = fec.ldpc_decode's figures of those LLRs. A quant=dict(bits, ...) in fec decodes in fixed point (vaeq_ldpc_decode_q).  Both off: no output changes."""
     device = default_device() if device is None else torch.device(device)
     check_fec(fec)
     R = len(runs)

@@ -6,7 +6,8 @@ import torch
 from . import channel as ch
 from .awgn_runs import check_generator, first_run, run_awgn_epochs
 from .dp_runs import default_device, resolve_generator
-from .engine import INFO_FLOAT as INFO_FIGURES, INFO_INT as INFO_COUNTS, AWGNEngine, check_fec, label_bits  # noqa: F401  (the keys of engine.awgn_info, under this module's names)
+from .engine import INFO_FLOAT as INFO_FIGURES, INFO_INT as INFO_COUNTS, AWGNEngine  # noqa: F401  (the keys of engine.awgn_info, under this module's names)
+from .fec import check_fec, label_bits
 from .shared_funcs import _CHANNELS, qam_tables
 
 
@@ -132,8 +133,8 @@ def run_awgn_batch(runs, mod, sps, M_est, batch_len, N_valid, N_train, num_epoch
     bit_err, hyp int64), each [R, num_epochs // epe] on the CPU: engine.awgn_info in y-mode on the y and the shift of every validation launch.
     want_llr / fec: (SER_valid, info or None, extras), for the LAST evaluated validation only and on the device: with want_llr extras["llr"] =
     dict(llr[R,2b,N_valid] f32 = AWGNEngine.llr on that validation's y and shift under the hyp of AWGNEngine.info on them, bits int8 =
-    engine.label_bits of its TX data, hyp[R]); with fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) extras["fec"] =
-    engine.ldpc_decode's figures of those LLRs. A quant=dict(bits, ...) in fec decodes in fixed point (vaeq_ldpc_decode_q).  Both off: no output changes."""
+    fec.label_bits of its TX data, hyp[R]); with fec = dict(code=fec.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) extras["fec"] =
+    fec.ldpc_decode's figures of those LLRs. A quant=dict(bits, ...) in fec decodes in fixed point (vaeq_ldpc_decode_q).  Both off: no output changes."""
     device = default_device() if device is None else torch.device(device)
     check_fec(fec)
     R = len(runs)

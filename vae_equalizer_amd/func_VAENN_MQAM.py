@@ -14,7 +14,8 @@ from torch import nn
 from . import channel as ch
 from .awgn_runs import check_generator, first_run, run_awgn_epochs
 from .dp_runs import default_device
-from .engine import NNEngine, check_fec, label_bits
+from .engine import NNEngine
+from .fec import check_fec, label_bits
 from .func_VAELE_MQAM_shaping import SER_q, SER_symb, find_shift  # noqa: F401  (identical helpers in both reference files)
 from .shared_funcs import _CHANNELS, _LEVELS
 
@@ -151,8 +152,8 @@ def run_vaenn_batch(runs, mod, sps, M_est, kernel_1, kernel_2, batch_len, N_vali
     frame and the shift of every validation launch.
     want_llr / fec: (SER_valid, info or None, extras), for the LAST evaluated validation only and on the device: with want_llr extras["llr"] =
     dict(llr[R,2b,N_valid] f32 = NNEngine.llr on that validation's frame and shift under the hyp of NNEngine.info on them, bits int8 =
-    engine.label_bits of its TX data, hyp[R]); with fec = dict(code=engine.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) extras["fec"] =
-    engine.ldpc_decode's figures of those LLRs. A quant=dict(bits, ...) in fec decodes in fixed point (vaeq_ldpc_decode_q).  Both off: no output changes."""
+    fec.label_bits of its TX data, hyp[R]); with fec = dict(code=fec.LdpcCode, t0=0, max_iter=20, alpha=0.75, depth=None) extras["fec"] =
+    fec.ldpc_decode's figures of those LLRs. A quant=dict(bits, ...) in fec decodes in fixed point (vaeq_ldpc_decode_q).  Both off: no output changes."""
     device = default_device() if device is None else torch.device(device)
     R = len(runs)
     t = vaenn_tables(mod, channel, sps)

@@ -130,7 +130,7 @@ def fec_keys(fec_metrics):
 
 
 def fec_values(fec):
-    """engine.fec_figures' dict -> [R, 4] float32 on the CPU, in FEC_KEYS order: BER_post, FER, BER_pre and the mean over the codewords of iters;
+    """fec.fec_figures' dict -> [R, 4] float32 on the CPU, in FEC_KEYS order: BER_post, FER, BER_pre and the mean over the codewords of iters;
     [R, 6] with an outer code: then BER_outer and FER_outer, in FEC_OUTER_KEYS order."""
     cols = [fec["BER_post"], fec["FER"], fec["BER_pre"], fec["iters"].double().mean(1).float()]
     if "outer" in fec:
